@@ -12,13 +12,21 @@ kernel runs on the true 512x612 planes, network and loss on 512x640 (28 zero-pad
 columns; the reference itself cannot run W=612, trainer.py:107-108); images/s counts frames.
 Weak scaling: every rank processes its own batch of 16; gradients are all-reduced with RCCL.
 
-The JSON line also carries
+A plain run sets up, warms up, times exactly K eager steps and prints the headline line (`value`, `ms_per_step`,
+`final_loss`, ...).  --dump-outputs DIR also writes what the last timed step computed (see dump_outputs()).
+--full adds everything else below, each measured after the timed steps.
+
+With --full the JSON line also carries
+  graph        -- the same step replayed from a hipGraph (one GPU, or N > 1 with --dp_graph);
   roofline     -- the dominant kernel (implicit-GEMM conv: fp32 MFMA, or fp32 products from six bf16 MFMAs), algorithmic FLOPs / HIP-event time
                   of its launches in instrumented steps of the same workload (run serially on one stream:
                   in the timed steps weight-gradient kernels overlap data-gradient kernels, which would
                   stretch per-kernel durations), vs the 157.3 TFLOP/s fp32 matrix peak -- or, for the bf16x3 kernel, the
                   dense bf16 peak / 6 = 416.7 fp32-equivalent TFLOP/s (MI355X_MICROARCH.md); `kernels` lists the top four;
   precision    -- which products run where, the test that bounds the error, and the same step with PD_CONV_X3=0;
+  xolp_kernel  -- K1 (polar preprocessing) GB/s inside the step, back to back and at batch 128;
+  attention    -- with --attention: the attention kernels alone;
+  dp           -- N > 1: every rank's own step time and the exposed all-reduce;
   cpu_baseline -- the CPU oracle (oracle/: plain PyTorch-CPU restatement of the reference) timed on
                   this box's host cores on a bounded sample (rank 0, N == 1 only).
 """
@@ -61,12 +69,55 @@ def build_trainer(batch, height, width, log_dir):
     return Trainer(opts)
 
 
-def train_step(tr, batch):
+def train_step(tr, batch, keep=None):
+    """One train step; `keep` (a dict), when given, receives the step's outputs and losses."""
     tr.model_optimizer.zero_grad()
-    _, losses, _ = tr.process_batch(dict(batch), is_train=True)
+    outputs, losses, _ = tr.process_batch(dict(batch), is_train=True)
     losses["loss"].backward()
     tr.model_optimizer.step()
+    if keep is not None:
+        keep.update(outputs=outputs, losses=losses)
     return losses["loss"]
+
+
+DUMP_SAMPLE = 1 << 20        # elements: a larger array is dumped as this many seeded samples (4 MB in float32)
+
+
+def dump_outputs(out_dir, tr, keep):
+    """What the last timed step hands its caller, as <name>.npy: every loss (float64 scalars), every output map of the
+    network (disparities, depths; float32) and the parameters after the step's Adam update (float32, Trainer order,
+    flattened).  An array of more than DUMP_SAMPLE elements is replaced by a fixed sample: the elements at
+    DUMP_SAMPLE indices drawn with replacement from numpy's default_rng(0), sorted.  ~30 MB for the headline step;
+    more than 64 MB is refused."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(flat):
+        n = flat.numel()
+        if n <= DUMP_SAMPLE:
+            return flat
+        idx = np.sort(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+        return flat[torch.from_numpy(idx).to(flat.device)]
+
+    arrays = {}
+    for k, v in keep["losses"].items():
+        arrays[k.replace("/", "_s")] = np.float64(float(v.detach()))
+    seen = set()
+    for k in sorted(keep["outputs"], key=lambda k: (len(k), str(k))):    # ("disp", s) before its alias ("disp", 0, s),
+        # ("depth", 0, s) before ("mono_depth", 0, s)
+        t = keep["outputs"][k]
+        if not torch.is_tensor(t) or id(t) in seen:
+            continue
+        seen.add(id(t))
+        name = "_".join(str(p) for p in (k if isinstance(k, tuple) else (k,)))
+        t = t.detach()
+        arrays[name] = (sample(t.reshape(-1)) if t.numel() > DUMP_SAMPLE else t).float().cpu().numpy()
+    params = torch.cat([p.detach().reshape(-1) for p in tr.parameters_to_train])
+    arrays["params"] = sample(params).float().cpu().numpy()
+    total = sum(np.asarray(a).nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"dump of {total} bytes exceeds 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _oracle_step_factory(sample_batch):
@@ -190,10 +241,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline (graph replay, fp32-MFMA-only "
+                         "step, roofline, K1 GB/s, attention kernels, per-rank DP view, CPU baseline); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, output maps, a sample of the updated "
+                         "parameters) as DIR/<name>.npy")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_graph", action="store_true",
-                    help="time the eager step only (default on one GPU: the step is also captured into a hipGraph and reported "
-                         "beside the eager loop; `value` is always the eager loop)")
+                    help="with --full: time the eager step only (default on one GPU: the step is also captured into a hipGraph "
+                         "and reported beside the eager loop; `value` is always the eager loop)")
     ap.add_argument("--dp_graph", action="store_true",
                     help="with --gpus N > 1: also time the captured step under the gradient reducer (polardepth/graph.py, "
                          "segmented mode).  Off by default at N > 1: the scaling run's line must not depend on a capture "
@@ -206,8 +263,8 @@ def main():
                          "normals, supervised by the normals of the ground truth); not the headline workload")
     ap.add_argument("--bf16", action="store_true",
                     help="with --attention: the attention block on the bf16 matrix cores (configs[4] as specified: "
-                         "v_mfma_f32_32x32x16_bf16, fp32 softmax statistics and accumulators); the JSON line then carries "
-                         "an `attention` object graded against the bf16 MFMA peak")
+                         "v_mfma_f32_32x32x16_bf16, fp32 softmax statistics and accumulators); with --full the JSON line "
+                         "then carries an `attention` object graded against the bf16 MFMA peak")
     args = ap.parse_args()
     if args.attention:
         os.environ["PD_JOINT_ATTENTION"] = "1"
@@ -239,9 +296,9 @@ def main():
     batch[("pol", 0, 0)] = batch[("pol", 0, 0)][..., :FRAME_W].contiguous()      # true 512x612 planes for K1
     batch.pop("depth_gt"); batch.pop(("mask", 0, 0))
 
-    def timed_loop(step_fn):
+    def timed_loop(step_fn, keep=None):
         """W warm-up steps, then exactly K timed steps between barrier + synchronize on both sides; also the host time
-        of enqueueing one step into an empty queue."""
+        of enqueueing one step into an empty queue.  `keep` is handed to the last timed step."""
         t_host = None
         for i in range(args.warmup):
             if i == args.warmup - 1:
@@ -255,17 +312,53 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss = step_fn()
+        for i in range(args.steps):
+            loss = step_fn(keep if i == args.steps - 1 else None)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         return time.perf_counter() - t0, t_host, loss
 
-    dt, t_host, loss = timed_loop(lambda: train_step(tr, batch))
+    last = {} if args.dump_outputs else None
+    dt, t_host, loss = timed_loop(lambda keep=None: train_step(tr, batch, keep), last)
     eager = {"images_per_s": round(args.batch * args.steps / dt, 3), "ms_per_step": round(dt / args.steps * 1e3, 3),
              "host_enqueue_ms_per_step": None if t_host is None else round(t_host * 1e3, 2), "final_loss": round(float(loss.detach()), 6)}
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, tr, last)
+    del last
+
+    def headline(dt, loss_val):
+        result = {
+            "metric": "train images/sec (512x612, 3-encoder)", "value": round(args.batch * world * args.steps / dt, 3),
+            "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: full 3-encoder (augment_xolp+augment_normals), multi-scale loss "
+                                   "scales=[0,1,2,3], batch 16 per GPU, 512x612 frames (network/loss on 512x640 padded), "
+                                   "dropout 0.1, Adam lr 1e-4, fp32" + (" + joint-encoder attention (configs[4] variant)"
+                                                                       if args.attention else "") +
+                                   (" + separate normals decoder (arch1++_separate_normals_dec variant)" if args.normals_decoder else ""),
+                       "global_batch": args.batch * world, "height": H, "width": W, "frame_width": FRAME_W,
+                       "parallelism": f"dp{world}"},
+            "final_loss": round(loss_val, 6), "host_enqueue_ms_per_step": None if t_host is None else round(t_host * 1e3, 2),
+            "step_launch": "eager",
+            "eager": eager}
+        if args.bf16:
+            result["dtype"] = "f32 (network) + bf16 attention operands"
+            result["config"]["workload"] += " on the bf16 matrix cores"
+        return result
+
+    if not args.full:
+        if world > 1:
+            t = torch.tensor([dt], device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = t.item()
+        if rank == 0:
+            print(json.dumps(headline(dt, float(loss))), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
     # (before the graph section: a second trainer and the graph's memory pool slow this trainer's allocations afterwards)
     # the same eager step with every convolution on the fp32 MFMA (flags PD_CONV_FP32_MFMA of pd_conv2d* / pd_conv2d_wgrad):
     # what the bf16x3 kernels buy, measured in this process on this GPU
@@ -306,7 +399,7 @@ def main():
             for _ in range(max(extra, 0)):
                 gstep.step()
             saved_warmup, args.warmup = args.warmup, 0
-            dt_g, _, loss_g = timed_loop(lambda: gstep.step())
+            dt_g, _, loss_g = timed_loop(lambda keep=None: gstep.step())
             args.warmup = saved_warmup
             torch.cuda.synchronize()
             loss_g_val = float(loss_g.detach())      # (the loss tensor is a static buffer of the graph: read it before the next replay)
@@ -499,21 +592,9 @@ def main():
                      "peak_TFLOPs": peak, "fwd_frac": round(4 * fl / t_f / 1e9 / peak, 4),
                      "bwd_frac": round(10 * fl / t_b / 1e9 / peak, 4)}
 
-    result = {
-        "metric": "train images/sec (512x612, 3-encoder)", "value": round(args.batch * world * args.steps / dt, 3),
-        "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[2]: full 3-encoder (augment_xolp+augment_normals), multi-scale loss "
-                               "scales=[0,1,2,3], batch 16 per GPU, 512x612 frames (network/loss on 512x640 padded), "
-                               "dropout 0.1, Adam lr 1e-4, fp32" + (" + joint-encoder attention (configs[4] variant)"
-                                                                   if args.attention else "") +
-                               (" + separate normals decoder (arch1++_separate_normals_dec variant)" if args.normals_decoder else ""),
-                   "global_batch": args.batch * world, "height": H, "width": W, "frame_width": FRAME_W,
-                   "parallelism": f"dp{world}"},
-        "final_loss": round(loss_val, 6), "host_enqueue_ms_per_step": None if t_host is None else round(t_host * 1e3, 2),
-        "step_launch": "eager",
-        "eager": eager, "graph": graph_info,
+    result = headline(dt, loss_val)
+    result.update({
+        "graph": graph_info,
         "roofline": roofline, "xolp_kernel": xolp_kernel,
         "precision": {"accumulate": "f32",
                       "conv_products": "fp32 MFMA; the layers with >= 32 output channels and enough tiles to fill the chip (forward with zero "
@@ -529,14 +610,11 @@ def main():
                                   "oracle: disparities 2e-5, losses 1e-4, every gradient tensor within 2x the fp32 oracle's own distance "
                                   "from fp64)",
                       "fp32_mfma_only": fp32_only},
-    }
+    })
     if dp_info is not None:
         result["dp"] = dp_info
     if attention is not None:
         result["attention"] = attention
-        if args.bf16:
-            result["dtype"] = "f32 (network) + bf16 attention operands"
-            result["config"]["workload"] += " on the bf16 matrix cores"
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.attention and not args.normals_decoder:
         result["cpu_baseline"] = cpu_baseline()
     if rank == 0:

@@ -261,7 +261,7 @@ def test_resume_state_distinguishes_mid_epoch_from_end_of_epoch_checkpoints():
         t.model_optimizer = opt
         t.model_lr_scheduler = torch.optim.lr_scheduler.StepLR(opt, 2, 0.1)
         t.opt = types.SimpleNamespace(load_weights_folder=None, models_to_load=["m"], resume_state=True)
-        t.device = "cpu"
+        t.device = None     # host-only: the dropout step counter (DropoutState, device memory of a real Trainer) stays out
         t._load_into = lambda n, path, strict=False: None
         return t
     import tempfile

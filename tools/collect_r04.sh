@@ -5,15 +5,15 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ev4; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 STAGE=${1:-a}
 if [ "$STAGE" = a ]; then
-python3 $R/bench.py > $O/r04_bench_b16.json 2> $O/bench.err || exit 1
+python3 $R/bench.py --full > $O/r04_bench_b16.json 2> $O/bench.err || exit 1
 rm -rf $O/serial $O/overlap $O/fetch $O/write
-PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python3 $R/bench.py --steps 3 --warmup 1 --no_cpu_baseline --no_graph > $O/serial.log 2>&1 || exit 2
+PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python3 $R/bench.py --full --steps 3 --warmup 1 --no_cpu_baseline --no_graph > $O/serial.log 2>&1 || exit 2
 python3 $R/tools/step_breakdown.py $O/serial 70 > $O/r04_step_breakdown_serial.txt
 cp $(ls $O/serial/*/*kernel_stats.csv | head -1) $O/r04_bench_b16_kernel_stats_serial.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/overlap -- python3 $R/bench.py --steps 3 --warmup 1 --no_cpu_baseline --no_graph > $O/overlap.log 2>&1 || exit 3
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/overlap -- python3 $R/bench.py --full --steps 3 --warmup 1 --no_cpu_baseline --no_graph > $O/overlap.log 2>&1 || exit 3
 cp $(ls $O/overlap/*/*kernel_stats.csv | head -1) $O/r04_bench_b16_kernel_stats_overlap.csv
-PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 $R/bench.py --steps 1 --warmup 1 --no_cpu_baseline --no_graph > $O/fetch.log 2>&1 || exit 5
-PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 $R/bench.py --steps 1 --warmup 1 --no_cpu_baseline --no_graph > $O/write.log 2>&1 || exit 6
+PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 $R/bench.py --full --steps 1 --warmup 1 --no_cpu_baseline --no_graph > $O/fetch.log 2>&1 || exit 5
+PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 $R/bench.py --full --steps 1 --warmup 1 --no_cpu_baseline --no_graph > $O/write.log 2>&1 || exit 6
 python3 $R/tools/pmc_hbm_summary.py $O/fetch $O/write $O/r04_pmc_hbm_traffic.json > $O/pmc.log 2>&1
 rm -rf $O/serial $O/overlap $O/fetch $O/write
 echo done a; exit 0

@@ -1,8 +1,8 @@
 """Summarise two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) into HBM bytes per launch and kernel.
 
     cd /tmp && export TMPDIR=/tmp
-    PD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d out/fetch -- python3 bench.py --steps 1 --warmup 1 --no_cpu_baseline
-    PD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d out/write -- python3 bench.py --steps 1 --warmup 1 --no_cpu_baseline
+    PD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d out/fetch -- python3 bench.py --full --steps 1 --warmup 1 --no_cpu_baseline
+    PD_WGRAD_STREAM=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d out/write -- python3 bench.py --full --steps 1 --warmup 1 --no_cpu_baseline
     python tools/pmc_hbm_summary.py out/fetch out/write profiles/rNN_pmc_hbm_traffic.json
 
 FETCH_SIZE / WRITE_SIZE are reported in KB, summed over the XCDs; FETCH_SIZE is doubled (MI355X_MICROARCH.md:
@@ -66,7 +66,7 @@ if __name__ == "__main__":
             dom = pref
             break
     out = {"_about": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- "
-                     "PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 python bench.py --steps 1 --warmup 1 --no_cpu_baseline; KB per launch (mean over "
+                     "PD_WGRAD_STREAM=0 PD_ENCODER_STREAMS=0 python bench.py --full --steps 1 --warmup 1 --no_cpu_baseline; KB per launch (mean over "
                      "the launches of the run); hbm_bytes_per_launch = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
                      "(tools/pmc_hbm_summary.py)",
            "dominant": {"kernel": dom, **({"hbm_bytes_per_launch": kernels[dom]["hbm_bytes_per_launch"],

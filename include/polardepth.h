@@ -148,8 +148,19 @@ int pd_polar_theta(const void* rho, void* theta_d, void* theta_s1, void* theta_s
  *         PD_CONV_BF16X3     bf16-split products whenever the shape fits those kernels, whatever the tile count (tests);
  *         PD_CONV_WGRAD_SPLIT_IN_REGS  weight gradient: conv_wgrad_uni_kernel's in-register split instead of
  *                            conv_wgrad_x3c_kernel (kept for its test; slower than either);
- *         PD_CONV_GENERAL_KERNELS      the general gather kernels instead of the uniform-tap / scalar-pixel ones (tests).
- *       PD_CONV_FP32_MFMA and PD_CONV_BF16X3 exclude each other; unknown bits are an error.
+ *         PD_CONV_GENERAL_KERNELS      the general gather kernels instead of the uniform-tap / scalar-pixel ones (tests);
+ *         PD_CONV_BF16       opt-in bf16 arithmetic (training mode): on the layers the single-bf16 kernels take
+ *                            (pd_conv2d_uses_bf16 / pd_conv2d_wgrad_uses_bf16 non-zero) both operands are rounded ONCE to
+ *                            bf16, round-to-nearest-even (v_cvt_pk_bf16_f32: a NaN stays a NaN; FLT_MAX and everything
+ *                            from 0x1.ff8p127 up round to +-infinity), and each product is ONE v_mfma_f32_32x32x16_bf16
+ *                            with fp32 accumulation.  Storage stays fp32 (inputs, outputs, weights, gradients), and the
+ *                            epilogue (bias, activation, addend, BatchNorm partial sums) stays fp32.  bf16 denormal
+ *                            operands (fp32 inputs below 2^-126 in magnitude round to them) are KEPT, not flushed: the
+ *                            conversion and the MFMA preserve them on gfx950 (measured: 2^-130 x 2^20 gives 2^-110;
+ *                            tests/test_conv_bf16_gpu.py pins it).  Every other layer -- 1x1,
+ *                            strided, the 16-channel tail, out_scale, shapes outside the kernels' tile grids -- keeps the
+ *                            arithmetic it has without the flag: a per-layer fallback, not an error.
+ *       PD_CONV_FP32_MFMA and PD_CONV_BF16X3 exclude each other, PD_CONV_BF16 excludes both; unknown bits are an error.
  */
 #define PD_CONV_AUTO 0u
 #define PD_CONV_FP32_MFMA 1u
@@ -160,7 +171,8 @@ int pd_polar_theta(const void* rho, void* theta_d, void* theta_s1, void* theta_s
                                  * also where the halo-tile kernel (conv_halo_x3_kernel) fits: A/B measurement and tests */
 #define PD_CONV_WGRAD_ROW_WORKGROUPS 32u /* bf16-split 3x3 weight gradient with one filter row per workgroup (conv_wgrad_halo_x3_kernel)
                                          * also where the rolling-row kernel (conv_wgrad_roll_x3_kernel) fits: A/B measurement and tests */
-#define PD_CONV_FLAGS_ALL 63u
+#define PD_CONV_BF16 128u      /* single-bf16 products (above); bit 64 is unassigned */
+#define PD_CONV_FLAGS_ALL 191u
 int pd_conv2d_tile_m(long M, int Cout);
 long pd_conv2d_stats_rows(long M, int Cout);
 /* Non-zero (3: the halo-tile kernel conv_halo_x3_kernel -- stride 1, the output grid Ho x Wo (0 x 0: unknown, never 3) a whole
@@ -174,6 +186,12 @@ long pd_conv2d_stats_rows(long M, int Cout);
  * (ops._igemm_label) and bench.py's roofline object use it. */
 int pd_conv2d_uses_x3(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int act, int has_out_scale,
                       int Ho, int Wo, unsigned flags);
+/* 3 when pd_conv2d / pd_conv2d_add / pd_conv2d_rect run this shape on the single-bf16 form of the halo-tile kernel
+ * (conv_halo_bf16_kernel: one v_mfma_f32_32x32x16_bf16 per 32x32x16 block, operands rounded once) -- i.e. PD_CONV_BF16 is
+ * in `flags` and pd_conv2d_uses_x3 answers 3 for the same arguments without it; 0 otherwise (the layer keeps the arithmetic
+ * of pd_conv2d_uses_x3's answer).  Pure host logic, the same arguments as pd_conv2d_uses_x3. */
+int pd_conv2d_uses_bf16(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int act, int has_out_scale,
+                        int Ho, int Wo, unsigned flags);
 int pd_conv2d(const void* x, const void* w, const void* bias, const void* out_scale, void* y, void* stats,
               int N, int H, int W, int C, long sN, long sH, long sW, long sC,
               int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int mode, int act,
@@ -243,6 +261,12 @@ int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* dbias, void* 
  * the profiler label of a launch and bench.py's roofline object use it. */
 int pd_conv2d_wgrad_uses_x3(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho, int Wo,
                             unsigned flags);
+/* 3 (conv_wgrad_roll_bf16_kernel) or 2 (conv_wgrad_halo_bf16_kernel): pd_conv2d_wgrad runs this shape on the single-bf16 form
+ * of the kernel pd_conv2d_wgrad_uses_x3 names with the same code (PD_CONV_BF16 in `flags`); 0: the layer keeps the arithmetic it
+ * has without the flag.  The slice count of these kernels depends on the shape and `flags` only, never on ws_bytes:
+ * pd_conv2d_wgrad_workspace(M, Cout, K, flags) bytes hold it, and a larger workspace gives the same bits.  Pure host logic. */
+int pd_conv2d_wgrad_uses_bf16(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho, int Wo,
+                              unsigned flags);
 
 /* 7x7 / stride-2 / pad-3 stems (pre_encoders.py:54 ShallowEncoder.Conv1, torchvision resnet conv1) executed as a
  * 4x4 / stride-1 / pad-2 convolution over the space-to-depth input [N][H/2][W/2][4C] (4C is a multiple of 4 ->

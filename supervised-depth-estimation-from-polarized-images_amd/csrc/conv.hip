@@ -1343,6 +1343,13 @@ extern "C" int pd_conv2d_uses_x3(long M, int Co, int C, int KH, int KW, int stri
     return x3_eligible(a, true);
 }
 
+// PD_CONV_BF16 changes the arithmetic of the halo-tile kernel only (conv2d_impl below): its layers run the one-term form
+extern "C" int pd_conv2d_uses_bf16(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int act,
+                                   int has_out_scale, int Ho, int Wo, unsigned flags) {
+    if (!(flags & PD_CONV_BF16) || !pd::conv_flags_ok(flags)) return 0;
+    return pd_conv2d_uses_x3(M, Co, C, KH, KW, stride, pad, mode, act, has_out_scale, Ho, Wo, flags) == 3 ? 3 : 0;
+}
+
 extern "C" int pd_conv2d_tile_m(long M, int Co) {
     if (Co <= 32) return 128;   // 128x32 tile: four waves of one 32x32 MFMA tile each
     return M >= 64 * 1024 ? 128 : 64;
@@ -2552,6 +2559,15 @@ extern "C" int pd_conv2d_wgrad_uses_x3(long M, int Co, int C, int KH, int KW, in
     return x3c;
 }
 
+// PD_CONV_BF16: the one-term forms of the halo-tile / rolling-row kernels, with the slice count of the workspace the flags ask
+// for (never of the caller's ws_bytes: a larger workspace must not change the summation order)
+extern "C" int pd_conv2d_wgrad_uses_bf16(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho,
+                                         int Wo, unsigned flags) {
+    if (!(flags & PD_CONV_BF16) || !pd::conv_flags_ok(flags)) return 0;
+    const int r = pd_conv2d_wgrad_uses_x3(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags);
+    return r >= 2 ? r : 0;
+}
+
 extern "C" int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* dbias, void* workspace, size_t ws_bytes,
                                int N, int H, int W, int C, long sN, long sH, long sW, long sC,
                                int Ho, int Wo, int Co, int KH, int KW, int stride, int pad, int mode,
@@ -2584,12 +2600,14 @@ extern "C" int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* db
     hipStream_t st = (hipStream_t)stream;
     if (wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL)) && wgrad_halo_eligible(a, vec)) {
         // halo-tile kernel: its slice count never exceeds what the workspace holds
+        // (PD_CONV_BF16, the one-term forms: the slice count of the workspace the flags ask for, whatever ws_bytes says)
+        const bool bf16 = (flags & PD_CONV_BF16) != 0;
         const size_t per_slice = ((size_t)Co * a.K + Co) * sizeof(float);
-        const int s_cap = (int)std::min<size_t>(ws_bytes / per_slice, 1 << 20);
+        const int s_cap = (int)std::min<size_t>((bf16 ? need : ws_bytes) / per_slice, 1 << 20);
         WgradRollPlan rp;
         // 3x3 with long tile columns: all three filter rows per workgroup, input rows rolling through LDS
-        const int S = !(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, vec, s_cap, rp) ? launch_wgrad_roll(a, rp, st, dbias != nullptr)
-                                                                                             : launch_wgrad_halo(a, s_cap, st, dbias != nullptr);
+        const int S = !(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, vec, s_cap, rp) ? launch_wgrad_roll(a, rp, st, dbias != nullptr, bf16)
+                                                                                             : launch_wgrad_halo(a, s_cap, st, dbias != nullptr, bf16);
         a.bpart = dbias ? a.part + (size_t)S * Co * a.K : nullptr;
         int rc = pd::check_launch("pd_conv2d_wgrad");
         if (rc) return rc;

@@ -21,19 +21,21 @@
 // CO32 (round 4: the decoder's 96 -> 32 and 64 -> 32 layers): a workgroup owns 32 output channels; its wave pairs take the
 // two 16-pixel steps of a tile instead of two output-channel blocks and write two partial slices (2 s, 2 s + 1).  C % 32 == 0:
 // the upper 32-channel block of the last 64-channel input block may be empty (its wave idles, its loads are masked).
+// TERMS = 1: the single-bf16 form (PD_CONV_BF16, "conv_wgrad_halo_bf16_kernel"): one RNE-rounded plane per operand, the hi x hi
+// product only -- KS MFMAs per 16-pixel step --, a third of the planes; the next tile's items are staged behind each step's MFMAs.
 namespace wgh {
 constexpr int NPX = 32;                                                  // pixels per tile: TR rows x TW columns, 2 MFMA k-steps
 // TW = 32 | 16 | 8 | 4 (the widest that divides Wo): 1 x 32, 2 x 16, 4 x 8 or 8 x 4 pixel tiles -- a 16-pixel step is then half a
 // row, a row, two or four rows; either way the step's pixels are the tile's row-major pixels 16 ks .. 16 ks + 15, in runs of four
 // consecutive columns (what one transposed read takes).  (8 x 4: the 16x20 planes of the 512-channel layers.)
-template <int KS, int TW, bool CO32> struct Geo {
+template <int KS, int TW, bool CO32, int TERMS = 3> struct Geo {
     static constexpr int TR = NPX / TW;
     static constexpr int HW = TW + KS - 1;                               // X columns per tile row
     static constexpr int XPX = TR * HW;                                  // X pixels per tile (one filter row: no vertical halo)
     static constexpr int NIX = (XPX * 16 + NT - 1) / NT;                 // 16-byte X items per thread (64 channels = 16 quads per pixel)
     static constexpr int NCOB = CO32 ? 1 : 2;                            // 32-channel blocks of dY per workgroup
-    static constexpr unsigned DP_BYTES = 3 * NCOB * NPX * 64;            // dY planes of one tile: [term][co block][pixel][32 ch x 2 B]
-    static constexpr unsigned XP_BYTES = 3 * 2 * XPX * 64;               // X planes of one tile: [term][ci block][pixel][32 ch x 2 B]
+    static constexpr unsigned DP_BYTES = TERMS * NCOB * NPX * 64;        // dY planes of one tile: [term][co block][pixel][32 ch x 2 B]
+    static constexpr unsigned XP_BYTES = TERMS * 2 * XPX * 64;           // X planes of one tile: [term][ci block][pixel][32 ch x 2 B]
     static constexpr unsigned BUF_BYTES = DP_BYTES + XP_BYTES;           // two tiles live in LDS: the one multiplied, the one being written
     static constexpr unsigned LDS_BYTES = 2 * BUF_BYTES;
 };
@@ -54,10 +56,10 @@ struct WgradHaloArgs {
     int tiles_w, tiles_h, ntiles_total, tiles_per_slice;
 };
 
-template <int KS, int TW, bool BIAS, bool CO32>
+template <int KS, int TW, bool BIAS, bool CO32, int TERMS = 3>
 __global__ __launch_bounds__(NT, KS == 3 ? 3 : 2) void conv_wgrad_halo_x3_kernel(const WgradHaloArgs ha) {
     using namespace wgh;
-    using G = Geo<KS, TW, CO32>;
+    using G = Geo<KS, TW, CO32, TERMS>;
     constexpr int HW = G::HW, XPX = G::XPX, NIX = G::NIX, TR = G::TR, NCOB = G::NCOB, ND = CO32 ? 1 : 2, BCO = 32 * NCOB;
     constexpr unsigned DP_BYTES = G::DP_BYTES, BUF_BYTES = G::BUF_BYTES;
     static_assert(NIX <= 3 && 16 * (NIX - 1) < XPX, "X items per thread");
@@ -145,6 +147,10 @@ __global__ __launch_bounds__(NT, KS == 3 ? 3 : 2) void conv_wgrad_halo_x3_kernel
     const bool do_bias = BIAS && a.bpart != nullptr && kh == 0 && cb == 0;
     auto put3 = [&](const float4 v, unsigned off, unsigned plane_stride, unsigned sg) {
         uint2 h, m, l;
+        if constexpr (TERMS == 1) {                 // one term: the RNE-rounded value
+            *reinterpret_cast<uint2*>(lds_c + off) = uint2{x3::cvt_pk_bf16(v.x, v.y) ^ sg, x3::cvt_pk_bf16(v.z, v.w) ^ sg};
+            return;
+        }
         x3::split2(v.x, v.y, h.x, m.x, l.x);
         x3::split2(v.z, v.w, h.y, m.y, l.y);
         *reinterpret_cast<uint2*>(lds_c + off) = uint2{h.x ^ sg, h.y ^ sg};
@@ -206,20 +212,31 @@ __global__ __launch_bounds__(NT, KS == 3 ? 3 : 2) void conv_wgrad_halo_x3_kernel
         for (int ks = 0; ks < (CO32 ? 1 : 2); ++ks) {
             x3::bf16x8 fa[3];
 #pragma unroll
-            for (int tm = 0; tm < 3; ++tm)
+            for (int tm = 0; tm < TERMS; ++tm)
                 fa[tm] = bf(tr_read(lds_a, BUF * BUF_BYTES + (unsigned)(tm * NCOB * NPX * 64 + ks * 16 * 64)),
                             tr_read(lds_a, BUF * BUF_BYTES + (unsigned)(tm * NCOB * NPX * 64 + ks * 16 * 64 + 4 * 64)));
             x3::bf16x8 fb[KS][3];
 #pragma unroll
             for (int kw = 0; kw < KS; ++kw)
 #pragma unroll
-                for (int tm = 0; tm < 3; ++tm) {
+                for (int tm = 0; tm < TERMS; ++tm) {
                     const int row0 = TW == 32 ? 0 : TW == 16 ? ks : TW == 8 ? 2 * ks : 4 * ks, col0 = TW == 32 ? 16 * ks : 0;
                     const unsigned o = BUF * BUF_BYTES + (unsigned)(tm * 2 * XPX * 64 + (row0 * HW + col0 + kw) * 64);
                     fb[kw][tm] = bf(tr_read(lds_b, o), tr_read(lds_b, o + RUN2 * 64));
                 }
             // products largest first, the taps interleaved so that consecutive MFMAs never share an accumulator; one item of
             // the next tile behind every second group of KS MFMAs
+            if constexpr (TERMS == 1) {
+                if (w_live) {
+#pragma unroll
+                    for (int kw = 0; kw < KS; ++kw)
+                        acc[kw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[kw][0], acc[kw], 0, 0, 0);
+                }
+                // the next tile's items behind this step's MFMAs (CO32: one step, every item; else 3 + 2)
+                if (CO32 || ks == 0) { item(nxt, PD_I(0)); item(nxt, PD_I(1)); item(nxt, PD_I(2)); }
+                if (CO32 || ks == 1) { item(nxt, PD_I(3)); item(nxt, PD_I(4)); }
+                continue;
+            }
 #pragma unroll
             for (int pr = 0; pr < 6; ++pr) {
                 const int ta = pr == 0 ? 0 : pr == 1 ? 0 : pr == 2 ? 1 : pr == 3 ? 0 : pr == 4 ? 1 : 2;
@@ -316,7 +333,7 @@ static int wgrad_halo_slices_bound(int Co, int K) {
 }
 
 // s_cap: partial rows the caller's workspace holds; returns the partial rows written
-static int launch_wgrad_halo(WgradArgs a, int s_cap, hipStream_t st, bool bias) {
+static int launch_wgrad_halo(WgradArgs a, int s_cap, hipStream_t st, bool bias, bool bf16 = false) {
     WgradHaloArgs ha;
     const bool co32 = wgrad_halo_co32(a);
     ha.ncb = (a.C + 63) / 64;
@@ -338,8 +355,11 @@ static int launch_wgrad_halo(WgradArgs a, int s_cap, hipStream_t st, bool bias) 
     ha.g = a;
     const long nwg = (long)per_slice_wgs * S;
     const dim3 grid((unsigned)((nwg + 7) / 8 * 8)), block(NT);
-#define PD_WGH(KSV, TWV, C32) do { if (bias) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, true, C32>), grid, block, 0, st, ha); \
-                                else hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, false, C32>), grid, block, 0, st, ha); } while (0)
+#define PD_WGH(KSV, TWV, C32) do { \
+        if (bf16) { if (bias) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, true, C32, 1>), grid, block, 0, st, ha); \
+                    else hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, false, C32, 1>), grid, block, 0, st, ha); } \
+        else if (bias) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, true, C32>), grid, block, 0, st, ha); \
+        else hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, false, C32>), grid, block, 0, st, ha); } while (0)
     if (co32) PD_WGH(3, 32, true);
     else if (a.KH == 3) { if (tw == 32) PD_WGH(3, 32, false); else if (tw == 16) PD_WGH(3, 16, false); else if (tw == 8) PD_WGH(3, 8, false); else PD_WGH(3, 4, false); }
     else { if (tw == 32) PD_WGH(5, 32, false); else if (tw == 16) PD_WGH(5, 16, false); else PD_WGH(5, 8, false); }

@@ -9,15 +9,18 @@
 // a tile, 2 halo columns): they sit in a ring of four groups in LDS, so per tile ONE new group and one dY tile are staged and
 // split -- 5 items per 108 MFMAs.  230 registers (two workgroups per CU, as the 5x5 kernel), 77 KB of LDS.
 // Slices are row ranges of one tile column; a slice starts with three groups (7 % more staging at 43 tiles per slice).
+// TERMS = 1: the single-bf16 form (PD_CONV_BF16, "conv_wgrad_roll_bf16_kernel"): one RNE-rounded plane per operand, the hi x hi
+// product only (18 MFMAs per tile and wave instead of 108), a third of the planes (26 KB of LDS); the staging of one item per
+// (step, filter row) stays where it was, behind that pair's MFMAs.
 namespace wgr {
 using namespace wgh;
-template <int TW> struct RGeo {
+template <int TW, int TERMS = 3> struct RGeo {
     static constexpr int TR = NPX / TW;                                  // rows per tile: 1 | 2
     static constexpr int HW = TW + 2;
     static constexpr int GPX = TR * HW;                                  // pixels of one input row group
     static constexpr int NIX = (GPX * 16 + NT - 1) / NT;                 // 16-byte X items per thread and group
-    static constexpr unsigned DP_BYTES = 3 * 2 * NPX * 64;               // dY planes of one tile: [term][co block][pixel][32 ch x 2 B]
-    static constexpr unsigned GS_BYTES = 3 * 2 * GPX * 64;               // X planes of one group: [term][ci block][pixel][32 ch x 2 B]
+    static constexpr unsigned DP_BYTES = TERMS * 2 * NPX * 64;           // dY planes of one tile: [term][co block][pixel][32 ch x 2 B]
+    static constexpr unsigned GS_BYTES = TERMS * 2 * GPX * 64;           // X planes of one group: [term][ci block][pixel][32 ch x 2 B]
     static constexpr unsigned X_BASE = 2 * DP_BYTES;
     static constexpr unsigned LDS_BYTES = X_BASE + 4 * GS_BYTES;
 };
@@ -30,10 +33,10 @@ struct WgradRollArgs {
     int spc, rps;                 // slices per tile column, tile rows per slice
 };
 
-template <int TW, bool BIAS>
+template <int TW, bool BIAS, int TERMS = 3>
 __global__ __launch_bounds__(NT, 2) void conv_wgrad_roll_x3_kernel(const WgradRollArgs ra) {
     using namespace wgr;
-    using G = RGeo<TW>;
+    using G = RGeo<TW, TERMS>;
     constexpr int HW = G::HW, GPX = G::GPX, NIX = G::NIX, TR = G::TR;
     constexpr unsigned DP_BYTES = G::DP_BYTES, GS_BYTES = G::GS_BYTES, X_BASE = G::X_BASE;
     static_assert(NIX == 3 && 16 * (NIX - 1) < GPX, "X items per thread");
@@ -98,6 +101,10 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_roll_x3_kernel(const WgradRo
     const bool do_bias = BIAS && a.bpart != nullptr && cb == 0;
     auto put3 = [&](const float4 v, unsigned off, unsigned plane_stride, unsigned sg) {
         uint2 h, m, l;
+        if constexpr (TERMS == 1) {                 // one term: the RNE-rounded value
+            *reinterpret_cast<uint2*>(lds_c + off) = uint2{x3::cvt_pk_bf16(v.x, v.y) ^ sg, x3::cvt_pk_bf16(v.z, v.w) ^ sg};
+            return;
+        }
         x3::split2(v.x, v.y, h.x, m.x, l.x);
         x3::split2(v.z, v.w, h.y, m.y, l.y);
         *reinterpret_cast<uint2*>(lds_c + off) = uint2{h.x ^ sg, h.y ^ sg};
@@ -169,7 +176,7 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_roll_x3_kernel(const WgradRo
         for (int ks = 0; ks < 2; ++ks) {
             x3::bf16x8 fa[3];
 #pragma unroll
-            for (int tm = 0; tm < 3; ++tm)
+            for (int tm = 0; tm < TERMS; ++tm)
                 fa[tm] = bf(tr_read(lds_a, BUF * DP_BYTES + (unsigned)(tm * 2 * NPX * 64 + ks * 16 * 64)),
                             tr_read(lds_a, BUF * DP_BYTES + (unsigned)(tm * 2 * NPX * 64 + ks * 16 * 64 + 4 * 64)));
 #pragma unroll
@@ -183,18 +190,18 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_roll_x3_kernel(const WgradRo
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-                    for (int tm = 0; tm < 3; ++tm) {
+                    for (int tm = 0; tm < TERMS; ++tm) {
                         const unsigned o = (unsigned)(tm * 2 * GPX * 64 + (row * HW + col0 + kw) * 64);
                         fb[kw][tm] = bf(tr_read(bb[d], o), tr_read(bb[d], o + 4 * 64));
                     }
 #pragma unroll
-                for (int pr = 0; pr < 6; ++pr) {
+                for (int pr = 0; pr < (TERMS == 3 ? 6 : 1); ++pr) {
                     const int ta = pr == 0 ? 0 : pr == 1 ? 0 : pr == 2 ? 1 : pr == 3 ? 0 : pr == 4 ? 1 : 2;
                     const int tb = pr == 0 ? 0 : pr == 1 ? 1 : pr == 2 ? 0 : pr == 3 ? 2 : pr == 4 ? 1 : 0;
 #pragma unroll
                     for (int kw = 0; kw < 3; ++kw)
                         acc[kh][kw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ta], fb[kw][tb], acc[kh][kw], 0, 0, 0);
-                    if (pr == 2) {                      // one item of the next tile / group behind the first half of every (step, filter row)
+                    if (pr == (TERMS == 3 ? 2 : 0)) {                      // one item of the next tile / group behind the first half of every (step, filter row)
                         if (it < 2) { put_d(it, BUF ^ 1u); dv[it] = ld_d(it); }
                         else if (it < 2 + NIX) { put_x(xv[it - 2], it - 2, slot_w); xv[it - 2] = ld_x(it - 2); }
                         ++it;
@@ -272,7 +279,7 @@ static int wgrad_roll_slices_bound(int Co, int K) {
     return 512 / (per > 0 ? per : 1);
 }
 
-static int launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st, bool bias) {
+static int launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st, bool bias, bool bf16 = false) {
     WgradRollArgs ra;
     ra.ncb = a.C / 64;
     a.ctiles = a.Co / 64;
@@ -282,8 +289,11 @@ static int launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st
     ra.g = a;
     const long nwg = (long)ra.ncb * a.ctiles * p.S;
     const dim3 grid((unsigned)((nwg + 7) / 8 * 8)), block(NT);
-#define PD_WGR(TWV) do { if (bias) hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, true>), grid, block, 0, st, ra); \
-                         else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, false>), grid, block, 0, st, ra); } while (0)
+#define PD_WGR(TWV) do { \
+        if (bf16) { if (bias) hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, true, 1>), grid, block, 0, st, ra); \
+                    else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, false, 1>), grid, block, 0, st, ra); } \
+        else if (bias) hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, true>), grid, block, 0, st, ra); \
+        else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, false>), grid, block, 0, st, ra); } while (0)
     if (p.tw == 32) PD_WGR(32); else PD_WGR(16);
 #undef PD_WGR
     return p.S;

@@ -28,29 +28,35 @@
 //     stems (C = 36 / 12 / 8) get whole 16-channel groups (144 / 48 / 32 floats per filter row) where the per-tap form would
 //     leave their last group 1/4 .. 3/4 empty.  Only the first / last columns of the IMAGE see a window that leaves its row:
 //     per halo item two 2-bit counts (pixels missing on the left / right) mask those quads, in the border tiles only.
+// TERMS = 1 is the single-bf16 form (PD_CONV_BF16, "conv_halo_bf16_kernel" in the profiler): every element is rounded ONCE to
+// bf16 (v_cvt_pk_bf16_f32, RNE -- the hi term of the split) into ONE A plane and ONE weight plane per buffer, and a chunk is the
+// hi x hi product only: 4 (NCB = 1: 2) MFMAs, 2 + NCB ds_read_b128.  The MFMAs no longer cover the staging, so the one-term
+// chunk does its vector work in one block behind them instead of threading it between them.  The sign alternation stays.
 namespace x3h {
 constexpr int CK = 16;
 // TW = 32 | 16 | 8: the 256-pixel output tile is 8 x 32, 16 x 16 or 32 x 8; an MFMA row block (32 pixels) is then one row,
 // two rows of 16 or four rows of 8 -- the widest tile that divides the output grid
-template <int KH, int KW, int TW, int NCB> struct Geo {
+template <int KH, int KW, int TW, int NCB, int TERMS = 3> struct Geo {
     static constexpr int TR = 256 / TW, BR = 32 / TW;
     static constexpr int HW = TW + KW - 1, HH = TR + KH - 1, HP = HW * HH;
     static constexpr unsigned BP_BYTES = 32 * NCB * CK * 2;          // one weight plane: (32 NCB) x 16 bf16
     static constexpr int NI = (HP * 4 + NT - 1) / NT;                 // 16-byte halo items per thread and channel group
-    static constexpr unsigned AP_BYTES = 3 * 2 * HP * 16;             // A planes: [term][half][halo pixel] x 16 B
+    static constexpr unsigned AP_BYTES = TERMS * 2 * HP * 16;         // A planes: [term][half][halo pixel] x 16 B
     static constexpr unsigned BP_BASE = AP_BYTES;                     // weight planes: [buffer][term] x 64 x 16 bf16
-    static constexpr unsigned LDS_BYTES = BP_BASE + 2 * 3 * BP_BYTES;
+    static constexpr unsigned EPI_BYTES = 4 * 64 * 32 * 4 + 4 * 64 * 2 * 4;     // the epilogue's transposition tiles reuse the planes
+    static constexpr unsigned PLANE_BYTES = BP_BASE + 2 * TERMS * BP_BYTES;
+    static constexpr unsigned LDS_BYTES = PLANE_BYTES > EPI_BYTES ? PLANE_BYTES : EPI_BYTES;
 };
 }  // namespace x3h
 
-template <int MODE, int KH, int KW, int TW, int NCB, bool ROWWIN>
+template <int MODE, int KH, int KW, int TW, int NCB, bool ROWWIN, int TERMS = 3>
 __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
     using namespace x3h;
-    using G = Geo<KH, KW, TW, NCB>;
+    using G = Geo<KH, KW, TW, NCB, TERMS>;
+    static_assert(TERMS == 1 || TERMS == 3, "bf16 terms per operand");
     constexpr int HW = G::HW, HP = G::HP, NI = G::NI, T = KH * KW, TR = G::TR, BR = G::BR, BNW = 32 * NCB;
     constexpr unsigned BP_BASE = G::BP_BASE, BP_BYTES = G::BP_BYTES;
     static_assert(!ROWWIN || (KW == 1 && MODE == MODE_ZERO), "row windows: zero padding, the filter row folded into the channels");
-    static_assert(G::LDS_BYTES >= 4 * 64 * 32 * 4 + 4 * 64 * 2 * 4, "the epilogue's transposition tiles reuse the ring");
     __shared__ __attribute__((aligned(16))) float smem_all[G::LDS_BYTES / 4];
 
     // ---- tile: XCD-aware order as everywhere (consecutive logical tiles -- neighbours in x, then y -- share an L2)
@@ -191,6 +197,16 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
     auto split_b0 = [&]() {                     // chunk 0 -> planes 0 (prologue only; the loop threads it)
         const float4 w4 = NCB == 2 ? wq : make_float4(wq2[0].x, wq2[0].y, 0.f, 0.f);
         uint2 h, m, l;
+        if constexpr (TERMS == 1) {                 // one term: the RNE-rounded value
+            h.x = x3::cvt_pk_bf16(w4.x, w4.y);
+            if constexpr (NCB == 2) {
+                h.y = x3::cvt_pk_bf16(w4.z, w4.w);
+                *reinterpret_cast<uint2*>(lds_c + sp_off) = uint2{h.x ^ wsign, h.y ^ wsign};
+            } else {
+                *reinterpret_cast<unsigned*>(lds_c + sp_off) = h.x ^ wsign;
+            }
+            return;
+        }
         x3::split2(w4.x, w4.y, h.x, m.x, l.x);
         if constexpr (NCB == 2) {
             x3::split2(w4.z, w4.w, h.y, m.y, l.y);
@@ -206,7 +222,10 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
     // one halo item: registers -> three plane slots (every element split once per tile)
     auto halo_item = [&](auto i_tag) {
         constexpr int I = decltype(i_tag)::value;
-        if constexpr (I < NI) {
+        if constexpr (I < NI && TERMS == 1) {
+            const uint2 h = {x3::cvt_pk_bf16(hv[I].x, hv[I].y), x3::cvt_pk_bf16(hv[I].z, hv[I].w)};
+            if (I < NI - 1 || hlast_ok) *reinterpret_cast<uint2*>(lds_c + hdst0 + 1024u * I) = h;
+        } else if constexpr (I < NI) {
             uint2 h, m, l;
             x3::split2(hv[I].x, hv[I].y, h.x, m.x, l.x);
             x3::split2(hv[I].z, hv[I].w, h.y, m.y, l.y);
@@ -248,6 +267,40 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
         if (halo_issue) halo_load(s_g + 1);
         const int ey = MODE == MODE_TRANSPOSED ? KH - 1 - s_kh : s_kh, ex = MODE == MODE_TRANSPOSED ? KW - 1 - s_kw : s_kw;
         const unsigned fa = fa_base + (unsigned)((ey * HW + ex) * 16);
+        if constexpr (TERMS == 1) {
+            // single bf16: both row blocks' A fragments and the NCB B fragments, 2 NCB MFMAs; then the next chunk's weights
+            // (rounded once, one plane) and, LAST, the next group's halo -- behind the barrier that frees the A planes
+            u32x4 a1[2], b1[NCB];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a1[i] = *reinterpret_cast<const u32x4*>(lds_c + fa + (unsigned)(i * BR * HW * 16));
+#pragma unroll
+            for (int j = 0; j < NCB; ++j)
+                b1[j] = *reinterpret_cast<const u32x4*>(lds_c + fb_off + (BUF * BP_BYTES + (unsigned)j * 32 * CK * 2));
+            if (LAST) __syncthreads();              // every wave holds its fragments of this group's last tap: the A plane is free
+#pragma unroll
+            for (int j = 0; j < NCB; ++j)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(a1[i]), bf(b1[j]), acc[i][j], 0, 0, 0);
+            if constexpr (NCB == 2) {
+                const uint2 h = {x3::cvt_pk_bf16(ws[0], ws[1]), x3::cvt_pk_bf16(ws[2], ws[3])};
+                load_b(std::integral_constant<int, 0>{});
+                *reinterpret_cast<uint2*>(lds_c + sp_off + NXT * BP_BYTES) = uint2{h.x ^ wsign, h.y ^ wsign};
+            } else {
+                const unsigned h = x3::cvt_pk_bf16(ws[0], ws[1]);
+                load_b(std::integral_constant<int, (int)NXT>{});
+                *reinterpret_cast<unsigned*>(lds_c + sp_off + NXT * BP_BYTES) = h ^ wsign;
+            }
+            if (LAST) {
+#define PD_I(n) std::integral_constant<int, n>{}
+                halo_item(PD_I(0)); halo_item(PD_I(1)); halo_item(PD_I(2)); halo_item(PD_I(3)); halo_item(PD_I(4)); halo_item(PD_I(5)); halo_item(PD_I(6));
+#undef PD_I
+            }
+            static_assert(NI <= 7, "halo items per thread");
+            if (++s_kw == KW) { s_kw = 0; if (++s_kh == KH) { s_kh = 0; ++s_g; } }
+            __syncthreads();
+            return;
+        }
         u32x4 av[2][3], fb[NCB][3];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -453,7 +506,9 @@ static bool x3_halo_plan(const ConvArgs& a, HaloPlan& p) {
 }
 static bool x3_halo_eligible(const ConvArgs& a) { HaloPlan p; return x3_halo_plan(a, p); }
 
-static int launch_conv_x3_halo(ConvArgs& a, hipStream_t st) {
+// TERMS = 1: the single-bf16 form (PD_CONV_BF16)
+template <int TERMS>
+static int launch_conv_x3_halo_t(ConvArgs& a, hipStream_t st) {
     HaloPlan p;
     if (!x3_halo_plan(a, p)) return pd::fail(PD_EINVAL, "pd_conv2d: internal: halo plan");
     const int tw = p.tw;
@@ -466,10 +521,10 @@ static int launch_conv_x3_halo(ConvArgs& a, hipStream_t st) {
     // three (3x3 only: 53 KB, 166 registers; 3x3x64 @256x320 forward 154 -> 185 TF, data gradient 185 -> 200) -> weights staged
     // through registers, no ring: 45 KB / 52.5 KB, three workgroups per CU for 5x5 as well.
 #define PD_HALO(KHV, KWV, TWV, NCBV, RW) do { \
-        if (a.mode == MODE_ZERO) hipLaunchKernelGGL((conv_halo_x3_kernel<MODE_ZERO, KHV, KWV, TWV, NCBV, RW>), grid, block, 0, st, a); \
+        if (a.mode == MODE_ZERO) hipLaunchKernelGGL((conv_halo_x3_kernel<MODE_ZERO, KHV, KWV, TWV, NCBV, RW, TERMS>), grid, block, 0, st, a); \
         else if constexpr (!RW) { \
-            if (a.mode == MODE_REFLECT) hipLaunchKernelGGL((conv_halo_x3_kernel<MODE_REFLECT, KHV, KWV, TWV, NCBV, false>), grid, block, 0, st, a); \
-            else hipLaunchKernelGGL((conv_halo_x3_kernel<MODE_TRANSPOSED, KHV, KWV, TWV, NCBV, false>), grid, block, 0, st, a); } } while (0)
+            if (a.mode == MODE_REFLECT) hipLaunchKernelGGL((conv_halo_x3_kernel<MODE_REFLECT, KHV, KWV, TWV, NCBV, false, TERMS>), grid, block, 0, st, a); \
+            else hipLaunchKernelGGL((conv_halo_x3_kernel<MODE_TRANSPOSED, KHV, KWV, TWV, NCBV, false, TERMS>), grid, block, 0, st, a); } } while (0)
     if (p.rowwin) PD_HALO(4, 1, 32, 2, true);
     else if (p.ncb == 1 && a.KH == 3) { if (tw == 32) PD_HALO(3, 3, 32, 1, false); else PD_HALO(3, 3, 16, 1, false); }
     else if (p.ncb == 1) PD_HALO(5, 5, 8, 1, false);
@@ -477,4 +532,7 @@ static int launch_conv_x3_halo(ConvArgs& a, hipStream_t st) {
     else { if (tw == 32) PD_HALO(5, 5, 32, 2, false); else if (tw == 16) PD_HALO(5, 5, 16, 2, false); else PD_HALO(5, 5, 8, 2, false); }
 #undef PD_HALO
     return pd::check_launch("pd_conv2d");
+}
+static int launch_conv_x3_halo(ConvArgs& a, hipStream_t st) {
+    return (a.flags & PD_CONV_BF16) ? launch_conv_x3_halo_t<1>(a, st) : launch_conv_x3_halo_t<3>(a, st);
 }

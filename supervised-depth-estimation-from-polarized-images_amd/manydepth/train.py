@@ -13,6 +13,10 @@ from .options import MonodepthOptions
 
 def main():
     opts = MonodepthOptions().parse()
+    # PD_BF16=1: the opt-in bf16 training mode of the convolutions (and of the attention variant); the reference CLI has no
+    # flag for it, and the library and the Trainer read no environment variable for it -- only this entry point does
+    if os.environ.get("PD_BF16") == "1":
+        opts.bf16 = True
     if int(os.environ.get("WORLD_SIZE", 1)) > 1 and not torch.distributed.is_initialized():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
         torch.distributed.init_process_group("nccl")      # "nccl" is RCCL on ROCm

@@ -67,6 +67,30 @@ def _normals_decoder_variant(opt):
     return bool(getattr(opt, "normals_decoder", False)) or os.environ.get("PD_NORMALS_DECODER") == "1"
 
 
+def _bf16_variant(opt):
+    """Opt-in bf16 training mode: every convolution the single-bf16 kernels take rounds its operands once to bf16 and forms each
+    product with one bf16 MFMA (fp32 storage, epilogue, gradients and Adam: ops.CONV_BF16); with the attention variant the
+    attention block runs on the bf16 kernels as well.  Not a reference CLI flag: selected on the options object only
+    (``opt.bf16 = True``; the shell entry point manydepth/train.py maps PD_BF16=1 onto it)."""
+    return bool(getattr(opt, "bf16", False))
+
+
+class _Bf16Step:
+    """The flag words of this Trainer's training forward passes in bf16 mode, restored on exit: the precision is recorded by
+    every autograd node when its forward runs, so the backward (and a captured replay) follows it without a global switch."""
+
+    def __enter__(self):
+        self.attn = PF.USE_BF16_ATTENTION
+        self.flags = ops.conv_flags(conv=ops._with_bf16(ops.CONV_FLAGS, True), wgrad=ops._with_bf16(ops.WGRAD_FLAGS, True))
+        self.flags.__enter__()
+        PF.USE_BF16_ATTENTION = True
+        return self
+
+    def __exit__(self, *exc):
+        PF.USE_BF16_ATTENTION = self.attn
+        return self.flags.__exit__(*exc)
+
+
 class Trainer:
     def __init__(self, options):
         self.opt = options
@@ -189,6 +213,7 @@ class Trainer:
         # independent encoders on separate HIP streams (PD_ENCODER_STREAMS=0: everything on the current stream)
         self.encoder_streams = os.environ.get("PD_ENCODER_STREAMS", "1") != "0" and self.device.type == "cuda"
         self.step_graph = os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False))
+        self.bf16 = _bf16_variant(self.opt)        # training steps only: evaluation and the folded inference path stay fp32
         self._graphed = None
         self._enc_streams = []
         self.loss_cfg = PF.LossCfg(self.opt.scales, self.opt.min_depth, self.opt.max_depth, self.opt.normals_loss_weight,
@@ -346,7 +371,10 @@ class Trainer:
     def process_batch(self, inputs, is_train=False):
         for key, ipt in inputs.items():
             inputs[key] = ipt.to(self.device, non_blocking=True)
-        if self.train_teacher_and_pose:
+        if self.train_teacher_and_pose and is_train and self.bf16:
+            with _Bf16Step():
+                mono_outputs = self._forward_models(inputs)
+        elif self.train_teacher_and_pose:
             mono_outputs = self._forward_models(inputs)
         else:
             with torch.no_grad():

@@ -336,6 +336,7 @@ class ConvBNChainFn(torch.autograd.Function):
         s2d = (USE_S2D_STEMS and weight.shape[2] == 7 and weight.shape[3] == 7 and cfg.stride == 2 and cfg.pad == 3
                and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)
         ctx.s2d = s2d
+        ctx.conv_bf16 = ops.conv_bf16_mode()      # precision of this convolution, fixed here for its backward (ops.CONV_BF16)
         alg_k = None
         if s2d:
             alg_k = 49 * x.shape[1]                               # FLOPs are counted for the 7x7 filter, not the padded 4x4x4C
@@ -436,17 +437,18 @@ class ConvBNChainFn(torch.autograd.Function):
         if dres is not None and cfg.skip_out is not None and dres.stride(1) == 1:
             cfg.skip_out.grad = dres      # summed into the data gradient of the block's first convolution instead
             dres = None
+        db16, wb16 = ctx.conv_bf16
         if weight.requires_grad:
             # the bias feeds a BatchNorm: its gradient is identically zero (mean subtraction)
             gw = grad_buf(weight)
             if ctx.s2d:
                 def _stem_wgrad():
-                    dw2 = ops.conv2d_wgrad(x, dz, (Co, x.shape[1], 4, 4), 1, 2, alg_k=49 * (x.shape[1] // 4))
+                    dw2 = ops.conv2d_wgrad(x, dz, (Co, x.shape[1], 4, 4), 1, 2, alg_k=49 * (x.shape[1] // 4), bf16=wb16)
                     ops.s2d_weight_grad(dw2, gw, accumulate=True)
                 _wgrad_async(x, dz, _stem_wgrad)
             else:
                 _wgrad_async(x, dz, lambda: ops.conv2d_wgrad(x, dz, weight.shape, cfg.stride, cfg.pad,
-                                                             affine=cfg.affine, dw=gw, accumulate=True))
+                                                             affine=cfg.affine, dw=gw, accumulate=True, bf16=wb16))
             if bias is not None and bias.requires_grad:
                 grad_buf(bias)
         dx = None
@@ -458,7 +460,7 @@ class ConvBNChainFn(torch.autograd.Function):
                 skip, cfg.skip_in.grad = cfg.skip_in.grad, None
                 if skip is not None and tuple(skip.shape) != tuple(x.shape):
                     raise RuntimeError("SkipGrad: the skip gradient does not have the block input's shape")
-            dx = ops.conv2d_dgrad(dz, weight, (x.shape[2], x.shape[3]), cfg.stride, cfg.pad, addend=skip)
+            dx = ops.conv2d_dgrad(dz, weight, (x.shape[2], x.shape[3]), cfg.stride, cfg.pad, addend=skip, bf16=db16)
         elif cfg.skip_in is not None and cfg.skip_in.grad is not None:
             raise RuntimeError("SkipGrad: a skip gradient was deposited but the block input needs no gradient")
         for p in (weight, bias, gamma, beta):
@@ -488,6 +490,7 @@ class ReflectConvActFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, act, act_mail=None, dx_mail=None):
         x = ops.as_nhwc(x)
         y = ops.conv2d_fwd(x, weight, bias, 1, 1, mode=ops.MODE_REFLECT, act=act)
+        ctx.conv_bf16 = ops.conv_bf16_mode()
         ctx.act = act
         ctx.mails = (act_mail, dx_mail)         # ActGrad of this node's output / of its input
         ctx.params = (weight, bias)
@@ -515,7 +518,7 @@ class ReflectConvActFn(torch.autograd.Function):
             db = grad_buf(bias) if bias is not None and bias.requires_grad else None
             gw = grad_buf(weight)
             _wgrad_async(x, dz, lambda: ops.conv2d_wgrad(x, dz, weight.shape, 1, 1, mode=ops.MODE_REFLECT, dw=gw,
-                                                         dbias=db, accumulate=True))
+                                                         dbias=db, accumulate=True, bf16=ctx.conv_bf16[1]))
         dx = None
         if ctx.needs_input_grad[0]:
             Ci = x.shape[1]
@@ -524,13 +527,13 @@ class ReflectConvActFn(torch.autograd.Function):
                 #  whose every target pixel re-streams its slice of a multi-megabyte filter)
                 # the interior of the padded-grid gradient IS the zero-padding (pad 1) data gradient: it goes straight
                 # into dx; the four folded border strips are added by a kernel that touches 2(H+W) pixels per image
-                dx = ops.conv2d_dgrad(dz, weight, (H, W), 1, 1)
+                dx = ops.conv2d_dgrad(dz, weight, (H, W), 1, 1, bf16=ctx.conv_bf16[0])
                 dzv, ld_dz = nhwc_view(dz)
                 check(lib.pd_reflect_dgrad_border(ptr(dzv), ld_dz, ptr(ops.weight_cl(weight)), ptr(dx), N, H, W, Co, Ci,
                                                   stream_ptr()), "pd_reflect_dgrad_border")
             else:
                 # gradient on the reflection-padded grid (a zero-pad transposed conv), then fold the border
-                dxp = ops.conv2d_dgrad(dz, weight, (H + 2, W + 2), 1, 0)
+                dxp = ops.conv2d_dgrad(dz, weight, (H + 2, W + 2), 1, 0, bf16=ctx.conv_bf16[0])
                 dx = ops.empty_nhwc(N, Ci, H, W, dy.device)
                 check(lib.pd_reflect_fold(ptr(dxp), ptr(dx), N, H, W, Ci, stream_ptr()), "pd_reflect_fold")
             if dx_mail is not None and not dx_mail.closed:
@@ -643,6 +646,7 @@ class PaddedConvFn(torch.autograd.Function):
         x = ops.as_nhwc(x)
         mode = ops.MODE_REFLECT if reflect else ops.MODE_ZERO
         y = ops.conv2d_fwd(x, weight, bias, 1, pad, mode=mode, act=act)
+        ctx.conv_bf16 = ops.conv_bf16_mode()
         ctx.geom = (pad, mode, act)
         ctx.params = (weight, bias)
         ctx.save_for_backward(x, y if act != ops.ACT_NONE else None)
@@ -663,13 +667,14 @@ class PaddedConvFn(torch.autograd.Function):
         if weight.requires_grad:
             db = grad_buf(bias) if bias is not None and bias.requires_grad else None
             gw = grad_buf(weight)
-            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, 1, pad, mode=mode, dw=gw, dbias=db, accumulate=True))
+            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, 1, pad, mode=mode, dw=gw, dbias=db, accumulate=True,
+                                                         bf16=ctx.conv_bf16[1]))
         dx = None
         if ctx.needs_input_grad[0]:
             if mode == ops.MODE_ZERO:
-                dx = ops.conv2d_dgrad(dy, weight, (H, W), 1, pad)
+                dx = ops.conv2d_dgrad(dy, weight, (H, W), 1, pad, bf16=ctx.conv_bf16[0])
             else:
-                dxp = ops.conv2d_dgrad(dy, weight, (H + 2 * pad, W + 2 * pad), 1, 0)
+                dxp = ops.conv2d_dgrad(dy, weight, (H + 2 * pad, W + 2 * pad), 1, 0, bf16=ctx.conv_bf16[0])
                 dx = ops.empty_nhwc(N, Ci, H, W, dy.device)
                 check(lib.pd_reflect_fold_pad(ptr(dxp), ptr(dx), N, H, W, Ci, pad, stream_ptr()), "pd_reflect_fold_pad")
         for p in (weight, bias):
@@ -781,6 +786,7 @@ class ConvBiasFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, stride, pad):
         x = ops.as_nhwc(x)
         y = ops.conv2d_fwd(x, weight, bias, stride, pad)
+        ctx.conv_bf16 = ops.conv_bf16_mode()
         ctx.geom = (stride, pad)
         ctx.params = (weight, bias)
         ctx.save_for_backward(x)
@@ -795,8 +801,10 @@ class ConvBiasFn(torch.autograd.Function):
         if weight.requires_grad:
             db = grad_buf(bias) if bias is not None and bias.requires_grad else None
             gw = grad_buf(weight)
-            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, stride, pad, dw=gw, dbias=db, accumulate=True))
-        dx = ops.conv2d_dgrad(dy, weight, (x.shape[2], x.shape[3]), stride, pad) if ctx.needs_input_grad[0] else None
+            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, stride, pad, dw=gw, dbias=db, accumulate=True,
+                                                         bf16=ctx.conv_bf16[1]))
+        dx = (ops.conv2d_dgrad(dy, weight, (x.shape[2], x.shape[3]), stride, pad, bf16=ctx.conv_bf16[0])
+              if ctx.needs_input_grad[0] else None)
         for p in (weight, bias):
             if p is not None:
                 _ready(p)
@@ -1166,6 +1174,7 @@ class ConvBiasActFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, stride, pad, act):
         x = ops.as_nhwc(x)
         y = ops.conv2d_fwd(x, weight, bias, stride, pad, act=act)
+        ctx.conv_bf16 = ops.conv_bf16_mode()
         ctx.geom = (stride, pad, act)
         ctx.params = (weight, bias)
         ctx.save_for_backward(x, y if act != ops.ACT_NONE else None)
@@ -1184,8 +1193,10 @@ class ConvBiasActFn(torch.autograd.Function):
         if weight.requires_grad:
             db = grad_buf(bias) if bias is not None and bias.requires_grad else None
             gw = grad_buf(weight)
-            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, stride, pad, dw=gw, dbias=db, accumulate=True))
-        dx = ops.conv2d_dgrad(dy, weight, (x.shape[2], x.shape[3]), stride, pad) if ctx.needs_input_grad[0] else None
+            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, stride, pad, dw=gw, dbias=db, accumulate=True,
+                                                         bf16=ctx.conv_bf16[1]))
+        dx = (ops.conv2d_dgrad(dy, weight, (x.shape[2], x.shape[3]), stride, pad, bf16=ctx.conv_bf16[0])
+              if ctx.needs_input_grad[0] else None)
         for p in (weight, bias):
             if p is not None:
                 _ready(p)

@@ -23,6 +23,11 @@ PROFILE = None      # bench.py sets this to a list: (kernel label, algorithmic f
 # Tests and bench.py switch families in-process by assigning CONV_FLAGS / WGRAD_FLAGS (or `with conv_flags(...)`).
 CONV_AUTO, CONV_FP32_MFMA, CONV_BF16X3, CONV_WGRAD_SPLIT_IN_REGS, CONV_GENERAL_KERNELS, CONV_X3_IM2COL = 0, 1, 2, 4, 8, 16
 CONV_WGRAD_ROW_WORKGROUPS = 32        # one filter row per workgroup also where the rolling-row weight-gradient kernel fits (A/B, tests)
+# Opt-in bf16 training mode (PD_CONV_BF16): operands rounded once to bf16, one bf16 MFMA per product, fp32 storage and epilogue,
+# on the layers the single-bf16 kernels take (pd_conv2d_uses_bf16 / pd_conv2d_wgrad_uses_bf16); no environment variable selects
+# it -- `with conv_flags(conv=CONV_BF16, wgrad=CONV_BF16)` or a Trainer with opt.bf16 = True.  The autograd functions fix it
+# when their forward runs (functional.py: ctx.conv_bf16) and hand it to their backward's launches.
+CONV_BF16 = 128
 CONV_FLAGS = (CONV_FP32_MFMA if os.environ.get("PD_CONV_X3", "1") == "0" else       # pd_conv2d, _add, _rect
               CONV_X3_IM2COL if os.environ.get("PD_CONV_HALO", "1") == "0" else CONV_AUTO)   # PD_CONV_HALO=0: the per-tap gather kernel everywhere
 WGRAD_FLAGS = (CONV_FP32_MFMA if os.environ.get("PD_WGRAD_X3C", "1") == "0" else     # pd_conv2d_wgrad
@@ -51,6 +56,22 @@ class conv_flags:
         return False
 
 
+def conv_bf16_mode():
+    """(forward / data gradient, weight gradient) bf16 bits of the flag words as they stand: what a convolution's forward records
+    for its backward."""
+    return (bool(CONV_FLAGS & CONV_BF16), bool(WGRAD_FLAGS & CONV_BF16))
+
+
+def _with_bf16(word, bf16):
+    """`word` with its PD_CONV_BF16 bit set to `bf16` (None: the word as it stands).  A word that asks for another arithmetic
+    (fp32 MFMA, forced bf16 split) keeps it: the bit would make the word invalid."""
+    if bf16 is None:
+        return word
+    if bf16 and not (word & (CONV_FP32_MFMA | CONV_BF16X3)):
+        return word | CONV_BF16
+    return word & ~CONV_BF16
+
+
 def _profiled(label, flops, fn, shape=None):
     if PROFILE is None:
         return fn()
@@ -62,16 +83,21 @@ def _profiled(label, flops, fn, shape=None):
     return r
 
 
-def _igemm_label(M, Co, vec, kind, C=0, KH=1, KW=1, stride=1, pad=0, mode=0, act=ACT_NONE, out_scale=False, out_hw=(0, 0)):
+def _igemm_label(M, Co, vec, kind, C=0, KH=1, KW=1, stride=1, pad=0, mode=0, act=ACT_NONE, out_scale=False, out_hw=(0, 0),
+                 flags=None):
     """Profiler label = the kernel family pd_conv2d launches for this call (same rule as launch_conv in conv.hip)."""
-    rb = lib.pd_conv2d_uses_x3(M, Co, C, KH, KW, stride, pad, mode, act, int(out_scale), out_hw[0], out_hw[1], CONV_FLAGS) if vec else 0
+    flags = CONV_FLAGS if flags is None else flags
+    if vec and lib.pd_conv2d_uses_bf16(M, Co, C, KH, KW, stride, pad, mode, act, int(out_scale), out_hw[0], out_hw[1], flags):
+        return "conv_halo_bf16_kernel<8x32,64>"
+    flags &= ~CONV_BF16
+    rb = lib.pd_conv2d_uses_x3(M, Co, C, KH, KW, stride, pad, mode, act, int(out_scale), out_hw[0], out_hw[1], flags) if vec else 0
     if rb == 3:
         return "conv_halo_x3_kernel<8x32,64>"
     if rb:
         return f"conv_igemm_x3_kernel<{128 * rb},64>"
     bm = lib.pd_conv2d_tile_m(M, Co)
     bn = 64 if Co > 32 else (32 if Co > 16 else 16)
-    uni = (vec and not (CONV_FLAGS & CONV_GENERAL_KERNELS) and bn >= 32 and C % 32 == 0 and C > 0 and KH * KW <= 31 and pad < KH and pad < KW and
+    uni = (vec and not (flags & CONV_GENERAL_KERNELS) and bn >= 32 and C % 32 == 0 and C > 0 and KH * KW <= 31 and pad < KH and pad < KW and
            (mode in (MODE_ZERO, MODE_REFLECT) or (mode == MODE_TRANSPOSED and stride == 1)))
     if uni:
         return f"conv_igemm_uni_kernel<{bm},{bn}>"
@@ -184,12 +210,14 @@ def weight_transposed(w):
     return wt
 
 
-def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None):
+def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None, bf16=None):
     """dX of a zero-padded convolution: transposed convolution of dy (NHWC) with w.
 
     addend: optional tensor of dX's shape (channel stride 1) that is added in the kernel's epilogue -- the gradient of a
-    residual block's skip connection, which autograd would otherwise add in a separate pass."""
+    residual block's skip connection, which autograd would otherwise add in a separate pass.
+    bf16: the PD_CONV_BF16 bit of the forward this differentiates (None: CONV_FLAGS as it stands)."""
     _require_cuda(dy, w)
+    flags = _with_bf16(CONV_FLAGS, bf16)
     dy = as_nhwc(dy)
     N, Co, Hy, Wy = dy.shape
     _, Ci, KH, KW = w.shape
@@ -198,7 +226,7 @@ def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None):
         wt = weight_transposed(w)
     dx = empty_nhwc(N, Ci, H, W, dy.device)
     sN, sC, sH, sW = dy.stride()
-    if (USE_S2_PHASES and not (CONV_FLAGS & CONV_GENERAL_KERNELS) and addend is None and stride == 2 and KH == 3 and KW == 3 and pad == 1 and H == 2 * Hy and W == 2 * Wy
+    if (USE_S2_PHASES and not (flags & CONV_GENERAL_KERNELS) and addend is None and stride == 2 and KH == 3 and KW == 3 and pad == 1 and H == 2 * Hy and W == 2 * Wy
             and Co % 32 == 0 and Ci % 4 == 0 and Ci > 16 and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0):
         # stride-2 data gradient by output parity: four stride-1 2x2 sub-filter launches + one interleave
         def _phases():
@@ -208,7 +236,7 @@ def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None):
             for c, off in enumerate((0, 1, 3, 5)):
                 ph, pw = c >> 1, c & 1
                 check(lib.pd_conv2d_rect(ptr(dy), wsub.data_ptr() + 4 * off * Ci * Co, ptr(sub[c]), N, Hy, Wy, Co, sN, sH, sW,
-                                         sC, Hy, Wy, Ci, 1 + ph, 1 + pw, ph, pw, MODE_TRANSPOSED, Ci, CONV_FLAGS, stream_ptr()),
+                                         sC, Hy, Wy, Ci, 1 + ph, 1 + pw, ph, pw, MODE_TRANSPOSED, Ci, flags, stream_ptr()),
                       "pd_conv2d_rect(dgrad s2 phase)")
             check(lib.pd_interleave4(ptr(sub), ptr(dx), N, Hy, Wy, Ci, stream_ptr()), "pd_interleave4")
         _profiled("conv_dgrad_s2_phases", 2.0 * N * Hy * Wy * Co * Ci * KH * KW, _phases,
@@ -227,18 +255,18 @@ def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None):
         assert addend.shape == dx.shape and addend.stride(1) == 1 and addend.is_cuda
         ld_add = addend.stride(3)
         assert addend.stride(2) == W * ld_add and addend.stride(0) == H * W * ld_add
-        _profiled(_igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W)),
+        _profiled(_igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W), flags=flags),
                   2.0 * N * Hy * Wy * Co * Ci * KH * KW,
                   lambda: check(lib.pd_conv2d_add(ptr(dy), ptr(wt), ptr(addend), ld_add, ptr(dx), N, Hy, Wy, Co, sN, sH, sW,
-                                                  sC, H, W, Ci, KH, KW, stride, pad, MODE_TRANSPOSED, Ci, CONV_FLAGS, stream_ptr()),
+                                                  sC, H, W, Ci, KH, KW, stride, pad, MODE_TRANSPOSED, Ci, flags, stream_ptr()),
                                 "pd_conv2d_add(dgrad)"),
                   shape=("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED))
         return dx
     # algorithmic flops of the data gradient = those of the forward conv it differentiates
-    _profiled(_igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W)), 2.0 * N * Hy * Wy * Co * Ci * KH * KW,
+    _profiled(_igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W), flags=flags), 2.0 * N * Hy * Wy * Co * Ci * KH * KW,
               lambda: check(lib.pd_conv2d(ptr(dy), ptr(wt), None, None, ptr(dx), None, N, Hy, Wy, Co, sN, sH, sW, sC,
                                           H, W, Ci, KH, KW, stride, pad, MODE_TRANSPOSED, ACT_NONE, 0, 0.0, 1.0, Ci,
-                                          CONV_FLAGS, stream_ptr()), "pd_conv2d(dgrad)"),
+                                          flags, stream_ptr()), "pd_conv2d(dgrad)"),
               shape=("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED))
     return dx
 
@@ -258,9 +286,11 @@ def _workspace(nbytes, device):
 
 
 def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, mode=MODE_ZERO, affine=None, dw=None, dbias=None,
-                 want_bias=False, accumulate=False, alg_k=None):
-    """dW (channels_last [Co,Ci,kh,kw]) and optionally dbias of conv(x, w) given dy (NHWC)."""
+                 want_bias=False, accumulate=False, alg_k=None, bf16=None):
+    """dW (channels_last [Co,Ci,kh,kw]) and optionally dbias of conv(x, w) given dy (NHWC).
+    bf16: the PD_CONV_BF16 bit of the forward this differentiates (None: WGRAD_FLAGS as it stands)."""
     _require_cuda(x, dy)
+    flags = _with_bf16(WGRAD_FLAGS, bf16)
     dy = as_nhwc(dy)
     N, C, H, W = x.shape
     Co, Ci, KH, KW = w_shape
@@ -284,18 +314,22 @@ def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, mode=MODE_ZERO, affine=None, d
                                 "pd_conv16_wgrad"),
                   shape=("wgrad", N, C, H, W, Co, KH, stride, mode))
         return (dw, dbias) if (want_bias or dbias is not None) else dw
-    nbytes = lib.pd_conv2d_wgrad_workspace(M, Co, K, WGRAD_FLAGS)
+    nbytes = lib.pd_conv2d_wgrad_workspace(M, Co, K, flags)
     ws = _workspace(nbytes, x.device)
     sub, div = (affine if affine is not None else (0.0, 1.0))
     sN, sC, sH, sW = x.stride()
-    x3c = (lib.pd_conv2d_wgrad_uses_x3(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, WGRAD_FLAGS)
-           if (affine is None and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0 and dy.stride(3) % 4 == 0) else 0)
-    _profiled("conv_wgrad_roll_x3_kernel" if x3c == 3 else "conv_wgrad_halo_x3_kernel" if x3c == 2 else "conv_wgrad_x3c_kernel" if x3c else "conv_wgrad_kernel",
+    fits = affine is None and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0 and dy.stride(3) % 4 == 0
+    x3c = lib.pd_conv2d_wgrad_uses_x3(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags & ~CONV_BF16) if fits else 0
+    one = lib.pd_conv2d_wgrad_uses_bf16(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags) if fits else 0
+    label = ("conv_wgrad_roll_bf16_kernel" if one == 3 else "conv_wgrad_halo_bf16_kernel" if one == 2 else
+             "conv_wgrad_roll_x3_kernel" if x3c == 3 else "conv_wgrad_halo_x3_kernel" if x3c == 2 else "conv_wgrad_x3c_kernel" if x3c else
+             "conv_wgrad_kernel")
+    _profiled(label,
               2.0 * M * Co * (alg_k if alg_k is not None else K),
               lambda: check(lib.pd_conv2d_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), N, H, W, C,
                                                 sN, sH, sW, sC, Ho, Wo, Co, KH, KW, stride, pad, mode,
                                                 int(affine is not None), sub, div, dy.stride(3), int(accumulate),
-                                                WGRAD_FLAGS, stream_ptr()), "pd_conv2d_wgrad"),
+                                                flags, stream_ptr()), "pd_conv2d_wgrad"),
               shape=("wgrad", N, C, H, W, Co, KH, stride, mode))
     return (dw, dbias) if (want_bias or dbias is not None) else dw
 

@@ -190,6 +190,62 @@ def test_shape_validation_of_the_fused_kernels_needs_no_gpu():
                        8, 0, None) == -22 and b"row stride" in L.pd_last_error()
 
 
+def test_shape_validation_of_the_glue_kernels_needs_no_gpu():
+    """The K3 refusals (csrc/elementwise.hip) that are decided before any launch return PD_EINVAL (-22) with their message,
+    and pd_chain_bwd_rows is the documented min(1024, ceil(quads / 256))."""
+    L = _lib.lib
+    p = ctypes.c_void_p(16)      # a non-null, 16-byte aligned dummy: never dereferenced on these paths
+    err = L.pd_last_error
+
+    def fwd(N, H, W, C, ld_res=None, ld_out=None, pool=0, drop_p=0.0):
+        return L.pd_chain_fwd(p, p, p, p, p, N, H, W, C, C if ld_res is None else ld_res, C if ld_out is None else ld_out, 1, pool,
+                              drop_p, 1, 2, None, 0, None)
+
+    def reduce_(N, H, W, C, ld_dy=None, pool=0, drop_p=0.0):
+        return L.pd_chain_bwd_reduce(p, C if ld_dy is None else ld_dy, p, p, C, p, p, p, p, p, N, H, W, C, 1, pool, drop_p, 1, 2, None,
+                                     0, None)
+
+    def apply_(N, H, W, C, ld_dy=None, pool=0, dres=None, relu_post=0):
+        return L.pd_chain_bwd_apply(p, C if ld_dy is None else ld_dy, p, p, C, p, p, p, p, p, p, dres, N, H, W, C, 1, pool, 0.0, 1, 2,
+                                    None, relu_post, None)
+
+    for f in (fwd, reduce_, apply_):
+        assert f(1, 4, 4, 12) == -22 and b"C/4 must divide 256" in err()           # a thread keeps its channel quad
+        assert f(1, 4, 4, 6) == -22 and b"multiple of 4" in err()
+        assert f(1, 1, 4, 8, pool=1) == -22 and b"pooling needs H,W >= 2" in err()
+        assert f(1, 4, 1, 8, pool=1) == -22 and b"pooling needs H,W >= 2" in err()
+        assert f(2, 32768, 32768, 4) == -22 and b"too large for 32-bit" in err()    # 2^31 quads
+        assert f(1, 46340, 46340, 4) == -22 and b"too large for 32-bit" in err()    # inside 2^31 but not below 2^31 - 2^22
+        assert f(0, 4, 4, 8) == 0                                                    # empty batch: nothing launched
+    assert fwd(1, 4, 4, 8, ld_out=4) == -22 and b"bad row stride" in err()
+    assert fwd(1, 4, 4, 8, ld_out=10) == -22 and b"bad row stride" in err()          # rows must stay 16-byte aligned
+    assert fwd(1, 4, 4, 8, ld_res=4) == -22 and b"bad row stride" in err()
+    assert reduce_(1, 4, 4, 8, ld_dy=4) == -22 and b"bad row stride" in err()
+    assert apply_(1, 4, 4, 8, ld_dy=4) == -22 and b"bad row stride" in err()
+    assert fwd(1, 4, 4, 8, drop_p=1.0) == -22 and b"dropout p must be in [0,1)" in err()
+    assert fwd(1, 4, 4, 8, drop_p=-0.1) == -22 and b"dropout p" in err()
+    assert apply_(1, 4, 4, 8, dres=p) == -22 and b"dres is only produced for post-add ReLU" in err()
+    assert L.pd_chain_fwd(p, p, None, None, p, 1, 4, 4, 8, 0, 8, 1, 0, 0.0, 1, 2, None, 0, None) == -22 and b"null tensor" in err()
+    assert L.pd_maxpool3s2_bwd_add(p, p, p, 4, p, 1, 4, 4, 8, None) == -22 and b"bad addend" in err()
+    assert L.pd_maxpool3s2_fwd(p, p, p, 1, 4, 4, 6, None) == -22 and b"pd_maxpool3s2_fwd" in err()
+    assert L.pd_upcat_fwd(p, None, 8, p, 1, 4, 4, 8, 8, None) == -22 and b"bad skip tensor" in err()
+    assert L.pd_upcat_fwd(p, p, 4, p, 1, 4, 4, 8, 8, None) == -22 and b"bad skip tensor" in err()
+    assert L.pd_up_bwd(p, 4, p, 1, 4, 4, 8, None) == -22 and b"pd_up_bwd" in err()                      # ld_d < Ca
+    assert L.pd_relu_add(p, p, p, 6, 1, None) == -22 and b"multiple of 4" in err()
+    assert L.pd_reflect_fold_pad(p, p, 1, 3, 5, 4, 3, None) == -22 and b"pad must be in [1, min(H, W))" in err()
+    assert L.pd_reflect_fold_pad(p, p, 1, 5, 3, 4, 3, None) == -22 and b"pad must be" in err()
+    assert L.pd_reflect_fold_pad(p, p, 1, 5, 5, 4, 0, None) == -22 and b"pad must be" in err()
+    assert L.pd_adam_step(p, p, p, p, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0, None, 1.0, 0, None) == -22 and b"pd_adam_step" in err()
+    assert L.pd_act_bwd(p, p, p, 8, 4, None) == -22 and b"pd_act_bwd" in err()
+    assert L.pd_bn_bwd_finalize(p, 4, 8, 16.0, p, 16, p, p, p, 0, None) == -22 and b"accumulator needs 2 C + 1" in err()
+    assert L.pd_bn_fwd_finalize(p, 4, 8, 16.0, p, p, p, p, 0.1, 1e-5, p, 16, p, p, p, p, 1, None) == -22 and b"accumulator" in err()
+    assert L.pd_bn_fwd_finalize(None, 0, 8, 1.0, p, p, None, None, 0.1, 1e-5, None, 0, p, p, None, None, 0, None) == -22 \
+        and b"eval needs running stats" in err()
+    for N, H, W, C in ((1, 1, 1, 4), (3, 2, 2, 4), (1, 5, 7, 16), (2, 6, 8, 64), (1, 4, 6, 1024), (1, 64, 80, 256), (2, 128, 160, 128),
+                       (16, 256, 320, 64)):
+        assert L.pd_chain_bwd_rows(N, H, W, C) == min(1024, -(-(N * H * W * (C // 4)) // 256))
+
+
 def test_which_shapes_take_the_bf16_split_kernels():
     """pd_conv2d_uses_x3 / pd_conv2d_wgrad_uses_x3 (host logic, no GPU): the routing rule the profiler labels, bench.py's
     roofline object and the production-size tests rely on.  Arguments: M, Cout, C, KH, KW, stride, pad, mode, act, scale."""

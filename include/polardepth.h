@@ -116,6 +116,34 @@ int pd_polar_calc_normals(const void* phi, const void* theta, void* out, int B, 
 int pd_polar_theta(const void* rho, void* theta_d, void* theta_s1, void* theta_s2, void* bins,
                    const void* tables, size_t tables_bytes, long n, void* stream);
 
+/* General polarizer angles and 8-bit / 16-bit / fp32 intensities (polarisation/xolp.py:8-34 for any four angles).
+ *
+ * pd_polar_fit_matrix (host only, no GPU): coef_out = row-major 3x4 coefficients P = (A^T A)^-1 A^T of the least-squares
+ * fit I(theta) = x0 + x1 cos 2theta + x2 sin 2theta, A = [1, cos 2theta_j, sin 2theta_j] with |a| < 4 DBL_EPSILON snapped to 0
+ * and |p| < 1e-12 max|p| snapped to 0 (0/45/90/135 degrees give exactly .25 .25 .25 .25 / .5 0 -.5 0 / 0 .5 0 -.5).
+ * Non-finite angles and angle sets of rank < 3 (e.g. 0/90/180/270 degrees) return PD_EINVAL. */
+int pd_polar_fit_matrix(const double angles_rad[4], double coef_out[12]);
+
+#define PD_POLAR_U8 0
+#define PD_POLAR_U16 1
+#define PD_POLAR_F32 2
+/*
+ * pol        [B,4,H,W] device, element type `dtype` (PD_POLAR_U8 / _U16 / _F32), planes in the order of the angles
+ *            given to pd_polar_fit_matrix
+ * coef       HOST pointer to the 12 coefficients; read during the call and passed as kernel arguments (no allocation,
+ *            copy or synchronisation: the call can be captured into a graph)
+ * iun        [B,1,H,Wout] fp32 or NULL   (Imax + Imin) / 2
+ * xolp / xolp_std / normals / tables / Wout   as for pd_polar_fwd; tables may be NULL unless normals are requested
+ * Per pixel, in fp64 without contraction: x_k = ((P[k][0] I0 + P[k][1] I1) + P[k][2] I2) + P[k][3] I3,
+ * r = sqrt(x1^2 + x2^2), Imax = x0 + r, Imin = x0 - r, Iun = (Imax + Imin) / 2, rho = (Imax - Imin) / (Imax + Imin) with
+ * inf and NaN -> 0, phi = 0.5 atan2(x2, x1); each rounded once to fp32.  xolp_std and the normals derive from the fp32
+ * rho, phi exactly as pd_polar_normals_from_xolp does.  flags: PD_POLAR_PRECISE_NORMALS only.  Shape, alignment and size
+ * rules of pd_polar_fwd.
+ */
+int pd_polar_general_fwd(const void* pol, int dtype, const double* coef, void* iun, void* xolp, void* xolp_std,
+                         void* normals, const void* tables, size_t tables_bytes,
+                         int B, int H, int W, int Wout, int flags, void* stream);
+
 /* ------------------------------------------------------------------------- K2
  * Implicit-GEMM convolution on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
  *

@@ -1076,3 +1076,272 @@ extern "C" int pd_polar_fwd(const void* pol, const void* mask, void* xolp, void*
     if (rc) return rc;
     return pd::check_launch("pd_polar_fwd");
 }
+
+// ------------------------------------------------------------------ general angles / 8-bit, 16-bit, fp32 intensities
+// polarisation/xolp.py:8-34 for ANY four polarizer angles and any real intensities: the least-squares fit
+// I(theta) = x0 + x1 cos 2theta + x2 sin 2theta is x = P I with the 3x4 matrix P = (A^T A)^-1 A^T, which depends on the
+// angles alone -- the host forms it once in fp64 (pd_polar_fit_matrix) and the kernel receives its 12 entries as
+// arguments.  Canonical arithmetic: fp64, left-to-right sums, IEEE sqrt and division, one rounding to fp32
+// per result.  Nothing here depends on the (I0-I90, I45-I135) look-up tables of polar_kernel; the theta tables, the
+// standardisation and the normals are the shared helpers above, called as normals_from_xolp_kernel calls them.
+extern "C" int pd_polar_fit_matrix(const double angles_rad[4], double coef_out[12]) {
+    PD_REQUIRE(angles_rad && coef_out, "pd_polar_fit_matrix: null pointer");
+    double A[4][3];
+    for (int j = 0; j < 4; ++j) {
+        PD_REQUIRE(std::isfinite(angles_rad[j]), "pd_polar_fit_matrix: angle %d is not finite", j);
+        A[j][0] = 1.0;
+        A[j][1] = cos(2.0 * angles_rad[j]);
+        A[j][2] = sin(2.0 * angles_rad[j]);
+        for (int k = 1; k < 3; ++k)
+            if (fabs(A[j][k]) < 4.0 * 2.220446049250313e-16) A[j][k] = 0.0;   // cos(pi/2) = 6e-17 is a zero
+    }
+    // normal equations, inverse by cofactors: exact for the standard set (A^T A = diag(4, 2, 2)); the condition number of
+    // A^T A is below 10 for every usable filter arrangement
+    double M[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            double s = 0.0;
+            for (int j = 0; j < 4; ++j) s += A[j][r] * A[j][c];
+            M[r][c] = s;
+        }
+    double C[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+            C[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1];      // cofactor (cyclic indices carry the sign)
+        }
+    const double det = M[0][0] * C[0][0] + M[0][1] * C[0][1] + M[0][2] * C[0][2];
+    // det / (product of the diagonal) = product of the squared sines between each column and the span of the others'
+    // predecessors (Hadamard): below 1e-12 the three columns are dependent to within 1e-6 -- rank < 3 for any measured data
+    const double diag = M[0][0] * M[1][1] * M[2][2];
+    PD_REQUIRE(diag > 0.0 && det > 1e-12 * diag,
+               "pd_polar_fit_matrix: the angles do not determine the fit (rank < 3, e.g. 0/90/180/270 degrees)");
+    double pmax = 0.0;
+    for (int k = 0; k < 3; ++k)
+        for (int j = 0; j < 4; ++j) {
+            // (A^T A)^-1 is symmetric: entry (k, c) = C[c][k] / det
+            const double p = ((C[0][k] * A[j][0] + C[1][k] * A[j][1]) + C[2][k] * A[j][2]) / det;
+            coef_out[4 * k + j] = p;
+            pmax = std::max(pmax, fabs(p));
+        }
+    for (int i = 0; i < 12; ++i)
+        if (fabs(coef_out[i]) < 1e-12 * pmax) coef_out[i] = 0.0;
+    return PD_OK;
+}
+
+namespace {
+
+struct GenCoef { double p[12]; };   // row-major 3x4, travels as a kernel argument
+
+// the four planes of one quad as loaded: 4 B (u8), 8 B (u16) or 16 B (f32) per plane
+template <typename T> struct GenRaw;
+template <> struct GenRaw<uint8_t> {
+    uint32_t w[4];
+    __device__ __forceinline__ void zero() { w[0] = w[1] = w[2] = w[3] = 0u; }
+    __device__ __forceinline__ void load(const uint8_t* p, int k) { w[k] = *reinterpret_cast<const uint32_t*>(p); }
+    __device__ __forceinline__ double get(int k, int j) const { return static_cast<double>(static_cast<float>((w[k] >> (8 * j)) & 0xffu)); }
+};
+template <> struct GenRaw<uint16_t> {
+    uint2 w[4];
+    __device__ __forceinline__ void zero() { for (int k = 0; k < 4; ++k) w[k] = make_uint2(0u, 0u); }
+    __device__ __forceinline__ void load(const uint16_t* p, int k) { w[k] = *reinterpret_cast<const uint2*>(p); }
+    __device__ __forceinline__ double get(int k, int j) const {
+        const uint32_t v = j < 2 ? w[k].x : w[k].y;
+        return static_cast<double>(static_cast<float>((v >> (16 * (j & 1))) & 0xffffu));
+    }
+};
+template <> struct GenRaw<float> {
+    float4 w[4];
+    __device__ __forceinline__ void zero() { for (int k = 0; k < 4; ++k) w[k] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    __device__ __forceinline__ void load(const float* p, int k) { w[k] = *reinterpret_cast<const float4*>(p); }
+    __device__ __forceinline__ double get(int k, int j) const {
+        return static_cast<double>(j == 0 ? w[k].x : j == 1 ? w[k].y : j == 2 ? w[k].z : w[k].w);
+    }
+};
+
+// One thread = one quad of 4 pixels; geometry and the walk over the output quads are polar_kernel's (PolarGeo, advance).
+// OUT_XOLP: hardware-scheduled, one quad per thread, no LDS.  OUT_FAST / OUT_PRECISE: persistent, one workgroup per CU,
+// the theta tables staged once into LDS; the next quad's planes are requested before the current quad is computed.
+template <typename T, int OUT, int NTH>
+__global__ __launch_bounds__(NTH) void polar_general_kernel(
+    const T* __restrict__ pol, float* __restrict__ iun, float* __restrict__ xolp, float* __restrict__ xolp_std,
+    float* __restrict__ normals, const char* __restrict__ blob, const PolarGeo g, const GenCoef cf) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool NORMALS = OUT != OUT_XOLP;
+    constexpr bool PRECISE = OUT == OUT_PRECISE;
+    const unsigned in_row = 4u * g.wq_in, out_row = 4u * g.wq_out;
+    auto load_quad = [&](const QuadPos& p) -> GenRaw<T> {
+        GenRaw<T> r;
+        r.zero();
+        if (p.b < g.B && p.cq < g.wq_in) {
+            const unsigned p4 = static_cast<unsigned>(p.b) * 4u * g.P + p.row * in_row + 4u * p.cq;   // in elements
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r.load(pol + (p4 + static_cast<unsigned>(k) * g.P), k);
+        }
+        return r;
+    };
+    QuadPos q;
+    {
+        const unsigned q0 = blockIdx.x * static_cast<unsigned>(NTH) + threadIdx.x;
+        q.row = q0 / static_cast<unsigned>(g.wq_out);
+        q.cq = static_cast<int>(q0 - q.row * static_cast<unsigned>(g.wq_out));
+        q.b = static_cast<int>(q.row / static_cast<unsigned>(g.Hrows));
+        q.row -= static_cast<unsigned>(q.b) * static_cast<unsigned>(g.Hrows);
+    }
+    GenRaw<T> rc = load_quad(q);
+    Tabs tabs;
+    if (NORMALS) stage_tables<PRECISE>(blob, smem, NTH, tabs);
+
+    while (q.b < g.B) {
+        const unsigned po = q.row * out_row + 4u * q.cq;     // first output pixel of the quad inside its plane
+        const unsigned b = static_cast<unsigned>(q.b);
+        const bool pad = q.cq >= g.wq_in;                    // padding columns of a pitched output
+        QuadPos qn = q;
+        advance(qn, g);
+        const GenRaw<T> rn = load_quad(qn);
+        __builtin_amdgcn_sched_barrier(0);
+
+        float o_iun[4], o_rho[4], o_phi[4], o_n[9][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            __builtin_amdgcn_sched_barrier(0);               // one pixel's fp64 chain at a time: register pressure
+            const double i0 = rc.get(0, j), i1 = rc.get(1, j), i2 = rc.get(2, j), i3 = rc.get(3, j);
+            const double x0 = ((cf.p[0] * i0 + cf.p[1] * i1) + cf.p[2] * i2) + cf.p[3] * i3;
+            const double x1 = ((cf.p[4] * i0 + cf.p[5] * i1) + cf.p[6] * i2) + cf.p[7] * i3;
+            const double x2 = ((cf.p[8] * i0 + cf.p[9] * i1) + cf.p[10] * i2) + cf.p[11] * i3;
+            const double r = sqrt(x1 * x1 + x2 * x2);        // xolp.py:22-29 literally
+            const double imax = x0 + r;
+            const double imin = x0 - r;
+            const double sum = imax + imin;
+            double rho = (imax - imin) / sum;
+            if (isinf(rho) || isnan(rho)) rho = 0.0;         // rho[rho == inf] = 0; nan_to_num
+            o_iun[j] = static_cast<float>(sum / 2.0);
+            o_rho[j] = static_cast<float>(rho);
+            o_phi[j] = static_cast<float>(0.5 * atan2(x2, x1));
+            if (NORMALS) {
+                float v[9]; int bi[3];
+                float sp = 0.f, cp = 1.f;
+                if (!PRECISE) sincos_f32(o_phi[j], sp, cp);  // torch.cos/sin on the fp32 AoLP
+                normals9<PRECISE, true>(o_rho[j], o_phi[j], cp, sp, tabs, v, bi);
+#pragma unroll
+                for (int c = 0; c < 9; ++c) o_n[c][j] = pad ? 0.f : v[c];
+            }
+        }
+        if (iun) {
+            float* o = iun + (b * g.Pout + po);
+            store4<true>(o, o_iun[0], o_iun[1], o_iun[2], o_iun[3]);
+        }
+        if (xolp) {
+            float* o = xolp + (b * 2u * g.Pout + po);
+            store4<true>(o, o_rho[0], o_rho[1], o_rho[2], o_rho[3]);
+            store4<true>(o + g.Pout, o_phi[0], o_phi[1], o_phi[2], o_phi[3]);
+        }
+        if (xolp_std) {
+            float* o = xolp_std + (b * 2u * g.Pout + po);
+            float sr[4], sf[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sr[j] = pad ? 0.f : standardise(o_rho[j]); sf[j] = pad ? 0.f : standardise(o_phi[j]); }
+            store4<true>(o, sr[0], sr[1], sr[2], sr[3]);
+            store4<true>(o + g.Pout, sf[0], sf[1], sf[2], sf[3]);
+        }
+        if (NORMALS && normals) {
+            float* o = normals + (b * 9u * g.Pout + po);
+#pragma unroll
+            for (unsigned c = 0; c < 9; ++c) store4<true>(o + c * g.Pout, o_n[c][0], o_n[c][1], o_n[c][2], o_n[c][3]);
+        }
+        q = qn;
+        rc = rn;
+    }
+}
+
+// workgroup sizes: XOLP only 256 (hardware-scheduled); with normals one persistent workgroup per CU, 1024 threads on the
+// fp32 theta path (4 waves per SIMD, 128 VGPRs each: the fp64 chain of one pixel fits) and kThreadsP on the fp64 one
+constexpr int kThreadsG = 256;
+
+template <typename T>
+int general_launch(const void* pol, const GenCoef& cf, void* iun, void* xolp, void* xolp_std, void* normals,
+                   const void* tables, size_t lds, int B, int H, int W, int Wout, bool precise, hipStream_t st) {
+    const long P = (long)H * W, Pout = (long)H * Wout;
+    const bool pitched = Wout != W;
+    const bool need_normals = normals != nullptr;
+    const int nth = need_normals ? (precise ? kThreadsP : fast_threads()) : kThreadsG;
+    const long max_b = (1L << 30) / (9 * Pout);
+    int rc = PD_OK;
+    for (long b0 = 0; b0 < B && rc == PD_OK; b0 += max_b) {
+        const int nb = (int)std::min<long>(max_b, B - b0);
+        PolarGeo g;
+        g.B = nb; g.Hrows = pitched ? H : 1;
+        g.wq_in = pitched ? W / 4 : (int)(P / 4); g.wq_out = pitched ? Wout / 4 : (int)(P / 4);
+        g.P = (unsigned)P; g.Pout = (unsigned)Pout; g.flags = 0;
+#ifdef PD_POLAR_TRACE
+        g.trace = nullptr;
+#endif
+        const long total = (long)nb * (Pout / 4);
+        long blocks = (total + nth - 1) / nth;
+        if (need_normals && blocks > 256) blocks = 256;
+        const long step = blocks * nth;
+        g.drow = (int)(step / g.wq_out); g.dcq = (int)(step % g.wq_out);
+        const T* pol_b = static_cast<const T*>(pol) + b0 * 4 * P;
+        float* iun_b = iun ? static_cast<float*>(iun) + b0 * Pout : nullptr;
+        float* xolp_b = xolp ? static_cast<float*>(xolp) + b0 * 2 * Pout : nullptr;
+        float* std_b = xolp_std ? static_cast<float*>(xolp_std) + b0 * 2 * Pout : nullptr;
+        float* nrm_b = normals ? static_cast<float*>(normals) + b0 * 9 * Pout : nullptr;
+        auto go = [&](auto kern) -> int {
+            int r = set_lds_limit(kern, lds);
+            if (r) return r;
+            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(nth), lds, st, pol_b, iun_b, xolp_b, std_b, nrm_b,
+                               static_cast<const char*>(tables), g, cf);
+            return PD_OK;
+        };
+        if (!need_normals) rc = go(polar_general_kernel<T, OUT_XOLP, kThreadsG>);
+        else if (precise) rc = go(polar_general_kernel<T, OUT_PRECISE, kThreadsP>);
+        else rc = go(polar_general_kernel<T, OUT_FAST, 1024>);
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int pd_polar_general_fwd(const void* pol, int dtype, const double* coef, void* iun, void* xolp, void* xolp_std,
+                                    void* normals, const void* tables, size_t tables_bytes,
+                                    int B, int H, int W, int Wout, int flags, void* stream) {
+    PD_REQUIRE(B >= 0 && H > 0 && W > 0, "pd_polar_general_fwd: bad shape B=%d H=%d W=%d", B, H, W);
+    if (B == 0) return PD_OK;  // empty batch: nothing to do (pointers may be null)
+    PD_REQUIRE(dtype == PD_POLAR_U8 || dtype == PD_POLAR_U16 || dtype == PD_POLAR_F32,
+               "pd_polar_general_fwd: unknown dtype %d", dtype);
+    PD_REQUIRE((flags & ~PD_POLAR_PRECISE_NORMALS) == 0,
+               "pd_polar_general_fwd: flags 0x%x not supported (PD_POLAR_PRECISE_NORMALS only)", flags);
+    PD_REQUIRE(pol && coef, "pd_polar_general_fwd: pol and coef must not be null");
+    PD_REQUIRE(iun || xolp || xolp_std || normals, "pd_polar_general_fwd: no output requested");
+    PD_REQUIRE(!normals || tables, "pd_polar_general_fwd: normals need the tables blob");
+    const long P = (long)H * W;
+    if (Wout <= 0) Wout = W;
+    PD_REQUIRE(Wout >= W, "pd_polar_general_fwd: output pitch %d < W %d", Wout, W);
+    PD_REQUIRE(Wout == W ? P % 4 == 0 : (W % 4 == 0 && Wout % 4 == 0),
+               "pd_polar_general_fwd: H*W (or W and the output pitch, when they differ) must be multiples of 4");
+    PD_REQUIRE(pd::aligned16(pol) && pd::aligned16(iun) && pd::aligned16(xolp) && pd::aligned16(xolp_std) &&
+                   pd::aligned16(normals) && pd::aligned16(tables),
+               "pd_polar_general_fwd: pointers must be 16-byte aligned");
+    const bool precise = (flags & PD_POLAR_PRECISE_NORMALS) != 0;
+    size_t lds = 0;
+    if (normals) {
+        const int nk = nk_from_blob_bytes(tables_bytes);
+        PD_REQUIRE(nk > 0, "pd_polar_general_fwd: tables blob too small or of an unexpected size");
+        lds = img_bytes_for(nk, precise);
+    }
+    // 32-bit addressing inside the kernel: at most 2^30 elements per output tensor
+    const long Pout = (long)H * Wout;
+    PD_REQUIRE(9 * Pout < (1L << 30), "pd_polar_general_fwd: image too large (%ld output pixels)", Pout);
+    GenCoef cf;
+    for (int i = 0; i < 12; ++i) {
+        cf.p[i] = coef[i];
+        PD_REQUIRE(std::isfinite(cf.p[i]), "pd_polar_general_fwd: coefficient %d is not finite", i);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    if (dtype == PD_POLAR_U8) rc = general_launch<uint8_t>(pol, cf, iun, xolp, xolp_std, normals, tables, lds, B, H, W, Wout, precise, st);
+    else if (dtype == PD_POLAR_U16) rc = general_launch<uint16_t>(pol, cf, iun, xolp, xolp_std, normals, tables, lds, B, H, W, Wout, precise, st);
+    else rc = general_launch<float>(pol, cf, iun, xolp, xolp_std, normals, tables, lds, B, H, W, Wout, precise, st);
+    if (rc) return rc;
+    return pd::check_launch("pd_polar_general_fwd");
+}

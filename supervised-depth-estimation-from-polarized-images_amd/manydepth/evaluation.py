@@ -18,10 +18,12 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
 
 class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
-                 augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None):
+                 augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
-        must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path)."""
+        must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
+        calibrated polarizer angles in degrees, in the order of the planes of ("pol", 0, 0) (or $PD_POL_ANGLES="a,b,c,d",
+        read here once); None = the nominal 0/45/90/135 set.  ("pol", 0, 0) may be uint8, uint16 or float32."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -32,6 +34,7 @@ class Evaluation:
         self.min_depth, self.max_depth, self.scales = 0.1, 2.0, [0, 1, 2, 3]
         self.augment_xolp, self.augment_normals = augment_xolp, augment_normals
         self.load_weights_folder = load_weights_folder
+        self.pol_angles = pdpolar.angles_from_degrees(pol_angles if pol_angles is not None else os.environ.get("PD_POL_ANGLES"))
         self.device = torch.device("cuda")
         self.models = {"rgb_encoder": networks.ShallowResnetEncoder(18, False)}
         if augment_normals:
@@ -70,7 +73,8 @@ class Evaluation:
     def predict(self, inputs):
         normals = None
         if ("pol", 0, 0) in inputs:
-            out = pdpolar.polar_forward(inputs[("pol", 0, 0)], want=("xolp", "normals") if self.augment_normals else ("xolp",))
+            kw = {} if self.pol_angles is None else {"angles": self.pol_angles}
+            out = pdpolar.polar_forward(inputs[("pol", 0, 0)], want=("xolp", "normals") if self.augment_normals else ("xolp",), **kw)
             inputs[("xolp", 0, 0)] = out["xolp"]; normals = out.get("normals")
         feats = self.models["rgb_encoder"](inputs["color_aug", 0, 0].float())
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None

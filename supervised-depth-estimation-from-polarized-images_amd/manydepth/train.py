@@ -17,6 +17,10 @@ def main():
     # flag for it, and the library and the Trainer read no environment variable for it -- only this entry point does
     if os.environ.get("PD_BF16") == "1":
         opts.bf16 = True
+    # PD_POL_ANGLES="a,b,c,d": the calibrated polarizer angles in degrees, in the order of the planes of ("pol", 0, 0)
+    # (opt.pol_angles; default: the nominal 0/45/90/135 set) -- read here only, like PD_BF16
+    if os.environ.get("PD_POL_ANGLES"):
+        opts.pol_angles = [float(x) for x in os.environ["PD_POL_ANGLES"].split(",")]
     if int(os.environ.get("WORLD_SIZE", 1)) > 1 and not torch.distributed.is_initialized():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
         torch.distributed.init_process_group("nccl")      # "nccl" is RCCL on ROCm

@@ -111,6 +111,11 @@ class Trainer:
         self.distributed = torch.distributed.is_available() and torch.distributed.is_initialized()
         self.rank = torch.distributed.get_rank() if self.distributed else 0
 
+        # calibrated polarizer angles (degrees, in the order of the planes of ("pol", 0, 0)): not a reference CLI flag --
+        # selected on the options object (``opt.pol_angles``; manydepth/train.py maps PD_POL_ANGLES="a,b,c,d" onto it).
+        # None = the nominal 0/45/90/135 set; given, K1 runs its general kernel (polardepth.polar.polar_forward(angles=))
+        self.pol_angles = pdpolar.angles_from_degrees(getattr(self.opt, "pol_angles", None))
+
         timestamp = datetime.now()
         self.data_path, self.data_path_val, self.log_dir = self.opt.data_path, self.opt.data_path_val, self.opt.log_dir
         self.log_path = os.path.join(self.opt.log_dir, self.opt.model_name + '_' + timestamp.strftime("%m-%d_%H-%M-%S"))
@@ -306,11 +311,17 @@ class Trainer:
             want = ["xolp"] + (["normals"] if self.opt.augment_normals else [])
             pol = inputs[("pol", 0, 0)]
             if pol.shape[2] != self.opt.height or pol.shape[3] > self.opt.width:
+                if pol.dtype != torch.uint8:
+                    raise ValueError(f'("pol", 0, 0) is {pol.dtype} {tuple(pol.shape[2:])}: the device LANCZOS resize serves uint8 '
+                                     f"planes only -- hand over 16-bit / float planes at {self.opt.height} rows and at most "
+                                     f"{self.opt.width} columns")
                 # raw frames from the loader (HAMMER_Dataset(raw_pol=True)): Pillow-exact LANCZOS resize on the device
                 pol = pdresize.resize_lanczos_u8(pol, (self.opt.height, self.opt.width))
             # planes narrower than the network width (512x612 frames -> 512x640): K1 pads on the fly
+            # (uint16 / float32 planes, or calibrated angles: the general kernel; otherwise the call is unchanged)
+            kw = {} if self.pol_angles is None else {"angles": self.pol_angles}
             out = pdpolar.polar_forward(pol, want=tuple(want),
-                                        out_width=self.opt.width if pol.shape[3] < self.opt.width else None)
+                                        out_width=self.opt.width if pol.shape[3] < self.opt.width else None, **kw)
             inputs[("xolp", 0, 0)] = out["xolp"]
             normals = out.get("normals")
         return normals

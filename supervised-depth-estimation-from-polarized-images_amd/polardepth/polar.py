@@ -65,8 +65,60 @@ def _device_tables(n, device_index):
     return blob.to(torch.device("cuda", device_index))
 
 
+STD_ANGLES = np.array([0.0, 45.0, 90.0, 135.0]) * np.pi / 180
+DTYPE_U8, DTYPE_U16, DTYPE_F32 = 0, 1, 2      # PD_POLAR_U8 / _U16 / _F32
+_GENERAL_DTYPES = {torch.uint8: DTYPE_U8, torch.uint16: DTYPE_U16, torch.float32: DTYPE_F32}
+
+
+def fit_matrix(angles):
+    """The 3x4 least-squares coefficients P = (A^T A)^-1 A^T of I(theta) = x0 + x1 cos 2theta + x2 sin 2theta for four
+    polarizer angles in radians (pd_polar_fit_matrix: host only, fp64).  float64 [3,4]; ValueError for anything but four
+    finite angles of rank 3."""
+    a = np.ascontiguousarray(np.asarray(angles, dtype=np.float64).reshape(-1))
+    if a.size != 4:
+        raise ValueError(f"fit_matrix needs four polarizer angles, got {a.size}")
+    coef = np.empty(12, dtype=np.float64)
+    dp = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    if lib.pd_polar_fit_matrix(dp(a), dp(coef)) != 0:
+        msg = lib.pd_last_error()
+        raise ValueError(msg.decode() if msg else "pd_polar_fit_matrix failed")
+    return coef.reshape(3, 4)
+
+
+def angles_from_degrees(spec):
+    """Four polarizer angles in degrees -- a sequence, or a string "a,b,c,d" -- as a float64 radians array for
+    ``polar_forward(angles=)``; None stays None.  ValueError unless they are four finite angles of rank 3."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        spec = [float(x) for x in spec.split(",")]
+    angles = np.asarray(spec, dtype=np.float64).reshape(-1) * np.pi / 180
+    fit_matrix(angles)
+    return angles
+
+
+def _polar_general(pol, angles, n, want, tables, out_width, out, precise):
+    """The general kernel (pd_polar_general_fwd): any four angles, uint8 / uint16 / float32 planes."""
+    coef = np.ascontiguousarray(fit_matrix(STD_ANGLES if angles is None else angles).reshape(-1))
+    pol = pol.contiguous()
+    B, _, H, W = pol.shape
+    if tables is None and "normals" in want:
+        tables = _device_tables(float(n), pol.device.index)
+    out = dict(out) if out is not None else {}      # pre-allocated outputs may be passed in
+    Wout = W if out_width is None else int(out_width)
+    for key, ch in (("iun", 1), ("xolp", 2), ("xolp_std", 2), ("normals", 9)):
+        if key in want and key not in out:
+            out[key] = torch.empty((B, ch, H, Wout), dtype=torch.float32, device=pol.device)
+    with torch.cuda.device(pol.device):
+        check(lib.pd_polar_general_fwd(ptr(pol), _GENERAL_DTYPES[pol.dtype], coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                       ptr(out.get("iun")), ptr(out.get("xolp")), ptr(out.get("xolp_std")),
+                                       ptr(out.get("normals")), ptr(tables), 0 if tables is None else tables.numel(),
+                                       B, H, W, Wout, int(bool(precise)), stream_ptr()), "pd_polar_general_fwd")
+    return out
+
+
 def polar_forward(pol, n=1.5, mode=MODE_LS, mask=None, want=("xolp",), tables=None, out_width=None, out=None,
-                  precise=False, ieee_rho=False, nt_loads=None):
+                  precise=False, ieee_rho=False, nt_loads=None, angles=None):
     """Run K1 on ``pol`` [B,4,H,W] uint8 (planes 0/45/90/135 deg) on the GPU.
 
     want: any of "xolp", "xolp_std", "normals", "ints".  Returns a dict of fp32 NCHW tensors
@@ -76,9 +128,25 @@ def polar_forward(pol, n=1.5, mode=MODE_LS, mask=None, want=("xolp",), tables=No
     ieee_rho=True selects PD_POLAR_IEEE_RHO (the literal fp64 sqrt/div sequence for every pixel: same bits, slower).
     nt_loads=True / False forces the nontemporal hint on / off the plane loads (PD_POLAR_NT_LOADS / PD_POLAR_PLAIN_LOADS:
     measurement; None = the library's size rule).
+
+    angles (four polarizer angles in radians, in the order of the planes) or a uint16 / float32 ``pol`` select the general
+    kernel (pd_polar_general_fwd: fp64 least-squares fit per pixel instead of the look-up tables; ``angles=None`` then means
+    0/45/90/135 deg).  It also serves want "iun" ([B,1,H,W], the unpolarised intensity); it has no Stokes mode, mask,
+    "ints", ieee_rho or nt_loads (ValueError).  uint8 planes without ``angles`` take K1 exactly as before.
     """
     if not (isinstance(pol, torch.Tensor) and pol.is_cuda):
         raise RuntimeError("polar_forward needs a CUDA(HIP) uint8 tensor; there is no CPU fallback")
+    if angles is not None or pol.dtype in (torch.uint16, torch.float32):
+        if pol.dtype not in _GENERAL_DTYPES or pol.dim() != 4 or pol.shape[1] != 4:
+            raise ValueError(f"pol must be uint8, uint16 or float32 [B,4,H,W], got {pol.dtype} {tuple(pol.shape)}")
+        bad = [name for name, on in (("mode=MODE_STOKES", mode != MODE_LS), ("mask", mask is not None),
+                                     ('want "ints"', "ints" in want), ("ieee_rho", bool(ieee_rho)),
+                                     ("nt_loads", nt_loads is not None)) if on]
+        if bad:
+            raise ValueError("polar_forward: the general kernel (angles= / uint16 / float32 planes) has no " + ", ".join(bad))
+        return _polar_general(pol, angles, n, want, tables, out_width, out, precise)
+    if "iun" in want:
+        raise ValueError('polar_forward: want "iun" is served by the general kernel only (pass angles=)')
     if pol.dtype != torch.uint8 or pol.dim() != 4 or pol.shape[1] != 4:
         raise ValueError(f"pol must be uint8 [B,4,H,W], got {pol.dtype} {tuple(pol.shape)}")
     pol = pol.contiguous()

@@ -210,8 +210,12 @@ long pd_conv2d_stats_rows(long M, int Cout);
  * row-window form --; 2 | 1: the per-tap gather kernel with 256- | 128-row tiles) when pd_conv2d / pd_conv2d_add send this shape (16-byte aligned NHWC operands assumed) to the kernel that forms the fp32
  * products on the bf16 matrix cores (conv_igemm_x3_kernel: x = hi + mid + lo in bf16, six MFMAs per 32x32x16 block, fp32
  * accumulation; PD_CONV_FP32_MFMA in `flags` keeps every layer on the fp32 MFMA): zero padding, the stride-1 data gradient or 3x3 reflection padding (a same-size layer is assumed), C % 4 == 0 and >= 8 (16-channel groups, the last may be partly empty),
- * Cout % 64 == 0, at least 512 tiles of 256 x 64 (M % 256 == 0) or 320 of 128 x 64 (M % 128 == 0), no out_scale, activation none or ELU.  The profiler label of a launch
- * (ops._igemm_label) and bench.py's roofline object use it. */
+ * Cout % 64 == 0, at least 512 tiles of 256 x 64 (M % 256 == 0) or 320 of 128 x 64 (M % 128 == 0), no out_scale, activation none or ELU.
+ * Who decides: route_conv (csrc/conv.hip) routes every launch, and this query, pd_conv2d_uses_bf16 and pd_conv2d_route read the
+ * same function's answer for a dense NHWC tensor of that shape (x and y 16-byte aligned, ldy = Cout, no addend, no BatchNorm
+ * statistics, the input grid taken to be the output grid; Ho = Wo = 0: a plane no halo tile divides) -- so for C % 4 != 0,
+ * which the 16-byte path cannot read, they answer 0 / the general kernel like the launch, where earlier versions could name
+ * a bf16-split kernel such a tensor never reached.  bench.py's roofline object uses it. */
 int pd_conv2d_uses_x3(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int act, int has_out_scale,
                       int Ho, int Wo, unsigned flags);
 /* 3 when pd_conv2d / pd_conv2d_add / pd_conv2d_rect run this shape on the single-bf16 form of the halo-tile kernel
@@ -220,6 +224,14 @@ int pd_conv2d_uses_x3(long M, int Cout, int C, int KH, int KW, int stride, int p
  * of pd_conv2d_uses_x3's answer).  Pure host logic, the same arguments as pd_conv2d_uses_x3. */
 int pd_conv2d_uses_bf16(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int act, int has_out_scale,
                         int Ho, int Wo, unsigned flags);
+/* The kernel pd_conv2d / pd_conv2d_add launch for this shape (the arguments and the tensor of pd_conv2d_uses_x3), as
+ * family | BN << 4 | BM << 12: family 0 conv_igemm_kernel (general gather) | 1 conv_igemm_uni_kernel (uniform-tap) |
+ * 2 conv_igemm_x3_kernel (bf16-split, per-tap gather) | 3 conv_halo_x3_kernel (bf16-split, halo tile) | 4 conv_halo_bf16_kernel
+ * (its single-bf16 form, PD_CONV_BF16); BM x BN the workgroup's tile of the output matrix, rows x columns (halo tile: 256
+ * pixels x 64 | 32 channels).  A flags word pd_conv2d refuses is read without PD_CONV_BF16.  Pure host logic; the profiler label
+ * of a launch (ops._igemm_label) is made of this answer alone. */
+int pd_conv2d_route(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int act, int has_out_scale,
+                    int Ho, int Wo, unsigned flags);
 int pd_conv2d(const void* x, const void* w, const void* bias, const void* out_scale, void* y, void* stats,
               int N, int H, int W, int C, long sN, long sH, long sW, long sC,
               int Ho, int Wo, int Cout, int KH, int KW, int stride, int pad, int mode, int act,
@@ -286,7 +298,10 @@ int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* dbias, void* 
  * operands split once per tile and read through ds_read_b64_tr_b16) or
  * 1 when pd_conv2d_wgrad sends this shape (zero or reflection padding; 16-byte aligned NHWC operands assumed) to the kernel that forms the
  * fp32 products on the bf16 matrix cores, every element split once (conv_wgrad_x3c_kernel; PD_CONV_FP32_MFMA: fp32 MFMA) --
- * the profiler label of a launch and bench.py's roofline object use it. */
+ * the profiler label of a launch and bench.py's roofline object use it.  Reflection padding other than ReflectionPad2d(1) in
+ * front of a same-size 3x3 runs the general kernel (0).  Who decides: route_wgrad (csrc/conv.hip) routes every launch, and this
+ * query and pd_conv2d_wgrad_uses_bf16 read the same function's answer for dense, 16-byte aligned NHWC x and dy (ldd = Cout) with
+ * a workspace of pd_conv2d_wgrad_workspace(M, Cout, K, flags) bytes; an empty output grid: 0. */
 int pd_conv2d_wgrad_uses_x3(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho, int Wo,
                             unsigned flags);
 /* 3 (conv_wgrad_roll_bf16_kernel) or 2 (conv_wgrad_halo_bf16_kernel): pd_conv2d_wgrad runs this shape on the single-bf16 form

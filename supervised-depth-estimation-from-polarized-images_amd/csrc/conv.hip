@@ -19,6 +19,10 @@
 // NHWC store with an arbitrary row stride (lets a layer write into a slice of a concat buffer).
 //
 // The weight-gradient kernel (contraction over pixels, "TN" GEMM) lives below in the same file.
+//
+// Which kernel family a launch gets is decided in ONE host function per entry point -- route_conv (forward / data gradient) and
+// route_wgrad (weight gradient) -- from the eligibility predicates that sit next to their kernels.  The launch functions map a
+// route to template arguments and test nothing else; the host queries of include/polardepth.h read the same routes.
 #include "pd_common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -35,6 +39,21 @@ constexpr unsigned OOB = 0x80000000u;   // byte offset beyond every buffer exten
 
 enum { MODE_ZERO = 0, MODE_REFLECT = 1, MODE_TRANSPOSED = 2 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2, ACT_SIGMOID = 3 };
+
+// compile-time integers as function arguments (register-array indices in the kernels, template arguments in the launchers)
+#define PD_I(n) std::integral_constant<int, n>{}
+#define PD_SB __builtin_amdgcn_sched_barrier(0);
+
+// f(tag) with a run-time padding mode / switch as a compile-time constant: f's `decltype(tag)::value` is a template argument
+template <typename F> void with_mode(int mode, F&& f) {
+    if (mode == MODE_ZERO) f(PD_I(MODE_ZERO)); else if (mode == MODE_REFLECT) f(PD_I(MODE_REFLECT)); else f(PD_I(MODE_TRANSPOSED));
+}
+template <typename F> void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
+// the 16-byte gather path of the activation tensor: whole channel quads, channels contiguous, every stride a whole quad
+inline bool vec16_ok(const void* x, int C, long sN, long sH, long sW, long sC, int affine) {
+    return (C % 4 == 0) && sC == 1 && (sW % 4 == 0) && (sH % 4 == 0) && (sN % 4 == 0) && !affine && pd::aligned16(x);
+}
 
 struct ConvArgs {
     const float* x;
@@ -1062,8 +1081,6 @@ __global__ __launch_bounds__(NT, RB == 2 ? 3 : 4) void conv_igemm_x3_kernel(cons
             const u32x4 bv = T == 0 ? fb[J][0] : T == 1 ? fb[J][1] : T == 2 ? fb[J][2] : T == 3 ? fb[J][0] : T == 4 ? fb[J][1] : fb[J][0];
             acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(u32x4{av[0], av[1], av[2], av[3]}), bf(bv), acc[I][J], 0, 0, 0);
         };
-#define PD_I(n) std::integral_constant<int, n>{}
-#define PD_SB __builtin_amdgcn_sched_barrier(0);
         x3::sp_h<0>(x0, t0); x3::sp_h<1>(x0, t0); x3::sp_h<2>(x0, t0); x3::sp_h<3>(x0, t0);
         PD_SB
         if constexpr (RB == 1) {       // one row block: 12 MFMAs, its mid / lo terms and the weights' split behind them
@@ -1113,8 +1130,6 @@ __global__ __launch_bounds__(NT, RB == 2 ? 3 : 4) void conv_igemm_x3_kernel(cons
         mm(t1, PD_I(RB - 1), PD_I(9)); x3::sp_l<3>(t1); PD_SB
         mm(t1, PD_I(RB - 1), PD_I(10)); mm(t1, PD_I(RB - 1), PD_I(11));
         }
-#undef PD_SB
-#undef PD_I
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     };
@@ -1223,22 +1238,22 @@ __global__ __launch_bounds__(NT, RB == 2 ? 3 : 4) void conv_igemm_x3_kernel(cons
 // are worth it from 320 on (3x3x512 @16x20: 117 -> 134 TF).  PD_CONV_BF16X3 in the caller's flags waives both counts.
 constexpr long X3_MIN_WG = 512, X3_MIN_WG1 = 320;
 
-// 0: not for the bf16-split kernel; 2 | 1: its row blocks per wave (256- | 128-row tiles)
 // what every bf16-split forward / data-gradient kernel needs of a launch (tile shapes and channel counts are the kernels' own)
-static bool x3_common_ok(const ConvArgs& a, bool vec) {
+static bool x3_common_ok(const ConvArgs& a, bool vec, bool has_scale) {
     const bool on = !(a.flags & PD_CONV_FP32_MFMA);
     return on && vec && a.KH * a.KW <= 31 && a.pad < a.KH && a.pad_w < a.KW &&
            (a.mode == MODE_ZERO || (a.mode == MODE_TRANSPOSED && a.sshift == 0) ||
             (a.mode == MODE_REFLECT && a.KH == 3 && a.KW == 3 && a.pad == 1 && a.pad_w == 1 && a.stride == 1 && a.Ho == a.H &&
              a.Wo == a.W && a.H >= 3 && a.W >= 3)) &&
-           !a.oscale && (a.act == ACT_NONE || a.act == ACT_ELU) && (a.ldy & 3) == 0 && ((size_t)a.y & 15) == 0 &&
+           !has_scale && (a.act == ACT_NONE || a.act == ACT_ELU) && (a.ldy & 3) == 0 && ((size_t)a.y & 15) == 0 &&
            (!a.add || ((a.ld_add & 3) == 0 && ((size_t)a.add & 15) == 0)) && (long)a.Co * a.K * 4 < 0x7fffffffL;
 }
-static int x3_eligible(const ConvArgs& a, bool vec) {
+// the per-tap gather kernel, given x3_common_ok: 0: not for it; 2 | 1: its row blocks per wave (256- | 128-row tiles)
+static int x3_eligible(const ConvArgs& a) {
     const bool force = (a.flags & PD_CONV_BF16X3) != 0;
     // (C % 4 == 0 is part of `vec`; a partly empty last channel group may at most double the contraction: C >= 8)
     // (whole 128-row tiles, except for a data gradient without BatchNorm statistics: its last tile may be partial)
-    if (!(x3_common_ok(a, vec) && (a.C + x3::CK - 1) / x3::CK * x3::CK <= 2 * a.C && a.Co % x3::BN == 0 &&
+    if (!((a.C + x3::CK - 1) / x3::CK * x3::CK <= 2 * a.C && a.Co % x3::BN == 0 &&
           (a.M % 128 == 0 || (a.mode == MODE_TRANSPOSED && !a.stats))))
         return 0;
     const long ct = a.Co / x3::BN;
@@ -1253,101 +1268,152 @@ static int x3_eligible(const ConvArgs& a, bool vec) {
 // 5x5x256x512: 13 MB) would then be streamed through every L2 by every row tile -- 1.1 GB per launch from the Infinity Cache
 // for 3x3x512 @16x20, which bounds it (twice the waves per CU changed nothing) -- so with >= 8 column tiles the COLUMN tile goes
 // outside: an XCD keeps its slice of the filter and streams the (smaller) activations once.
-static int x3_nmajor(const ConvArgs& a) { return (long)a.Co * a.K * 4 > (3L << 20) && a.ntiles >= 8 && a.ntiles % 8 == 0; }
+static int x3_nmajor(const ConvArgs& a, int ntiles) { return (long)a.Co * a.K * 4 > (3L << 20) && ntiles >= 8 && ntiles % 8 == 0; }
 #include "conv_x3_halo.hpp"
 
-static int launch_conv_x3(ConvArgs& a, int rb, hipStream_t st) {
-    a.mtiles = (int)((a.M + 128 * rb - 1) / (128 * rb));
-    a.ntiles = a.Co / x3::BN;
-    a.nmajor = x3_nmajor(a);
-    const long nblk = (long)a.mtiles * a.ntiles;
-    const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(NT);
-    if (rb == 2) {
-        if (a.mode == MODE_ZERO) hipLaunchKernelGGL((conv_igemm_x3_kernel<MODE_ZERO, 2>), grid, block, 0, st, a);
-        else if (a.mode == MODE_REFLECT) hipLaunchKernelGGL((conv_igemm_x3_kernel<MODE_REFLECT, 2>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((conv_igemm_x3_kernel<MODE_TRANSPOSED, 2>), grid, block, 0, st, a);
-    } else {
-        if (a.mode == MODE_ZERO) hipLaunchKernelGGL((conv_igemm_x3_kernel<MODE_ZERO, 1>), grid, block, 0, st, a);
-        else if (a.mode == MODE_REFLECT) hipLaunchKernelGGL((conv_igemm_x3_kernel<MODE_REFLECT, 1>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((conv_igemm_x3_kernel<MODE_TRANSPOSED, 1>), grid, block, 0, st, a);
+// ---- routing: which kernel one forward convolution / data gradient gets, and everything its launch needs.  route_conv is the
+// ONLY place that decides; launch_conv maps a route to template arguments, and the host queries (pd_conv2d_uses_x3,
+// pd_conv2d_uses_bf16, pd_conv2d_route -- hence the profiler labels of ops.py) read the route of the dense tensor they document.
+enum ConvFamily { CONV_NONE = -1, CONV_GENERAL = 0, CONV_UNI = 1, CONV_X3 = 2, CONV_HALO = 3 };
+struct ConvRoute {
+    int family;             // CONV_NONE: a separate column padding (pd_conv2d_rect) outside the uniform-tap kernel
+    int bm, bn, wm, wn;     // workgroup tile (rows x columns; halo-tile kernel: 256 pixels x 32 ncb columns), wave tile (gather kernels)
+    int mtiles, ntiles, nmajor;
+    bool vec;               // general kernel: 16-byte gather
+    int ns, rb;             // uniform-tap kernel: ring depth; bf16-split gather kernel: row blocks per wave (2 | 1: 256- | 128-row tiles)
+    HaloPlan halo;          // halo-tile kernel
+    int terms;              // ... bf16 terms per operand: 3, or 1 under PD_CONV_BF16
+};
+
+static ConvRoute route_conv(const ConvArgs& a, bool vec, bool has_scale) {
+    ConvRoute r{};
+    r.vec = vec; r.ns = 2; r.terms = 3;
+    const auto tiles = [&](int family, int bm, int bn, int wm, int wn, long mtiles) {
+        r.family = family; r.bm = bm; r.bn = bn; r.wm = wm; r.wn = wn;
+        r.mtiles = (int)mtiles; r.ntiles = (a.Co + bn - 1) / bn;
+    };
+    if (x3_common_ok(a, vec, has_scale)) {
+        // the halo-tile kernel (every activation element staged and split once per tile) where its tiling fits
+        if (!(a.flags & PD_CONV_X3_IM2COL) && x3_halo_plan(a, r.halo)) {
+            tiles(CONV_HALO, 256, 32 * r.halo.ncb, 0, 0, (long)a.N * (a.Ho / (256 / r.halo.tw)) * (a.Wo / r.halo.tw));
+            r.terms = (a.flags & PD_CONV_BF16) ? 1 : 3;       // PD_CONV_BF16 changes the arithmetic of this kernel only
+        } else if ((r.rb = x3_eligible(a)) != 0) {
+            tiles(CONV_X3, 128 * r.rb, x3::BN, 32 * r.rb, x3::BN, (a.M + 128 * r.rb - 1) / (128 * r.rb));
+        }
+        if (r.rb || r.family == CONV_HALO) { r.nmajor = x3_nmajor(a, r.ntiles); return r; }
     }
-    return pd::check_launch("pd_conv2d");
+    // fp32 MFMA tiles.  96 output columns (the data gradient of the decoder's 96 -> 32 layer): three 32-wide column tiles
+    // instead of a full and a half-empty 64-wide one (a quarter of the matrix work of that launch was padding)
+    const int bm = pd_conv2d_tile_m(a.M, a.Co);
+    const long mt = (a.M + bm - 1) / bm;
+    if (a.Co == 96 && bm == 128) tiles(CONV_GENERAL, 128, 32, 32, 32, mt);
+    else if (a.Co > 32 && bm == 128) tiles(CONV_GENERAL, 128, 64, 64, 32, mt);
+    else if (a.Co > 32) tiles(CONV_GENERAL, 64, 64, 32, 32, mt);
+    else if (a.Co > 16) tiles(CONV_GENERAL, 128, 32, 32, 32, mt);
+    else tiles(CONV_GENERAL, 128, 16, 32, 16, mt);   // 16x16x4 MFMA tiles
+    // uniform-tap kernel (direct-to-LDS staging) unless the caller asks for the general one  (reflection: pad < H, W is
+    // checked by pd_conv2d)
+    if (vec && !(a.flags & PD_CONV_GENERAL_KERNELS) && r.wn == 32 && a.C % BK == 0 && a.KH * a.KW <= 31 && a.pad < a.KH &&
+        a.pad_w < a.KW && (a.mode == MODE_ZERO || a.mode == MODE_REFLECT || (a.mode == MODE_TRANSPOSED && a.sshift == 0))) {
+        r.family = CONV_UNI;
+        // ring depth: 2 for the 128-row tiles (3 workgroups per CU); 3 for the 64x64 tile of the small-M layers, whose
+        // short chunks (16 MFMAs per wave) leave the loads half the time to land: 118 -> 135 TF on 3x3x256 @32x40
+        r.ns = (r.bm == 64 && a.mode != MODE_REFLECT) ? 3 : 2;
+    } else if (a.pad_w != a.pad) {
+        r.family = CONV_NONE;
+    }
+    return r;
 }
 
 template <int BM, int BN, int WM, int WN>
-int launch_conv(ConvArgs& a, bool vec, hipStream_t st) {
-    a.mtiles = (int)((a.M + BM - 1) / BM);
-    a.ntiles = (a.Co + BN - 1) / BN;
-    const long nblk = (long)a.mtiles * a.ntiles;
-    const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(NT);
-#define PD_LAUNCH(V, MD) hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, V, MD>), grid, block, 0, st, a)
-#define PD_LAUNCH_DMA(MD) hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, MD, true>), grid, block, 0, st, a)
-    constexpr bool dma = true;                                    // direct-to-LDS staging (the register-staged path serves the scalar gather)
-    const bool uni_on = !(a.flags & PD_CONV_GENERAL_KERNELS);       // uniform-tap kernel unless the caller asks for the general one
-    if constexpr (BN % 32 == 0 && WN == 32) {
-        const bool uni = vec && dma && uni_on && a.C % BK == 0 && a.KH * a.KW <= 31 && a.pad < a.KH && a.pad_w < a.KW &&
-                         (a.mode == MODE_ZERO || a.mode == MODE_REFLECT || (a.mode == MODE_TRANSPOSED && a.sshift == 0));
-        if (uni && a.mode == MODE_REFLECT) {       // (pad < H, W is checked by pd_conv2d)
-            hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MODE_REFLECT, 2>), grid, block, 0, st, a);
-            return pd::check_launch("pd_conv2d");
-        }
-        if (uni) {
-            // ring depth: 2 for the 128-row tiles (3 workgroups per CU); 3 for the 64x64 tile of the small-M layers, whose
-            // short chunks (16 MFMAs per wave) leave the loads half the time to land: 118 -> 135 TF on 3x3x256 @32x40
-            const int ns = BM == 64 ? 3 : 2;
-            if (ns == 2) {
-                if (a.mode == MODE_ZERO) hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MODE_ZERO, 2>), grid, block, 0, st, a);
-                else hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MODE_TRANSPOSED, 2>), grid, block, 0, st, a);
-            } else {
-                if (a.mode == MODE_ZERO) hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MODE_ZERO, 3>), grid, block, 0, st, a);
-                else hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MODE_TRANSPOSED, 3>), grid, block, 0, st, a);
-            }
-            return pd::check_launch("pd_conv2d");
-        }
-    }
-    if (a.pad_w != a.pad) return pd::fail(PD_EINVAL, "pd_conv2d_rect: shape outside the uniform-tap kernel (C %% 32, 16-byte aligned NHWC)");
-    if (vec && dma) {
-        if (a.mode == MODE_ZERO) PD_LAUNCH_DMA(MODE_ZERO);
-        else if (a.mode == MODE_REFLECT) PD_LAUNCH_DMA(MODE_REFLECT);
-        else PD_LAUNCH_DMA(MODE_TRANSPOSED);
-    } else if (vec) {
-        if (a.mode == MODE_ZERO) PD_LAUNCH(true, MODE_ZERO);
-        else if (a.mode == MODE_REFLECT) PD_LAUNCH(true, MODE_REFLECT);
-        else PD_LAUNCH(true, MODE_TRANSPOSED);
-    } else {
-        if (a.mode == MODE_ZERO) PD_LAUNCH(false, MODE_ZERO);
-        else if (a.mode == MODE_REFLECT) PD_LAUNCH(false, MODE_REFLECT);
-        else PD_LAUNCH(false, MODE_TRANSPOSED);
-    }
-#undef PD_LAUNCH
-#undef PD_LAUNCH_DMA
+void launch_conv_fp32(const ConvArgs& a, const ConvRoute& r, dim3 grid, hipStream_t st) {
+    const dim3 block(NT);
+    constexpr bool dma = true;        // direct-to-LDS staging (the register-staged path serves the scalar gather)
+    if constexpr (WN == 32)
+        if (r.family == CONV_UNI) return with_mode(a.mode, [&](auto md) {
+            constexpr int MD = decltype(md)::value;
+            if (r.ns == 2) hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MD, 2>), grid, block, 0, st, a);
+            else if constexpr (MD != MODE_REFLECT) hipLaunchKernelGGL((conv_igemm_uni_kernel<BM, BN, WM, WN, MD, 3>), grid, block, 0, st, a);
+        });
+    with_mode(a.mode, [&](auto md) {
+        constexpr int MD = decltype(md)::value;
+        if (r.vec && dma) hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, MD, true>), grid, block, 0, st, a);
+        else if (r.vec) hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, MD>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, MD>), grid, block, 0, st, a);
+    });
+}
+
+// route -> template arguments; no test of the shape here
+static int launch_conv(ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+    a.mtiles = r.mtiles; a.ntiles = r.ntiles; a.nmajor = r.nmajor;
+    const dim3 grid((unsigned)(((long)r.mtiles * r.ntiles + 7) / 8 * 8)), block(NT);
+    if (r.family == CONV_HALO) {
+        if (r.terms == 1) launch_conv_x3_halo<1>(a, r.halo, grid, st); else launch_conv_x3_halo<3>(a, r.halo, grid, st);
+    } else if (r.family == CONV_X3) {
+        with_mode(a.mode, [&](auto md) {
+            constexpr int MD = decltype(md)::value;
+            if (r.rb == 2) hipLaunchKernelGGL((conv_igemm_x3_kernel<MD, 2>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((conv_igemm_x3_kernel<MD, 1>), grid, block, 0, st, a);
+        });
+    } else if (r.bn == 64 && r.bm == 128) launch_conv_fp32<128, 64, 64, 32>(a, r, grid, st);
+    else if (r.bn == 64) launch_conv_fp32<64, 64, 32, 32>(a, r, grid, st);
+    else if (r.bn == 32) launch_conv_fp32<128, 32, 32, 32>(a, r, grid, st);
+    else launch_conv_fp32<128, 16, 32, 16>(a, r, grid, st);
     return pd::check_launch("pd_conv2d");
 }
 
+// Everything of ConvArgs but the tensor pointers and the tile counts (launch_conv), from the arguments of pd_conv2d
+static void fill_conv_args(ConvArgs& a, int N, int H, int W, int C, long sN, long sH, long sW, long sC, int Ho, int Wo, int Co,
+                           int KH, int KW, int stride, int pad, int pad_w, int mode, int act, int affine, float sub, float div,
+                           long ldy, unsigned flags) {
+    a.N = N; a.H = H; a.W = W; a.C = C; a.sN = sN; a.sH = sH; a.sW = sW; a.sC = sC;
+    a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_w = pad_w;
+    a.mode = mode; a.act = act; a.affine = affine; a.sub = sub; a.div = div;
+    a.K = KH * KW * C; a.M = (long)N * Ho * Wo; a.ldy = ldy; a.flags = flags;
+    a.sshift = 0;
+    while ((1 << a.sshift) < stride) ++a.sshift;
+    a.stats_rows = pd_conv2d_tile_m(a.M, Co);
+    a.w_bytes = (unsigned)((long)Co * a.K * 4);       // (< 2 GiB: checked by pd_conv2d)
+    const auto magic = [](long d, unsigned& mg, unsigned& sh) {       // n / d == mulhi(n, mg) >> sh for 0 <= n < 2^31, d >= 2
+        if (d <= 1 || d >= (1L << 31)) { mg = 0; sh = 0; return; }
+        int l = 0;
+        while ((1L << l) < d) ++l;                                // ceil(log2 d) >= 1
+        mg = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned long long)d - 1) / (unsigned long long)d);
+        sh = (unsigned)(l - 1);
+    };
+    magic((long)Ho * Wo, a.mg_hw, a.sh_hw);
+    magic(Wo, a.mg_wo, a.sh_wo);
+}
+static bool conv_vec(const ConvArgs& a) { return vec16_ok(a.x, a.C, a.sN, a.sH, a.sW, a.sC, a.affine) && pd::aligned16(a.w); }
+
 }  // namespace
+
+// The route of the tensor the queries document: dense, 16-byte aligned NHWC x and y (ldy = Cout), no addend, no BatchNorm
+// statistics, the input grid taken to be the output grid -- M is the caller's, also where it is no whole number of images.
+// Ho = Wo = 0 (grid unknown): a 3 x 3 plane stands in, the smallest legal same-size reflection layer; no halo tile divides it.
+extern "C" int pd_conv2d_route(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int act,
+                               int has_out_scale, int Ho, int Wo, unsigned flags) {
+    if (!pd::conv_flags_ok(flags)) flags &= ~PD_CONV_BF16;       // (no one-term form under a word pd_conv2d refuses)
+    const bool grid = Ho > 0 && Wo > 0;
+    const int H = grid ? Ho : 3, W = grid ? Wo : 3;
+    ConvArgs a{};
+    fill_conv_args(a, grid ? (int)(M / ((long)H * W)) : 1, H, W, C, (long)H * W * C, (long)W * C, C, 1, H, W, Co, KH, KW, stride, pad, pad,
+                   mode, act, 0, 0.f, 1.f, Co, flags);
+    a.M = M; a.stats_rows = pd_conv2d_tile_m(M, Co);
+    const ConvRoute r = route_conv(a, conv_vec(a), has_out_scale != 0);
+    return (r.family == CONV_HALO && r.terms == 1 ? 4 : r.family) | r.bn << 4 | r.bm << 12;
+}
 
 extern "C" int pd_conv2d_uses_x3(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int act,
                                  int has_out_scale, int Ho, int Wo, unsigned flags) {
-    ConvArgs a{};
-    a.flags = flags;
-    a.M = M; a.Co = Co; a.C = C; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = a.pad_w = pad; a.mode = mode; a.act = act;
-    a.K = KH * KW * C; a.ldy = Co;
-    a.H = a.Ho = Ho > 0 ? Ho : 16;            // (reflection padding: a same-size 3x3 layer is assumed)
-    a.W = a.Wo = Wo > 0 ? Wo : 16;
-    a.N = Ho > 0 && Wo > 0 ? (int)(M / ((long)Ho * Wo)) : 1;
-    a.sC = 1; a.sW = C; a.sH = (long)a.W * C; a.sN = a.sH * a.H;
-    a.oscale = has_out_scale ? reinterpret_cast<const float*>(16) : nullptr;
-    while ((1 << a.sshift) < stride) ++a.sshift;
-    a.stats_rows = pd_conv2d_tile_m(M, Co);
-    if (x3_common_ok(a, true) && !(flags & PD_CONV_X3_IM2COL) && Ho > 0 && Wo > 0 && x3_halo_eligible(a)) return 3;
-    return x3_eligible(a, true);
+    const int r = pd_conv2d_route(M, Co, C, KH, KW, stride, pad, mode, act, has_out_scale, Ho, Wo, flags), family = r & 15;
+    return family >= CONV_HALO ? 3 : family == CONV_X3 ? (r >> 12) / 128 : 0;       // (256- | 128-row tiles: 2 | 1)
 }
 
-// PD_CONV_BF16 changes the arithmetic of the halo-tile kernel only (conv2d_impl below): its layers run the one-term form
+// PD_CONV_BF16 changes the arithmetic of the halo-tile kernel only: its layers run the one-term form
 extern "C" int pd_conv2d_uses_bf16(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int act,
                                    int has_out_scale, int Ho, int Wo, unsigned flags) {
-    if (!(flags & PD_CONV_BF16) || !pd::conv_flags_ok(flags)) return 0;
-    return pd_conv2d_uses_x3(M, Co, C, KH, KW, stride, pad, mode, act, has_out_scale, Ho, Wo, flags) == 3 ? 3 : 0;
+    return (pd_conv2d_route(M, Co, C, KH, KW, stride, pad, mode, act, has_out_scale, Ho, Wo, flags) & 15) == 4 ? 3 : 0;
 }
 
 extern "C" int pd_conv2d_tile_m(long M, int Co) {
@@ -1364,7 +1430,39 @@ static int conv2d_impl(const void* x, const void* w, const void* bias, const voi
                        const void* addend, long ld_add,
                        int N, int H, int W, int C, long sN, long sH, long sW, long sC,
                        int Ho, int Wo, int Co, int KH, int KW, int stride, int pad, int mode, int act,
-                       int affine, float sub, float div, long ldy, unsigned flags, void* stream, int pad_w = -1);
+                       int affine, float sub, float div, long ldy, unsigned flags, void* stream, int pad_w = -1) {
+    if (pad_w < 0) pad_w = pad;
+    PD_REQUIRE(pd::conv_flags_ok(flags), "pd_conv2d: bad flags 0x%x", flags);
+    PD_REQUIRE(x && w && y, "pd_conv2d: null tensor");
+    PD_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0 && Co > 0, "pd_conv2d: bad dims");
+    PD_REQUIRE(KH > 0 && KW > 0 && stride > 0 && pad >= 0, "pd_conv2d: bad filter geometry");
+    PD_REQUIRE(mode >= 0 && mode <= 2 && act >= 0 && act <= 3, "pd_conv2d: bad mode/act");
+    PD_REQUIRE(mode != MODE_REFLECT || (pad < H && pad < W), "pd_conv2d: reflect pad must be < input size");
+    PD_REQUIRE(ldy >= Co && ldy < (1L << 22), "pd_conv2d: bad output row stride %ld (Cout=%d)", ldy, Co);
+    if (mode == MODE_TRANSPOSED) {
+        PD_REQUIRE((stride & (stride - 1)) == 0, "pd_conv2d: transposed mode needs a power-of-two stride");
+        // (a SMALLER x grid is the leading part of that output grid: the missing rows / columns read as zero -- the
+        //  sub-filters of a phase-decomposed stride-2 data gradient need exactly that, see pd_dgrad_s2_filters)
+        PD_REQUIRE(H <= (Ho + 2 * pad - KH) / stride + 1 && W <= (Wo + 2 * pad_w - KW) / stride + 1,
+                   "pd_conv2d: transposed: x grid exceeds the forward output grid of a %dx%d input", Ho, Wo);
+    } else {
+        // a smaller output grid computes the leading Ho x Wo outputs only (asymmetric bottom/right padding)
+        PD_REQUIRE(Ho <= (H + 2 * pad - KH) / stride + 1 && Wo <= (W + 2 * pad_w - KW) / stride + 1,
+                   "pd_conv2d: output grid does not match input/filter geometry");
+    }
+    if (N == 0) return PD_OK;
+    ConvArgs a;
+    a.x = (const float*)x; a.w = (const float*)w; a.bias = (const float*)bias; a.oscale = (const float*)out_scale; a.y = (float*)y; a.stats = (float*)stats;
+    a.add = (const float*)addend; a.ld_add = ld_add;
+    fill_conv_args(a, N, H, W, C, sN, sH, sW, sC, Ho, Wo, Co, KH, KW, stride, pad, pad_w, mode, act, affine, sub, div, ldy, flags);
+    PD_REQUIRE((long)Co * a.K * 4 < 0x7fffffffL, "pd_conv2d: weight tensor too large for 32-bit offsets");
+    // 32-bit byte offsets are relative to the first image of a tile: a tile (up to 256 rows) may span ceil(256/(Ho*Wo))+1 images
+    const long span = 256 / ((long)Ho * Wo) + 2;
+    PD_REQUIRE(span * sN * 4 < 0x7fffffffL, "pd_conv2d: image too large for 32-bit offsets (%ld bytes per image)", sN * 4);
+    const ConvRoute r = route_conv(a, conv_vec(a), out_scale != nullptr);
+    if (r.family == CONV_NONE) return pd::fail(PD_EINVAL, "pd_conv2d_rect: shape outside the uniform-tap kernel (C %% 32, 16-byte aligned NHWC)");
+    return launch_conv(a, r, (hipStream_t)stream);
+}
 
 extern "C" int pd_conv2d(const void* x, const void* w, const void* bias, const void* out_scale, void* y, void* stats,
                          int N, int H, int W, int C, long sN, long sH, long sW, long sC,
@@ -1392,71 +1490,6 @@ extern "C" int pd_conv2d_rect(const void* x, const void* w, void* y, int N, int 
     PD_REQUIRE(!(flags & PD_CONV_GENERAL_KERNELS), "pd_conv2d_rect: the general kernel has no separate column padding");
     return conv2d_impl(x, w, nullptr, nullptr, y, nullptr, nullptr, 0, N, H, W, C, sN, sH, sW, sC, Ho, Wo, Co, KH, KW, 1,
                        pad_h, mode, ACT_NONE, 0, 0.f, 1.f, ldy, flags, stream, pad_w);
-}
-
-static int conv2d_impl(const void* x, const void* w, const void* bias, const void* out_scale, void* y, void* stats,
-                       const void* addend, long ld_add,
-                       int N, int H, int W, int C, long sN, long sH, long sW, long sC,
-                       int Ho, int Wo, int Co, int KH, int KW, int stride, int pad, int mode, int act,
-                       int affine, float sub, float div, long ldy, unsigned flags, void* stream, int pad_w) {
-    if (pad_w < 0) pad_w = pad;
-    PD_REQUIRE(pd::conv_flags_ok(flags), "pd_conv2d: bad flags 0x%x", flags);
-    PD_REQUIRE(x && w && y, "pd_conv2d: null tensor");
-    PD_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0 && Co > 0, "pd_conv2d: bad dims");
-    PD_REQUIRE(KH > 0 && KW > 0 && stride > 0 && pad >= 0, "pd_conv2d: bad filter geometry");
-    PD_REQUIRE(mode >= 0 && mode <= 2 && act >= 0 && act <= 3, "pd_conv2d: bad mode/act");
-    PD_REQUIRE(mode != MODE_REFLECT || (pad < H && pad < W), "pd_conv2d: reflect pad must be < input size");
-    PD_REQUIRE(ldy >= Co && ldy < (1L << 22), "pd_conv2d: bad output row stride %ld (Cout=%d)", ldy, Co);
-    int sshift = 0;
-    while ((1 << sshift) < stride) ++sshift;
-    if (mode == MODE_TRANSPOSED) {
-        PD_REQUIRE((1 << sshift) == stride, "pd_conv2d: transposed mode needs a power-of-two stride");
-        // (a SMALLER x grid is the leading part of that output grid: the missing rows / columns read as zero -- the
-        //  sub-filters of a phase-decomposed stride-2 data gradient need exactly that, see pd_dgrad_s2_filters)
-        PD_REQUIRE(H <= (Ho + 2 * pad - KH) / stride + 1 && W <= (Wo + 2 * pad_w - KW) / stride + 1,
-                   "pd_conv2d: transposed: x grid exceeds the forward output grid of a %dx%d input", Ho, Wo);
-    } else {
-        // a smaller output grid computes the leading Ho x Wo outputs only (asymmetric bottom/right padding)
-        PD_REQUIRE(Ho <= (H + 2 * pad - KH) / stride + 1 && Wo <= (W + 2 * pad_w - KW) / stride + 1,
-                   "pd_conv2d: output grid does not match input/filter geometry");
-    }
-    if (N == 0) return PD_OK;
-    ConvArgs a;
-    a.x = (const float*)x; a.w = (const float*)w; a.bias = (const float*)bias; a.oscale = (const float*)out_scale; a.y = (float*)y; a.stats = (float*)stats;
-    a.add = (const float*)addend; a.ld_add = ld_add;
-    a.N = N; a.H = H; a.W = W; a.C = C; a.sN = sN; a.sH = sH; a.sW = sW; a.sC = sC;
-    a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_w = pad_w;
-    a.mode = mode; a.act = act; a.affine = affine; a.sub = sub; a.div = div;
-    a.K = KH * KW * C; a.M = (long)N * Ho * Wo; a.ldy = ldy; a.sshift = sshift;
-    a.flags = flags; a.stats_rows = pd_conv2d_tile_m(a.M, Co);
-    auto magic = [](long d, unsigned& mg, unsigned& sh) {       // n / d == mulhi(n, mg) >> sh for 0 <= n < 2^31, d >= 2
-        if (d <= 1 || d >= (1L << 31)) { mg = 0; sh = 0; return; }
-        int l = 0;
-        while ((1L << l) < d) ++l;                                // ceil(log2 d) >= 1
-        mg = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned long long)d - 1) / (unsigned long long)d);
-        sh = (unsigned)(l - 1);
-    };
-    magic((long)Ho * Wo, a.mg_hw, a.sh_hw);
-    magic(Wo, a.mg_wo, a.sh_wo);
-    const long wbytes = (long)Co * a.K * 4;
-    PD_REQUIRE(wbytes < 0x7fffffffL, "pd_conv2d: weight tensor too large for 32-bit offsets");
-    a.w_bytes = (unsigned)wbytes;
-    // 32-bit byte offsets are relative to the first image of a tile: a tile (up to 256 rows) may span ceil(256/(Ho*Wo))+1 images
-    const long span = 256 / ((long)Ho * Wo) + 2;
-    PD_REQUIRE(span * sN * 4 < 0x7fffffffL, "pd_conv2d: image too large for 32-bit offsets (%ld bytes per image)", sN * 4);
-    const bool vec = (C % 4 == 0) && sC == 1 && (sW % 4 == 0) && (sH % 4 == 0) && (sN % 4 == 0) && !affine &&
-                     pd::aligned16(x) && pd::aligned16(w);
-    hipStream_t st = (hipStream_t)stream;
-    const int bm = pd_conv2d_tile_m(a.M, Co);
-    // 96 output columns (the data gradient of the decoder's 96 -> 32 layer): three 32-wide column tiles instead of a full and a
-    // half-empty 64-wide one (a quarter of the matrix work of that launch was padding)
-    // the halo-tile kernel (every activation element staged and split once per tile) where its tiling fits
-    if (x3_common_ok(a, vec) && !(flags & PD_CONV_X3_IM2COL) && x3_halo_eligible(a)) return launch_conv_x3_halo(a, st);
-    if (const int rb = x3_eligible(a, vec)) return launch_conv_x3(a, rb, st);
-    if (Co == 96 && bm == 128) return launch_conv<128, 32, 32, 32>(a, vec, st);
-    if (Co > 32) return bm == 128 ? launch_conv<128, 64, 64, 32>(a, vec, st) : launch_conv<64, 64, 32, 32>(a, vec, st);
-    if (Co > 16) return launch_conv<128, 32, 32, 32>(a, vec, st);
-    return launch_conv<128, 16, 32, 16>(a, vec, st);   // 16x16x4 MFMA tiles
 }
 
 // ===================================================================== weight gradient
@@ -2330,8 +2363,6 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_x3c_kernel(const WgradUniArg
             const u32x4 av = T == 0 ? fa[G][BLK][0] : T == 1 ? fa[G][BLK][1] : T == 2 ? fa[G][BLK][2] : T == 3 ? fa[G][BLK][0] : T == 4 ? fa[G][BLK][1] : fa[G][BLK][0];
             acc[BLK] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(av), bf(u32x4{bv[0], bv[1], bv[2], bv[3]}), acc[BLK], 0, 0, 0);
         };
-#define PD_I(n) std::integral_constant<int, n>{}
-#define PD_SB __builtin_amdgcn_sched_barrier(0);
         x3::sp_h<0>(x0, t0); x3::sp_h<1>(x0, t0); x3::sp_h<2>(x0, t0); x3::sp_h<3>(x0, t0);
         PD_SB
 #define PD_XP(j) if constexpr (SPREAD) load_x_piece(nxt, PD_I(j));
@@ -2366,8 +2397,6 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_x3c_kernel(const WgradUniArg
         *reinterpret_cast<u32x4*>(lds_c + sp_off + (NXT * P_BYTES + 0 * 4096u)) = u32x4{td.h[0], td.h[1], td.h[2], td.h[3]};
         *reinterpret_cast<u32x4*>(lds_c + sp_off + (NXT * P_BYTES + 1 * 4096u)) = u32x4{td.m[0], td.m[1], td.m[2], td.m[3]};
         *reinterpret_cast<u32x4*>(lds_c + sp_off + (NXT * P_BYTES + 2 * 4096u)) = u32x4{td.l[0], td.l[1], td.l[2], td.l[3]};
-#undef PD_SB
-#undef PD_I
         dma_wait();
         __syncthreads();
     };
@@ -2488,6 +2517,9 @@ inline int wgrad_tco(int Co) { return Co > 32 ? 64 : (Co > 16 ? 32 : 16); }
 
 // bf16-split weight gradient (conv_wgrad_x3c_kernel) unless the caller asks for the fp32 MFMA or for the in-register split
 inline bool wgrad_x3c_enabled(unsigned flags) { return !(flags & (PD_CONV_FP32_MFMA | PD_CONV_WGRAD_SPLIT_IN_REGS)); }
+// conv_wgrad_uni_kernel's X3 branch (both operands split in registers by every wave that needs them): 216 vector
+// instructions per 24 MFMAs, measured 8 % slower than the fp32 kernel -- kept for its test, reached by flag only
+inline bool wgrad_x3_on(unsigned flags) { return (flags & PD_CONV_WGRAD_SPLIT_IN_REGS) && !(flags & PD_CONV_FP32_MFMA); }
 
 void wgrad_plan(long M, int Co, int K, unsigned flags, int* S, long* mper) {
     const int tco = wgrad_tco(Co);
@@ -2513,6 +2545,106 @@ void wgrad_plan(long M, int Co, int K, unsigned flags, int* S, long* mper) {
     *S = (int)s; *mper = per;
 }
 
+// ---- routing: which kernel one weight gradient gets, and everything its launch needs.  route_wgrad is the ONLY place that
+// decides; pd_conv2d_wgrad launches from the route, and pd_conv2d_wgrad_uses_x3 / _uses_bf16 read the route of the dense tensors
+// they document with the workspace pd_conv2d_wgrad_workspace asks for.
+enum WgradFamily { WGRAD_GENERAL = 0, WGRAD_UNI, WGRAD_UNI_X3, WGRAD_X3C, WGRAD_HALO, WGRAD_ROLL };
+struct WgradRoute {
+    int family;             // general | scalar-pixel fp32 | scalar-pixel split in registers | x3c | halo-tile | rolling-row
+    int tco, S; long mper;  // the first four: output channels per workgroup, slices and pixels per slice (wgrad_plan)
+    bool vec, row8;         // general kernel: 16-byte gather; x3c: the lean walker
+    int nb, nbw;            // scalar-pixel kernels (x3c included): border rows / column pairs
+    int s_cap; bool bf16;   // halo-tile / rolling-row: partial rows the workspace may take; the one-term form (PD_CONV_BF16)
+    WgradRollPlan roll;     // rolling-row
+};
+
+static WgradRoute route_wgrad(const WgradArgs& a, bool vec, unsigned flags, size_t ws_bytes) {
+    WgradRoute r{};
+    r.vec = vec; r.tco = wgrad_tco(a.Co);
+    wgrad_plan(a.M, a.Co, a.K, flags, &r.S, &r.mper);
+    // every kernel but the general one: zero padding, or ReflectionPad2d(1) in front of a same-size 3x3
+    const bool refl_ok = a.mode == MODE_REFLECT && a.pad == 1 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.Ho == a.H && a.Wo == a.W && a.H >= 3;
+    if (!(a.mode == MODE_ZERO || refl_ok)) return r;
+    if (wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL)) && wgrad_halo_eligible(a, vec)) {
+        // halo-tile kernel (both operands split once per tile, transposed LDS reads): its slice count never exceeds what the
+        // workspace holds.  PD_CONV_BF16, the one-term forms: the slice count of the workspace the FLAGS ask for, whatever ws_bytes
+        // says -- a larger workspace must not change the summation order.
+        r.bf16 = (flags & PD_CONV_BF16) != 0;
+        const size_t per_slice = ((size_t)a.Co * a.K + a.Co) * sizeof(float);
+        r.s_cap = (int)std::min<size_t>((r.bf16 ? pd_conv2d_wgrad_workspace(a.M, a.Co, a.K, flags) : ws_bytes) / per_slice, 1 << 20);
+        // 3x3 with long tile columns: all three filter rows per workgroup, input rows rolling through LDS
+        r.family = !(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, vec, r.s_cap, r.roll) ? WGRAD_ROLL : WGRAD_HALO;
+        return r;
+    }
+    // scalar-pixel variant: 16-byte path, 64- or 32-wide co tile, even output rows (pixel pairs stay inside a row), border
+    // classes that fit the 31-bit mask
+    r.nb = (a.pad + a.stride - 1) / a.stride; r.nbw = (r.nb + 1) / 2;
+    if (!(flags & PD_CONV_GENERAL_KERNELS) && (r.tco == 64 || r.tco == 32) && vec && a.Co % 4 == 0 && a.Wo % 2 == 0 && a.ldd % 4 == 0 &&
+        a.Ho >= 2 * r.nb && a.Wo >= 4 * r.nbw && a.Wo >= 14 && (2 * r.nb + 1) * (2 * r.nbw + 1) <= 31 && r.mper % WG_MC == 0 &&
+        a.M % 4 == 0 && a.K >= 4) {
+        // 17..32 output channels (decoder 96->32, 64->32): the fp32 kernel; 64-wide: bf16-split products, every element split
+        // once (x3c), or by flag the in-register split / the fp32 MFMA
+        r.family = r.tco == 32 ? WGRAD_UNI : wgrad_x3c_enabled(flags) ? WGRAD_X3C : wgrad_x3_on(flags) ? WGRAD_UNI_X3 : WGRAD_UNI;
+        // The lean walker (one row class and one 32-pixel advance per chunk: 5 scalar instructions per MFMA instead of 8)
+        // whenever the eight pixels a wave stages cannot straddle an output row.  (Round 3 kept it off the large planes,
+        // where its four loads left back to back at the chunk head: 148 -> 134 TF on 5x5x64 @256x320; with the pieces
+        // threaded behind the chunk's first MFMAs it wins there too: 144 -> 155.)
+        r.row8 = a.Wo % 8 == 0 && r.mper % 8 == 0 && a.M % 8 == 0;
+    }
+    return r;
+}
+
+// general | scalar-pixel | x3c kernels: route -> template arguments
+static int launch_wgrad_slices(const WgradArgs& a, const WgradRoute& r, bool bias, hipStream_t st) {
+    const dim3 grid((unsigned)(((long)a.ktiles * a.ctiles * a.S + 7) / 8 * 8)), block(NT);
+    const bool reflect = a.mode == MODE_REFLECT;
+    if (r.family == WGRAD_GENERAL) {
+        const auto gen = [&](auto tco) { with_bool(r.vec, [&](auto v) { with_bool(reflect, [&](auto refl) {
+            hipLaunchKernelGGL((conv_wgrad_kernel<decltype(tco)::value, decltype(v)::value, decltype(refl)::value ? MODE_REFLECT : MODE_ZERO>), grid, block, 0, st, a);
+        }); }); };
+        if (r.tco == 64) gen(PD_I(64)); else if (r.tco == 32) gen(PD_I(32)); else gen(PD_I(16));
+        return PD_OK;
+    }
+    WgradUniArgs ua; ua.g = a; ua.nb = r.nb; ua.nbw = r.nbw;
+    if (r.family == WGRAD_X3C) {
+        static const hipError_t lds_ok = [] {
+            hipError_t e = hipSuccess;
+            for (const void* f : {reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<true, true>), reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<false, true>),
+                                  reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<true, false>), reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<false, false>),
+                                  reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<true, false, true>), reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<false, false, true>)}) {
+                const hipError_t rc = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, x3c::LDS_BYTES);
+                if (rc != hipSuccess) e = rc;
+            }
+            return e;
+        }();
+        PD_REQUIRE(lds_ok == hipSuccess, "pd_conv2d_wgrad: cannot reserve %u bytes of LDS", x3c::LDS_BYTES);
+        with_bool(bias, [&](auto b) {
+            constexpr bool B = decltype(b)::value;
+            if (reflect) hipLaunchKernelGGL((conv_wgrad_x3c_kernel<B, false, true>), grid, block, x3c::LDS_BYTES, st, ua);
+            else if (r.row8) hipLaunchKernelGGL((conv_wgrad_x3c_kernel<B, true>), grid, block, x3c::LDS_BYTES, st, ua);
+            else hipLaunchKernelGGL((conv_wgrad_x3c_kernel<B, false>), grid, block, x3c::LDS_BYTES, st, ua);
+        });
+    } else if (r.tco == 32) {       // (reflect + bias in this network)
+        with_bool(reflect, [&](auto refl) { hipLaunchKernelGGL((conv_wgrad_uni_kernel<decltype(refl)::value, true, 32>), grid, block, 0, st, ua); });
+    } else {
+        with_bool(reflect, [&](auto refl) { with_bool(bias, [&](auto b) {
+            constexpr bool R = decltype(refl)::value, B = decltype(b)::value;
+            if (r.family == WGRAD_UNI_X3) hipLaunchKernelGGL((conv_wgrad_uni_kernel<R, B, 64, true>), grid, block, 0, st, ua);
+            else hipLaunchKernelGGL((conv_wgrad_uni_kernel<R, B>), grid, block, 0, st, ua);
+        }); });
+    }
+    return PD_OK;
+}
+
+// Everything of WgradArgs but the tensor pointers and the slice plan (route_wgrad), from the arguments of pd_conv2d_wgrad
+static void fill_wgrad_args(WgradArgs& a, int N, int H, int W, int C, long sN, long sH, long sW, long sC, int Ho, int Wo, int Co,
+                            int KH, int KW, int stride, int pad, int mode, int affine, float sub, float div, long ldd) {
+    a.N = N; a.H = H; a.W = W; a.C = C; a.sN = sN; a.sH = sH; a.sW = sW; a.sC = sC;
+    a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.mode = mode;
+    a.affine = affine; a.sub = sub; a.div = div;
+    a.K = KH * KW * C; a.M = (long)N * Ho * Wo; a.ldd = ldd;
+}
+
 }  // namespace
 
 extern "C" size_t pd_conv2d_wgrad_workspace(long M, int Co, int K, unsigned flags) {
@@ -2527,36 +2659,17 @@ extern "C" size_t pd_conv2d_wgrad_workspace(long M, int Co, int K, unsigned flag
     return ((size_t)S * Co * K + (size_t)S * Co) * sizeof(float);
 }
 
-// conv_wgrad_uni_kernel's X3 branch (both operands split in registers by every wave that needs them): 216 vector
-// instructions per 24 MFMAs, measured 8 % slower than the fp32 kernel -- kept for its test, reached by flag only
-static bool wgrad_x3_on(unsigned flags) { return (flags & PD_CONV_WGRAD_SPLIT_IN_REGS) && !(flags & PD_CONV_FP32_MFMA); }
-
-// 1 when pd_conv2d_wgrad sends this zero-padded shape (16-byte aligned NHWC operands assumed) to conv_wgrad_x3c_kernel
+// The route of the tensors the queries document: dense, 16-byte aligned NHWC x and dy (ldd = Cout), the workspace of
+// pd_conv2d_wgrad_workspace -- M is the caller's, also where it is no whole number of images; an empty grid: the general kernel
 extern "C" int pd_conv2d_wgrad_uses_x3(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho,
                                        int Wo, unsigned flags) {
-    const bool refl_ok = mode == MODE_REFLECT && pad == 1 && KH == 3 && KW == 3 && stride == 1 && Ho == H && Wo == W && H >= 3;
-    if (!(mode == MODE_ZERO || refl_ok)) return 0;
-    const bool uni_on = !(flags & PD_CONV_GENERAL_KERNELS);
-    int S = 0; long mper = 0;
-    wgrad_plan(M, Co, KH * KW * C, flags, &S, &mper);
-    const int nb = (pad + stride - 1) / stride, nbw = (nb + 1) / 2;
-    const bool x3c = uni_on && wgrad_x3c_enabled(flags) && wgrad_tco(Co) == 64 && C % 4 == 0 && Co % 4 == 0 && Wo % 2 == 0 && Ho >= 2 * nb &&
-           Wo >= 4 * nbw && Wo >= 14 && (2 * nb + 1) * (2 * nbw + 1) <= 31 && mper % WG_MC == 0 && M % 4 == 0 && KH * KW * C >= 4;
-    if (wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL)) && C % 4 == 0) {
-        // 2: the halo-tile kernel (both operands split once per tile, transposed LDS reads) -- the same test as pd_conv2d_wgrad's
-        WgradArgs a{};
-        a.mode = mode; a.stride = stride; a.KH = KH; a.KW = KW; a.pad = pad; a.C = C; a.Co = Co; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-        a.ldd = Co; a.sN = (long)H * W * C;
-        if (wgrad_halo_eligible(a, true)) {
-            // 3: the rolling-row kernel (all three filter rows per workgroup) -- with the workspace pd_conv2d_wgrad_workspace asks for
-            a.N = (int)(M / ((long)Ho * Wo)); a.M = M; a.K = KH * KW * C;
-            const size_t per_slice = ((size_t)Co * a.K + Co) * sizeof(float);
-            const int s_cap = (int)std::min<size_t>(pd_conv2d_wgrad_workspace(M, Co, a.K, flags) / per_slice, 1 << 20);
-            WgradRollPlan rp;
-            return !(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, true, s_cap, rp) ? 3 : 2;
-        }
-    }
-    return x3c;
+    if (Ho <= 0 || Wo <= 0) return 0;
+    WgradArgs a{};
+    fill_wgrad_args(a, (int)(M / ((long)Ho * Wo)), H, W, C, (long)H * W * C, (long)W * C, C, 1, Ho, Wo, Co, KH, KW, stride, pad, mode,
+                    0, 0.f, 1.f, Co);
+    a.M = M;
+    const int family = route_wgrad(a, vec16_ok(a.x, C, a.sN, a.sH, a.sW, a.sC, a.affine), flags, pd_conv2d_wgrad_workspace(M, Co, a.K, flags)).family;
+    return family == WGRAD_ROLL ? 3 : family == WGRAD_HALO ? 2 : family == WGRAD_X3C ? 1 : 0;
 }
 
 // PD_CONV_BF16: the one-term forms of the halo-tile / rolling-row kernels, with the slice count of the workspace the flags ask
@@ -2581,119 +2694,28 @@ extern "C" int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* db
     if (N == 0) return PD_OK;
     WgradArgs a;
     a.x = (const float*)x; a.dy = (const float*)dy;
-    a.N = N; a.H = H; a.W = W; a.C = C; a.sN = sN; a.sH = sH; a.sW = sW; a.sC = sC;
-    a.Ho = Ho; a.Wo = Wo; a.Co = Co; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.mode = mode;
-    a.affine = affine; a.sub = sub; a.div = div;
-    a.K = KH * KW * C; a.M = (long)N * Ho * Wo; a.ldd = ldd;
-    wgrad_plan(a.M, Co, a.K, flags, &a.S, &a.mper);
+    fill_wgrad_args(a, N, H, W, C, sN, sH, sW, sC, Ho, Wo, Co, KH, KW, stride, pad, mode, affine, sub, div, ldd);
     const size_t need = pd_conv2d_wgrad_workspace(a.M, Co, a.K, flags);
     PD_REQUIRE(ws_bytes >= need, "pd_conv2d_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
-    a.part = (float*)workspace;
-    a.bpart = dbias ? a.part + (size_t)a.S * Co * a.K : nullptr;
-    const int tco = wgrad_tco(Co);
-    a.ktiles = (a.K + WG_K - 1) / WG_K; a.ctiles = (Co + tco - 1) / tco;
-    const bool vec = (C % 4 == 0) && sC == 1 && (sW % 4 == 0) && (sH % 4 == 0) && (sN % 4 == 0) && !affine &&
-                     pd::aligned16(x);
     PD_REQUIRE(pd::aligned16(dy) && (ldd % 4 == 0 || Co < 4), "pd_conv2d_wgrad: dy must be 16-byte aligned rows");
+    const WgradRoute r = route_wgrad(a, vec16_ok(x, C, sN, sH, sW, sC, affine), flags, ws_bytes);
+    a.S = r.S; a.mper = r.mper;
     PD_REQUIRE(a.mper * ldd * 4 < 0x7fffffffL, "pd_conv2d_wgrad: slice too large for 32-bit offsets");
     PD_REQUIRE((a.mper / ((long)Ho * Wo) + 2) * sN * 4 < 0x7fffffffL, "pd_conv2d_wgrad: image too large for 32-bit offsets");
+    a.part = (float*)workspace;
+    a.bpart = dbias ? a.part + (size_t)a.S * Co * a.K : nullptr;
+    a.ktiles = (a.K + WG_K - 1) / WG_K; a.ctiles = (Co + r.tco - 1) / r.tco;
     hipStream_t st = (hipStream_t)stream;
-    if (wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL)) && wgrad_halo_eligible(a, vec)) {
-        // halo-tile kernel: its slice count never exceeds what the workspace holds
-        // (PD_CONV_BF16, the one-term forms: the slice count of the workspace the flags ask for, whatever ws_bytes says)
-        const bool bf16 = (flags & PD_CONV_BF16) != 0;
-        const size_t per_slice = ((size_t)Co * a.K + Co) * sizeof(float);
-        const int s_cap = (int)std::min<size_t>((bf16 ? need : ws_bytes) / per_slice, 1 << 20);
-        WgradRollPlan rp;
-        // 3x3 with long tile columns: all three filter rows per workgroup, input rows rolling through LDS
-        const int S = !(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, vec, s_cap, rp) ? launch_wgrad_roll(a, rp, st, dbias != nullptr, bf16)
-                                                                                             : launch_wgrad_halo(a, s_cap, st, dbias != nullptr, bf16);
-        a.bpart = dbias ? a.part + (size_t)S * Co * a.K : nullptr;
-        int rc = pd::check_launch("pd_conv2d_wgrad");
-        if (rc) return rc;
-        const long nw = (long)Co * a.K;
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(256), 0, st, a.part, (float*)dw, S, nw, accumulate);
-        if (dbias)
-            hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(256), 0, st, a.bpart, (float*)dbias, S, (long)Co, accumulate);
-        return pd::check_launch("pd_conv2d_wgrad/reduce");
-    }
-    const dim3 grid((unsigned)(((long)a.ktiles * a.ctiles * a.S + 7) / 8 * 8)), block(NT);
-#define PD_WG(T, V, MD) hipLaunchKernelGGL((conv_wgrad_kernel<T, V, MD>), grid, block, 0, st, a)
-    // scalar-pixel variant: 16-byte path, zero padding, 64-wide co tile, even output rows (pixel pairs stay inside a
-    // row), border classes that fit the 31-bit mask
-    const bool uni_on = !(flags & PD_CONV_GENERAL_KERNELS);
-    const int nb = (pad + stride - 1) / stride, nbw = (nb + 1) / 2;
-    const bool refl_ok = mode == MODE_REFLECT && pad == 1 && KH == 3 && KW == 3 && stride == 1 && Ho == H && Wo == W && H >= 3;
-    if (uni_on && (tco == 64 || tco == 32) && vec && (mode == MODE_ZERO || refl_ok) && Co % 4 == 0 && Wo % 2 == 0 && ldd % 4 == 0 &&
-        Ho >= 2 * nb && Wo >= 4 * nbw && Wo >= 14 && (2 * nb + 1) * (2 * nbw + 1) <= 31 && a.mper % WG_MC == 0 &&
-        a.M % 4 == 0 && a.K >= 4) {
-        WgradUniArgs ua; ua.g = a; ua.nb = nb; ua.nbw = nbw;
-        if (tco == 32) {              // 17..32 output channels (decoder 96->32, 64->32): reflect + bias in this network
-            if (mode == MODE_ZERO) hipLaunchKernelGGL((conv_wgrad_uni_kernel<false, true, 32>), grid, block, 0, st, ua);
-            else hipLaunchKernelGGL((conv_wgrad_uni_kernel<true, true, 32>), grid, block, 0, st, ua);
-        } else if (wgrad_x3c_enabled(flags)) {   // bf16-split products, every element split once (zero or reflection padding)
-            static const hipError_t lds_ok = [] {
-                hipError_t e = hipSuccess;
-                for (const void* f : {reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<true, true>), reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<false, true>),
-                                      reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<true, false>), reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<false, false>),
-                                      reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<true, false, true>),
-                                      reinterpret_cast<const void*>(conv_wgrad_x3c_kernel<false, false, true>)}) {
-                    const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, x3c::LDS_BYTES);
-                    if (r != hipSuccess) e = r;
-                }
-                return e;
-            }();
-            PD_REQUIRE(lds_ok == hipSuccess, "pd_conv2d_wgrad: cannot reserve %u bytes of LDS", x3c::LDS_BYTES);
-            // The lean walker (one row class and one 32-pixel advance per chunk: 5 scalar instructions per MFMA instead of 8)
-            // whenever the eight pixels a wave stages cannot straddle an output row.  (Round 3 kept it off the large planes,
-            // where its four loads left back to back at the chunk head: 148 -> 134 TF on 5x5x64 @256x320; with the pieces
-            // threaded behind the chunk's first MFMAs it wins there too: 144 -> 155.)
-            const bool row8 = Wo % 8 == 0 && a.mper % 8 == 0 && a.M % 8 == 0;
-            if (mode == MODE_REFLECT) {
-                if (dbias) hipLaunchKernelGGL((conv_wgrad_x3c_kernel<true, false, true>), grid, block, x3c::LDS_BYTES, st, ua);
-                else hipLaunchKernelGGL((conv_wgrad_x3c_kernel<false, false, true>), grid, block, x3c::LDS_BYTES, st, ua);
-            } else if (row8) {
-                if (dbias) hipLaunchKernelGGL((conv_wgrad_x3c_kernel<true, true>), grid, block, x3c::LDS_BYTES, st, ua);
-                else hipLaunchKernelGGL((conv_wgrad_x3c_kernel<false, true>), grid, block, x3c::LDS_BYTES, st, ua);
-            } else {
-                if (dbias) hipLaunchKernelGGL((conv_wgrad_x3c_kernel<true, false>), grid, block, x3c::LDS_BYTES, st, ua);
-                else hipLaunchKernelGGL((conv_wgrad_x3c_kernel<false, false>), grid, block, x3c::LDS_BYTES, st, ua);
-            }
-        } else if (wgrad_x3_on(flags)) {     // products on the bf16 matrix cores (three-way split, fp32 accuracy)
-            if (mode == MODE_ZERO) {
-                if (dbias) hipLaunchKernelGGL((conv_wgrad_uni_kernel<false, true, 64, true>), grid, block, 0, st, ua);
-                else hipLaunchKernelGGL((conv_wgrad_uni_kernel<false, false, 64, true>), grid, block, 0, st, ua);
-            } else {
-                if (dbias) hipLaunchKernelGGL((conv_wgrad_uni_kernel<true, true, 64, true>), grid, block, 0, st, ua);
-                else hipLaunchKernelGGL((conv_wgrad_uni_kernel<true, false, 64, true>), grid, block, 0, st, ua);
-            }
-        } else if (mode == MODE_ZERO) {
-            if (dbias) hipLaunchKernelGGL((conv_wgrad_uni_kernel<false, true>), grid, block, 0, st, ua);
-            else hipLaunchKernelGGL((conv_wgrad_uni_kernel<false, false>), grid, block, 0, st, ua);
-        } else {
-            if (dbias) hipLaunchKernelGGL((conv_wgrad_uni_kernel<true, true>), grid, block, 0, st, ua);
-            else hipLaunchKernelGGL((conv_wgrad_uni_kernel<true, false>), grid, block, 0, st, ua);
-        }
-    } else
-    if (tco == 64) {
-        if (vec) { if (mode == MODE_ZERO) PD_WG(64, true, MODE_ZERO); else PD_WG(64, true, MODE_REFLECT); }
-        else { if (mode == MODE_ZERO) PD_WG(64, false, MODE_ZERO); else PD_WG(64, false, MODE_REFLECT); }
-    } else if (tco == 32) {
-        if (vec) { if (mode == MODE_ZERO) PD_WG(32, true, MODE_ZERO); else PD_WG(32, true, MODE_REFLECT); }
-        else { if (mode == MODE_ZERO) PD_WG(32, false, MODE_ZERO); else PD_WG(32, false, MODE_REFLECT); }
-    } else {
-        if (vec) { if (mode == MODE_ZERO) PD_WG(16, true, MODE_ZERO); else PD_WG(16, true, MODE_REFLECT); }
-        else { if (mode == MODE_ZERO) PD_WG(16, false, MODE_ZERO); else PD_WG(16, false, MODE_REFLECT); }
-    }
-#undef PD_WG
-    int rc = pd::check_launch("pd_conv2d_wgrad");
-    if (rc) return rc;
+    int S = a.S;       // partial rows written: the halo-tile / rolling-row kernels cut their own slices
+    if (r.family == WGRAD_ROLL) S = launch_wgrad_roll(a, r.roll, st, dbias != nullptr, r.bf16);
+    else if (r.family == WGRAD_HALO) S = launch_wgrad_halo(a, r.s_cap, st, dbias != nullptr, r.bf16);
+    else if (int rc = launch_wgrad_slices(a, r, dbias != nullptr, st)) return rc;
+    a.bpart = dbias ? a.part + (size_t)S * Co * a.K : nullptr;
+    if (int rc = pd::check_launch("pd_conv2d_wgrad")) return rc;
     const long nw = (long)Co * a.K;
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(256), 0, st,
-                       a.part, (float*)dw, a.S, nw, accumulate);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(256), 0, st, a.part, (float*)dw, S, nw, accumulate);
     if (dbias)
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(256), 0, st,
-                           a.bpart, (float*)dbias, a.S, (long)Co, accumulate);
+        hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(256), 0, st, a.bpart, (float*)dbias, S, (long)Co, accumulate);
     return pd::check_launch("pd_conv2d_wgrad/reduce");
 }
 

@@ -192,7 +192,6 @@ __global__ __launch_bounds__(NT, KS == 3 ? 3 : 2) void conv_wgrad_halo_x3_kernel
         for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
     auto bf = [](uint2 lo, uint2 hi) { return __builtin_bit_cast(x3::bf16x8, u32x4{lo.x, lo.y, hi.x, hi.y}); };
 
-#define PD_I(n) std::integral_constant<int, n>{}
 #define PD_U(n) std::integral_constant<unsigned, n>{}
     // ---- prologue: tile t_beg -> planes 0, tile t_beg + 1 -> registers
     tile_begin();
@@ -268,7 +267,6 @@ __global__ __launch_bounds__(NT, KS == 3 ? 3 : 2) void conv_wgrad_halo_x3_kernel
         tile(PD_U(0));
         if (t + 1 < t_end) tile(PD_U(1));
     }
-#undef PD_I
 #undef PD_U
 
     // ---- partial tile of this slice: C/D layout col = lane % 32 -> ci, row -> co: (r&3) + 8*(r>>2) + 4*(lane>>5)
@@ -355,11 +353,9 @@ static int launch_wgrad_halo(WgradArgs a, int s_cap, hipStream_t st, bool bias, 
     ha.g = a;
     const long nwg = (long)per_slice_wgs * S;
     const dim3 grid((unsigned)((nwg + 7) / 8 * 8)), block(NT);
-#define PD_WGH(KSV, TWV, C32) do { \
-        if (bf16) { if (bias) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, true, C32, 1>), grid, block, 0, st, ha); \
-                    else hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, false, C32, 1>), grid, block, 0, st, ha); } \
-        else if (bias) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, true, C32>), grid, block, 0, st, ha); \
-        else hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, false, C32>), grid, block, 0, st, ha); } while (0)
+#define PD_WGH(KSV, TWV, C32) with_bool(bias, [&](auto b) { \
+        if (bf16) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, decltype(b)::value, C32, 1>), grid, block, 0, st, ha); \
+        else hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, decltype(b)::value, C32>), grid, block, 0, st, ha); })
     if (co32) PD_WGH(3, 32, true);
     else if (a.KH == 3) { if (tw == 32) PD_WGH(3, 32, false); else if (tw == 16) PD_WGH(3, 16, false); else if (tw == 8) PD_WGH(3, 8, false); else PD_WGH(3, 4, false); }
     else { if (tw == 32) PD_WGH(5, 32, false); else if (tw == 16) PD_WGH(5, 16, false); else PD_WGH(5, 8, false); }

@@ -289,11 +289,9 @@ static int launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st
     ra.g = a;
     const long nwg = (long)ra.ncb * a.ctiles * p.S;
     const dim3 grid((unsigned)((nwg + 7) / 8 * 8)), block(NT);
-#define PD_WGR(TWV) do { \
-        if (bf16) { if (bias) hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, true, 1>), grid, block, 0, st, ra); \
-                    else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, false, 1>), grid, block, 0, st, ra); } \
-        else if (bias) hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, true>), grid, block, 0, st, ra); \
-        else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, false>), grid, block, 0, st, ra); } while (0)
+#define PD_WGR(TWV) with_bool(bias, [&](auto b) { \
+        if (bf16) hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, decltype(b)::value, 1>), grid, block, 0, st, ra); \
+        else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, decltype(b)::value>), grid, block, 0, st, ra); })
     if (p.tw == 32) PD_WGR(32); else PD_WGR(16);
 #undef PD_WGR
     return p.S;

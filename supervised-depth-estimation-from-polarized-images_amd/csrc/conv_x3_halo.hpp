@@ -237,9 +237,7 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
         }
     };
     auto halo_split = [&]() {                                    // prologue: all items at once
-#define PD_I(n) std::integral_constant<int, n>{}
         halo_item(PD_I(0)); halo_item(PD_I(1)); halo_item(PD_I(2)); halo_item(PD_I(3)); halo_item(PD_I(4)); halo_item(PD_I(5)); halo_item(PD_I(6));
-#undef PD_I
     };
 
     // scalar tap state of the chunk being multiplied
@@ -292,9 +290,7 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
                 *reinterpret_cast<unsigned*>(lds_c + sp_off + NXT * BP_BYTES) = h ^ wsign;
             }
             if (LAST) {
-#define PD_I(n) std::integral_constant<int, n>{}
                 halo_item(PD_I(0)); halo_item(PD_I(1)); halo_item(PD_I(2)); halo_item(PD_I(3)); halo_item(PD_I(4)); halo_item(PD_I(5)); halo_item(PD_I(6));
-#undef PD_I
             }
             static_assert(NI <= 7, "halo items per thread");
             if (++s_kw == KW) { s_kw = 0; if (++s_kh == KH) { s_kh = 0; ++s_g; } }
@@ -319,8 +315,6 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
             constexpr int TA = TT < 2 ? 0 : TT == 2 ? 2 : TT < 5 ? 1 : 0, TB = TT == 0 ? 0 : TT == 1 ? 1 : TT == 2 ? 0 : TT == 3 ? 0 : TT == 4 ? 1 : 2;
             acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf(av[I][TA]), bf(fb[J][TB]), acc[I][J], 0, 0, 0);
         };
-#define PD_I(n) std::integral_constant<int, n>{}
-#define PD_SB __builtin_amdgcn_sched_barrier(0);
         if constexpr (NCB == 2) {
         PD_SB
         mm(PD_I(0), PD_I(0)); x3::sp_h<0, true>(ws, tw); PD_SB
@@ -367,8 +361,6 @@ __global__ __launch_bounds__(NT, 3) void conv_halo_x3_kernel(const ConvArgs a) {
         mm(PD_I(1), PD_I(5)); if (LAST) halo_item(PD_I(6));
         }
         static_assert(NI <= 7, "halo items per thread");
-#undef PD_SB
-#undef PD_I
         if (++s_kw == KW) { s_kw = 0; if (++s_kh == KH) { s_kh = 0; ++s_g; } }
         __syncthreads();                            // the next chunk's weight planes (and, behind LAST, the next halo) are written
     };
@@ -504,19 +496,12 @@ static bool x3_halo_plan(const ConvArgs& a, HaloPlan& p) {
     // 146 vs 150: not taken)
     return p.ncb == 2 || (a.KH == 3 && p.tw != 8) || (a.KH == 5 && p.tw == 8);
 }
-static bool x3_halo_eligible(const ConvArgs& a) { HaloPlan p; return x3_halo_plan(a, p); }
 
-// TERMS = 1: the single-bf16 form (PD_CONV_BF16)
+// TERMS = 1: the single-bf16 form (PD_CONV_BF16).  The plan is route_conv's; a.mtiles / a.ntiles / a.nmajor and the grid are set.
 template <int TERMS>
-static int launch_conv_x3_halo_t(ConvArgs& a, hipStream_t st) {
-    HaloPlan p;
-    if (!x3_halo_plan(a, p)) return pd::fail(PD_EINVAL, "pd_conv2d: internal: halo plan");
+static void launch_conv_x3_halo(const ConvArgs& a, const HaloPlan& p, dim3 grid, hipStream_t st) {
     const int tw = p.tw;
-    a.mtiles = a.N * (a.Ho / (256 / tw)) * (a.Wo / tw);
-    a.ntiles = a.Co / (32 * p.ncb);
-    a.nmajor = x3_nmajor(a);
-    const long nblk = (long)a.mtiles * a.ntiles;
-    const dim3 grid((unsigned)((nblk + 7) / 8 * 8)), block(NT);
+    const dim3 block(NT);
     // Occupancy history (round 4, same box): a three-chunk LDS-DMA weight ring at two workgroups per CU -> a two-chunk ring at
     // three (3x3 only: 53 KB, 166 registers; 3x3x64 @256x320 forward 154 -> 185 TF, data gradient 185 -> 200) -> weights staged
     // through registers, no ring: 45 KB / 52.5 KB, three workgroups per CU for 5x5 as well.
@@ -531,8 +516,4 @@ static int launch_conv_x3_halo_t(ConvArgs& a, hipStream_t st) {
     else if (a.KH == 3) { if (tw == 32) PD_HALO(3, 3, 32, 2, false); else if (tw == 16) PD_HALO(3, 3, 16, 2, false); else PD_HALO(3, 3, 8, 2, false); }
     else { if (tw == 32) PD_HALO(5, 5, 32, 2, false); else if (tw == 16) PD_HALO(5, 5, 16, 2, false); else PD_HALO(5, 5, 8, 2, false); }
 #undef PD_HALO
-    return pd::check_launch("pd_conv2d");
-}
-static int launch_conv_x3_halo(ConvArgs& a, hipStream_t st) {
-    return (a.flags & PD_CONV_BF16) ? launch_conv_x3_halo_t<1>(a, st) : launch_conv_x3_halo_t<3>(a, st);
 }

@@ -83,25 +83,19 @@ def _profiled(label, flops, fn, shape=None):
     return r
 
 
+# pd_conv2d_route's family code -> profiler label (the bf16-split kernels' labels name their default tile)
+_IGEMM_LABELS = ("conv_igemm_kernel<{bm},{bn},{gather}>", "conv_igemm_uni_kernel<{bm},{bn}>", "conv_igemm_x3_kernel<{bm},{bn}>",
+                 "conv_halo_x3_kernel<8x32,64>", "conv_halo_bf16_kernel<8x32,64>")
+
+
 def _igemm_label(M, Co, vec, kind, C=0, KH=1, KW=1, stride=1, pad=0, mode=0, act=ACT_NONE, out_scale=False, out_hw=(0, 0),
                  flags=None):
-    """Profiler label = the kernel family pd_conv2d launches for this call (same rule as launch_conv in conv.hip)."""
+    """Profiler label = the kernel pd_conv2d launches for this call, as the library's own routing answers (pd_conv2d_route)."""
     flags = CONV_FLAGS if flags is None else flags
-    if vec and lib.pd_conv2d_uses_bf16(M, Co, C, KH, KW, stride, pad, mode, act, int(out_scale), out_hw[0], out_hw[1], flags):
-        return "conv_halo_bf16_kernel<8x32,64>"
-    flags &= ~CONV_BF16
-    rb = lib.pd_conv2d_uses_x3(M, Co, C, KH, KW, stride, pad, mode, act, int(out_scale), out_hw[0], out_hw[1], flags) if vec else 0
-    if rb == 3:
-        return "conv_halo_x3_kernel<8x32,64>"
-    if rb:
-        return f"conv_igemm_x3_kernel<{128 * rb},64>"
-    bm = lib.pd_conv2d_tile_m(M, Co)
-    bn = 64 if Co > 32 else (32 if Co > 16 else 16)
-    uni = (vec and not (flags & CONV_GENERAL_KERNELS) and bn >= 32 and C % 32 == 0 and C > 0 and KH * KW <= 31 and pad < KH and pad < KW and
-           (mode in (MODE_ZERO, MODE_REFLECT) or (mode == MODE_TRANSPOSED and stride == 1)))
-    if uni:
-        return f"conv_igemm_uni_kernel<{bm},{bn}>"
-    return f"conv_igemm_kernel<{bm},{bn},{'vec' if vec else 'scalar'}>"
+    if not vec:     # an input the 16-byte path cannot read (strided channels, affine taps): the general kernel's scalar gather
+        flags = CONV_FP32_MFMA | CONV_GENERAL_KERNELS
+    r = lib.pd_conv2d_route(M, Co, C, KH, KW, stride, pad, mode, act, int(out_scale), out_hw[0], out_hw[1], flags)
+    return _IGEMM_LABELS[r & 15].format(bm=r >> 12, bn=(r >> 4) & 255, gather="vec" if vec else "scalar")
 
 
 def _require_cuda(*ts):

@@ -165,7 +165,10 @@ def test_production_tile_reflection_padded_conv(case, x3, monkeypatch):
         return y
     y, lab = _labels(run)
     # (forward on the REFLECT instantiation; the pad-1 data gradient is a zero-padding launch: fp32 or bf16-split kernel)
-    assert sum(l.startswith(("conv_igemm_uni_kernel<128,64>", "conv_igemm_x3_kernel", "conv_halo_x3_kernel")) for l in lab) == 2 and (({"conv_wgrad_x3c_kernel", "conv_wgrad_halo_x3_kernel", "conv_wgrad_roll_x3_kernel"} & set(lab)) if x3 == "1" else "conv_wgrad_kernel" in lab), lab
+    # (96 input channels on the fp32 MFMA: the data gradient's 96 output columns run as three 32-wide column tiles, and the label says so)
+    n32 = sum(l.startswith("conv_igemm_uni_kernel<128,32>") for l in lab)
+    assert n32 == (1 if C == 96 and x3 == "0" else 0), lab
+    assert sum(l.startswith(("conv_igemm_uni_kernel<128,64>", "conv_igemm_x3_kernel", "conv_halo_x3_kernel")) for l in lab) + n32 == 2 and (({"conv_wgrad_x3c_kernel", "conv_wgrad_halo_x3_kernel", "conv_wgrad_roll_x3_kernel"} & set(lab)) if x3 == "1" else "conv_wgrad_kernel" in lab), lab
     _close(y.detach().cpu(), ref.detach(), 3e-5, "fwd")
     _close(xc.grad.cpu(), xr.grad, 3e-5, "dgrad")
     _close(conv.weight.grad.cpu(), wr.grad, 3e-5, "wgrad")

@@ -190,6 +190,55 @@ def test_shape_validation_of_the_fused_kernels_needs_no_gpu():
                        8, 0, None) == -22 and b"row stride" in L.pd_last_error()
 
 
+def test_bf16_attention_entry_points_refuse_bad_arguments_without_a_gpu():
+    """pd_attn_bf16_fwd / _bwd / _bwd_parts return PD_EINVAL (-22) with their message before anything touches the device, and
+    pd_attn_bf16_workspace is N T 128 2 {2 forward, 7 backward} bytes of tile images (+ N T 8 of row statistics backward)."""
+    L = _lib.lib
+    err = L.pd_last_error
+    p = ctypes.c_void_p(64)      # a non-null, 16-byte aligned dummy: never dereferenced on these paths
+    odd = ctypes.c_void_p(72)    # 8-byte aligned only
+    N, T = 2, 96
+    for n, t in ((1, 32), (2, 96), (3, 640), (1026, 128)):
+        assert L.pd_attn_bf16_workspace(n, t, 128, 0) == n * t * 128 * 2 * 2
+        assert L.pd_attn_bf16_workspace(n, t, 128, 1) == n * t * 128 * 2 * 7 + n * t * 8
+    for bad in ((0, 96, 128), (-1, 96, 128), (2, 0, 128), (2, 100, 128), (2, 96, 64), (2, 96, 256)):
+        assert L.pd_attn_bf16_workspace(*bad, 0) == 0 and L.pd_attn_bf16_workspace(*bad, 1) == 0
+    wf, wb = L.pd_attn_bf16_workspace(N, T, 128, 0), L.pd_attn_bf16_workspace(N, T, 128, 1)
+
+    def fwd(q=p, k=p, v=p, o=p, lse=p, ws=p, wbytes=wf, N=N, T=T, C=128):
+        return L.pd_attn_bf16_fwd(q, k, v, o, lse, ws, wbytes, N, T, C, 0.1, None)
+
+    def bwd(parts=None, q=p, k=p, v=p, o=p, do=p, lse=p, delta=p, dq=p, dk=p, dv=p, ws=p, wbytes=wb, N=N, T=T, C=128):
+        a = (q, k, v, o, do, lse, delta, dq, dk, dv, ws, wbytes, N, T, C, 0.1)
+        return L.pd_attn_bf16_bwd(*a, None) if parts is None else L.pd_attn_bf16_bwd_parts(*a, parts, None)
+
+    assert fwd(C=64) == -22 and b"pd_attn_bf16_fwd: head dimension must be 128 (got 64)" in err()
+    assert fwd(T=100) == -22 and b"pd_attn_bf16_fwd: the token count must be a multiple of 32 (got 100)" in err()
+    assert fwd(T=0) == -22 and b"bad shape" in err()
+    assert fwd(N=-1) == -22 and b"bad shape" in err()
+    for name in ("q", "k", "v", "o", "lse", "ws"):
+        assert fwd(**{name: None}) == -22 and b"pd_attn_bf16_fwd: null tensor" in err(), name
+    assert fwd(wbytes=wf - 1) == -22 and b"pd_attn_bf16_fwd: workspace too small" in err()
+    for name in ("q", "k", "v", "o", "ws"):
+        assert fwd(**{name: odd}) == -22 and b"pd_attn_bf16_fwd: tensors must be 16-byte aligned" in err(), name
+    assert fwd(q=None, k=None, v=None, o=None, lse=None, ws=None, wbytes=0, N=0) == 0            # empty batch
+
+    for parts in (None, 7, 1, 2, 4):
+        assert bwd(parts, C=64) == -22 and b"pd_attn_bf16_bwd: head dimension must be 128 (got 64)" in err()
+        assert bwd(parts, T=100) == -22 and b"pd_attn_bf16_bwd: the token count must be a multiple of 32 (got 100)" in err()
+        assert bwd(parts, T=0) == -22 and b"bad shape" in err()
+        for name in ("q", "k", "v", "o", "do", "lse", "delta", "dq", "dk", "dv", "ws"):
+            assert bwd(parts, **{name: None}) == -22 and b"pd_attn_bf16_bwd: null tensor" in err(), name
+        assert bwd(parts, wbytes=wb - 1) == -22 and b"pd_attn_bf16_bwd: workspace too small" in err()
+        assert bwd(parts, wbytes=wf) == -22 and b"workspace too small" in err()                  # the forward size is not enough
+        for name in ("q", "k", "v", "o", "do", "dq", "dk", "dv", "ws"):
+            assert bwd(parts, **{name: odd}) == -22 and b"pd_attn_bf16_bwd: tensors must be 16-byte aligned" in err(), name
+        assert bwd(parts, N=0) == 0
+    for parts in (0, 8, -1):
+        assert bwd(parts) == -22 and b"pd_attn_bf16_bwd_parts: parts must be a combination of 1 | 2 | 4" in err()
+        assert bwd(parts, N=0) == -22                                                           # refused before the empty batch returns
+
+
 def test_shape_validation_of_the_glue_kernels_needs_no_gpu():
     """The K3 refusals (csrc/elementwise.hip) that are decided before any launch return PD_EINVAL (-22) with their message,
     and pd_chain_bwd_rows is the documented min(1024, ceil(quads / 256))."""

@@ -542,6 +542,22 @@ int pd_softmax_rows_bwd(const void* p, void* dp, long R, long L, float scale, vo
 int pd_resize_u8_pass(const void* src, void* dst, const void* coeffs, const void* bounds, int ksize, int P, int Hs,
                       int Ws, int out_size, int vertical, void* stream);
 
+/* ---- torchvision 0.8.2's PIL ColorJitter on uint8 planar RGB, Pillow-exact, fused with the loader's uint8 -> fp32 / 255
+ * (indoor_dataset.py:92-106, 192-233, 404-407; csrc/color.hip, arithmetic in csrc/color_math.hpp).
+ * src [B][3][H][W] uint8 (what pd_resize_u8_pass leaves for a [B,3,.,.] input), any H, W >= 1.
+ * dst_u8 [B][3][H][W] uint8 and dst_f32 [B][3][H][W] fp32 = (float)u / 255.0f: either may be NULL, not both.
+ * params: device double [B][8] = (code, value) x 4, applied in that order; code 0 none, 1 brightness, 2 contrast,
+ *   3 saturation, 4 hue, anything else 0.  The codes are read on the device (a captured step replays with new rows).
+ *   A row holds each operation at most once, as ColorJitter's do: a second contrast in a row behaves as code 0.
+ *   NULL = identity for every sample (the plain conversion): one launch, sum_ws is not read.
+ * sum_ws: 16 bytes per sample, 8-byte aligned, caller-owned: {uint64 sum of L, uint32 arrival ticket, int32 mean}.
+ *   The sum and ticket words must be ZERO on entry and are left zero by the call (a buffer zeroed once serves every
+ *   later call on the same stream, like acc_ws of pd_bn_fwd_finalize); the mean word is scratch.  The contrast
+ *   degenerate int(sum L / (H W) + 0.5) comes from integer partials and integer atomics: exact, independent of order.
+ * At most two launches (reduce, apply), no allocation, no host synchronisation. */
+int pd_color_jitter_u8(const void* src, const void* params, void* dst_u8, void* dst_f32, void* sum_ws, int B, int H,
+                       int W, void* stream);
+
 /* ---- fused attention (flash-attention recurrence on the fp32 matrix cores).
  * q, k, v, o, do, dq, dk, dv: [N][T][128] fp32 (token-major = NHWC), lse / delta: [N][T] fp32; T % 32 == 0.
  * pd_attn_fwd:  o = softmax(q k^T * scale) v,  lse = log sum exp of the scaled scores (saved for the backward). */

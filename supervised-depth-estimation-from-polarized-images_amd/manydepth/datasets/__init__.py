@@ -15,6 +15,14 @@ computed on the device by K1, instead of the per-pixel ``lstsq`` in the DataLoad
 Colour augmentation (indoor_dataset.py:92-106, 226-233, 300, 404-407): with probability 0.5 a training item's
 ``color_aug`` pyramid is the ColorJitter(brightness, contrast, saturation in [0.8, 1.2], hue in [-0.1, 0.1]) of
 its ``color`` pyramid -- torchvision 0.8.2's PIL path restated on PIL.ImageEnhance (torchvision is not installed).
+
+Opt-in (``raw_color=True`` / ``PD_DEVICE_COLOR=1``): the colour pyramids leave the workers too.  A file-backed item then
+carries the decoded frame at its native size, ``("color_raw", 0, 0)`` uint8 [3,Hf,Wf], and its augmentation draw,
+``"color_jitter"`` float64 [8] (``polardepth.color.pack_jitter``; zeros for a plain or an evaluation item), instead of the
+eight ``color`` / ``color_aug`` tensors; Trainer.process_batch / Evaluation.predict expand them on the device
+(``polardepth.color.color_pyramid``: the same successive LANCZOS resizes and ColorJitter, bit for bit).  The item draws
+from ``random`` exactly as the host path does.  Default collation stacks the frames, so every frame of a batch must have
+one native size -- HAMMER's do.
 """
 import glob
 import os
@@ -57,11 +65,14 @@ def apply_color_jitter(img, params):
 class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
-                 depth_modality="_gt", items_per_scene=8, raw_pol=None):
+                 depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None):
         super().__init__()
         # raw_pol: hand the four polarizer images over at their native size; the Trainer resizes them on the device
         # with the Pillow-exact LANCZOS kernels before K1.  Default: $PD_DEVICE_RESIZE == "1".
         self.raw_pol = (os.environ.get("PD_DEVICE_RESIZE") == "1") if raw_pol is None else bool(raw_pol)
+        # raw_color: hand the decoded RGB frame and the jitter draw over instead of the colour pyramids (module docstring).
+        # Default: $PD_DEVICE_COLOR == "1".  Synthetic items are not affected.
+        self.raw_color = (os.environ.get("PD_DEVICE_COLOR") == "1") if raw_color is None else bool(raw_color)
         self.data_path, self.modality, self.depth_modality, self.img_ext = data_path, modality, depth_modality, img_ext
         self.height, self.width, self.num_scales = height, width, num_scales
         self.is_train = is_train
@@ -105,12 +116,17 @@ class HAMMER_Dataset(Dataset):
         prev = color
         do_color_aug = self.is_train and random.random() > 0.5                     # indoor_dataset.py:300
         jitter = color_jitter_params() if do_color_aug else None                   # :404-405, one draw per item
-        for s in range(self.num_scales):          # successive LANCZOS resizes (indoor_dataset.py:192-215)
-            prev = prev.resize((W >> s, H >> s), Image.LANCZOS)
-            inputs[("color", 0, s)] = to_t(prev)
-            blank = inputs[("color", 0, s)].sum() == 0                             # :222-225 blank frames stay blank
-            inputs[("color_aug", 0, s)] = to_t(apply_color_jitter(prev, jitter)) if (do_color_aug and not blank) \
-                else inputs[("color", 0, s)]
+        if self.raw_color:                        # resizes, jitter and / 255 happen on the device (polardepth/color.py)
+            from polardepth.color import pack_jitter
+            inputs[("color_raw", 0, 0)] = torch.from_numpy(np.ascontiguousarray(np.asarray(color, dtype=np.uint8).transpose(2, 0, 1)))
+            inputs["color_jitter"] = torch.from_numpy(pack_jitter(jitter))
+        else:
+            for s in range(self.num_scales):      # successive LANCZOS resizes (indoor_dataset.py:192-215)
+                prev = prev.resize((W >> s, H >> s), Image.LANCZOS)
+                inputs[("color", 0, s)] = to_t(prev)
+                blank = inputs[("color", 0, s)].sum() == 0                         # :222-225 blank frames stay blank
+                inputs[("color_aug", 0, s)] = to_t(apply_color_jitter(prev, jitter)) if (do_color_aug and not blank) \
+                    else inputs[("color", 0, s)]
         pol_imgs = [Image.open(os.path.join(folder, d, name)).convert("L")
                     for d in ("pol00", "pol01", "pol10", "pol11")]                # 0, 45, 90, 135 degrees
         planes = [np.asarray(im if self.raw_pol else im.resize((W, H), Image.LANCZOS)) for im in pol_imgs]

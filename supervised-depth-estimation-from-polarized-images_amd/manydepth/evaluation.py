@@ -10,6 +10,7 @@ from manydepth import datasets, networks
 from manydepth.utils import readlines
 from polardepth import ops
 from polardepth import polar as pdpolar
+from polardepth import color as pdcolor
 from polardepth._lib import lib, check, ptr, stream_ptr
 
 _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, "teapot": 120, "cutlery": 140,
@@ -71,6 +72,7 @@ class Evaluation:
 
     @torch.no_grad()
     def predict(self, inputs):
+        pdcolor.expand_batch(inputs, (self.height, self.width), 4)      # HAMMER_Dataset(raw_color=True) batches
         normals = None
         if ("pol", 0, 0) in inputs:
             kw = {} if self.pol_angles is None else {"angles": self.pol_angles}

@@ -32,6 +32,7 @@ from manydepth import datasets, networks
 from polardepth import functional as PF
 from polardepth import polar as pdpolar
 from polardepth import resize as pdresize
+from polardepth import color as pdcolor
 from polardepth import ops
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
 from polardepth._lib import lib, check, ptr, stream_ptr
@@ -382,6 +383,9 @@ class Trainer:
     def process_batch(self, inputs, is_train=False):
         for key, ipt in inputs.items():
             inputs[key] = ipt.to(self.device, non_blocking=True)
+        # raw frames + jitter rows from the loader (HAMMER_Dataset(raw_color=True)): the colour pyramids on the device,
+        # 4 scales like the loaders above; inside the captured step under PD_STEP_GRAPH=1, like the raw_pol resize
+        pdcolor.expand_batch(inputs, (self.opt.height, self.opt.width), 4)
         if self.train_teacher_and_pose and is_train and self.bf16:
             with _Bf16Step():
                 mono_outputs = self._forward_models(inputs)

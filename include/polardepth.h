@@ -542,6 +542,23 @@ int pd_softmax_rows_bwd(const void* p, void* dp, long R, long L, float scale, vo
 int pd_resize_u8_pass(const void* src, void* dst, const void* coeffs, const void* bounds, int ksize, int P, int Hs,
                       int Ws, int out_size, int vertical, void* stream);
 
+/* ---- the same pass for 16-bit and float planes, the other two element types K1's general kernel takes: Pillow's
+ * ImagingResampleHorizontal_16bpc / ImagingResampleVertical_16bpc (mode I;16) and the IMAGING_TYPE_FLOAT32 case of
+ * ImagingResampleHorizontal_32bpc / ImagingResampleVertical_32bpc (mode F), src/libImaging/Resample.c.
+ * dtype   PD_POLAR_U16 or PD_POLAR_F32 (PD_POLAR_U8 is an error: pd_resize_u8_pass); src, dst: planes of that type, shapes
+ *         as for pd_resize_u8_pass
+ * coeffs  DOUBLE [out_size][ksize] = precompute_coeffs' w[x] / ww without the 8bpc normalisation; bounds as above
+ *         (polardepth/resize.py lanczos_coeffs_f64).  A bounds row that points outside the input is cut to fit.
+ * Per output: double ss = 0; ss += (double)in[first + x] * k[x] in tap order, multiply and add rounded separately.
+ *   F:    out = (float)ss.  NaN and infinity follow IEEE: a non-finite input reaches every output whose window holds it,
+ *         also through a zero coefficient.
+ *   I;16: v = ss >= 0 ? (int)(ss + 0.5) : (int)(ss - 0.5), then Pillow's BYTEWISE store: low byte = clip8(v % 256) with
+ *         C's remainder, high byte = clip8(v >> 8).  Undershoot (v < 0) gives 0.  Overshoot past 65535 does NOT saturate
+ *         to 65535: the high byte clips to 255 and the low byte wraps (65836 -> 0xff2c).  Data in 12-bit range never gets
+ *         there.  The image between the two passes has the planes' own type and the same rule. */
+int pd_resize_wide_pass(const void* src, void* dst, int dtype, const void* coeffs, const void* bounds, int ksize, int P,
+                        int Hs, int Ws, int out_size, int vertical, void* stream);
+
 /* ---- torchvision 0.8.2's PIL ColorJitter on uint8 planar RGB, Pillow-exact, fused with the loader's uint8 -> fp32 / 255
  * (indoor_dataset.py:92-106, 192-233, 404-407; csrc/color.hip, arithmetic in csrc/color_math.hpp).
  * src [B][3][H][W] uint8 (what pd_resize_u8_pass leaves for a [B,3,.,.] input), any H, W >= 1.

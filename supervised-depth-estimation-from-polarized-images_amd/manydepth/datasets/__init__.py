@@ -23,6 +23,12 @@ eight ``color`` / ``color_aug`` tensors; Trainer.process_batch / Evaluation.pred
 (``polardepth.color.color_pyramid``: the same successive LANCZOS resizes and ColorJitter, bit for bit).  The item draws
 from ``random`` exactly as the host path does.  Default collation stacks the frames, so every frame of a batch must have
 one native size -- HAMMER's do.
+
+Opt-in (``pol_native=True`` / ``PD_POL_NATIVE=1``): the polarizer planes keep the depth of their files -- 8-bit files
+(PIL mode ``L``) stay uint8, 16-bit files (``I;16``) become uint16, float files (``F``) float32 -- instead of the
+``convert("L")`` that clips a 16-bit file at 255.  The worker's resize is then PIL's LANCZOS in that mode, and with
+``raw_pol`` the planes travel raw and ``polardepth.resize.resize_lanczos`` gives the same bits on the device.  K1's general
+kernel takes all three (polardepth/polar.py).
 """
 import glob
 import os
@@ -65,7 +71,7 @@ def apply_color_jitter(img, params):
 class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
-                 depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None):
+                 depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None):
         super().__init__()
         # raw_pol: hand the four polarizer images over at their native size; the Trainer resizes them on the device
         # with the Pillow-exact LANCZOS kernels before K1.  Default: $PD_DEVICE_RESIZE == "1".
@@ -73,6 +79,9 @@ class HAMMER_Dataset(Dataset):
         # raw_color: hand the decoded RGB frame and the jitter draw over instead of the colour pyramids (module docstring).
         # Default: $PD_DEVICE_COLOR == "1".  Synthetic items are not affected.
         self.raw_color = (os.environ.get("PD_DEVICE_COLOR") == "1") if raw_color is None else bool(raw_color)
+        # pol_native: keep each polarizer file's depth (module docstring).  Default: $PD_POL_NATIVE == "1".  Synthetic items
+        # are not affected.
+        self.pol_native = (os.environ.get("PD_POL_NATIVE") == "1") if pol_native is None else bool(pol_native)
         self.data_path, self.modality, self.depth_modality, self.img_ext = data_path, modality, depth_modality, img_ext
         self.height, self.width, self.num_scales = height, width, num_scales
         self.is_train = is_train
@@ -127,10 +136,13 @@ class HAMMER_Dataset(Dataset):
                 blank = inputs[("color", 0, s)].sum() == 0                         # :222-225 blank frames stay blank
                 inputs[("color_aug", 0, s)] = to_t(apply_color_jitter(prev, jitter)) if (do_color_aug and not blank) \
                     else inputs[("color", 0, s)]
-        pol_imgs = [Image.open(os.path.join(folder, d, name)).convert("L")
-                    for d in ("pol00", "pol01", "pol10", "pol11")]                # 0, 45, 90, 135 degrees
-        planes = [np.asarray(im if self.raw_pol else im.resize((W, H), Image.LANCZOS)) for im in pol_imgs]
-        inputs[("pol", 0, 0)] = torch.from_numpy(np.stack(planes).astype(np.uint8))
+        pol_paths = [os.path.join(folder, d, name) for d in ("pol00", "pol01", "pol10", "pol11")]   # 0, 45, 90, 135 degrees
+        if self.pol_native:
+            inputs[("pol", 0, 0)] = self._native_planes(pol_paths)
+        else:
+            pol_imgs = [Image.open(p).convert("L") for p in pol_paths]
+            planes = [np.asarray(im if self.raw_pol else im.resize((W, H), Image.LANCZOS)) for im in pol_imgs]
+            inputs[("pol", 0, 0)] = torch.from_numpy(np.stack(planes).astype(np.uint8))
 
         def depth_of(sub):                        # 16-bit PNG in mm -> metres, nearest resize (hammer_dataset.py:135-169)
             im = Image.open(os.path.join(folder, sub, "{:06d}.png".format(idx)))
@@ -158,6 +170,23 @@ class HAMMER_Dataset(Dataset):
         inputs["stereo_T"] = torch.eye(4)
         inputs["stereo_T"][0, 3] = -0.0498921
         return inputs
+
+    def _native_planes(self, paths):
+        """The four polarizer files at the depth they were written with: [4,h,w] uint8 (mode L), uint16 (I;16, I;16L, I;16B,
+        I;16N) or float32 (F), resized by PIL in that mode unless ``raw_pol`` hands them over raw."""
+        from PIL import Image
+        imgs = [Image.open(p) for p in paths]
+        kinds = ["I;16" if im.mode.startswith("I;16") else im.mode for im in imgs]
+        dtypes = {"L": np.uint8, "I;16": np.uint16, "F": np.float32}
+        for p, im, kind in zip(paths, imgs, kinds):
+            if kind not in dtypes:
+                raise ValueError(f"{p}: polarizer image of mode {im.mode!r}; pol_native serves L, I;16 and F")
+            if kind != kinds[0]:
+                raise ValueError(f"{p}: polarizer image of mode {im.mode!r}, but {paths[0]} is {imgs[0].mode!r}: the four "
+                                 "planes of a frame must have one mode")
+        if not self.raw_pol:
+            imgs = [im.resize((self.width, self.height), Image.LANCZOS) for im in imgs]
+        return torch.from_numpy(np.stack([np.asarray(im).astype(dtypes[kinds[0]]) for im in imgs]))
 
     def __len__(self):
         return self.items

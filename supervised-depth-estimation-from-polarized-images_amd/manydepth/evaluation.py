@@ -73,11 +73,9 @@ class Evaluation:
     @torch.no_grad()
     def predict(self, inputs):
         pdcolor.expand_batch(inputs, (self.height, self.width), 4)      # HAMMER_Dataset(raw_color=True) batches
-        normals = None
-        if ("pol", 0, 0) in inputs:
-            kw = {} if self.pol_angles is None else {"angles": self.pol_angles}
-            out = pdpolar.polar_forward(inputs[("pol", 0, 0)], want=("xolp", "normals") if self.augment_normals else ("xolp",), **kw)
-            inputs[("xolp", 0, 0)] = out["xolp"]; normals = out.get("normals")
+        # the Trainer's hand-over: un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
+        normals = pdpolar.polar_inputs(inputs, (self.height, self.width),
+                                       ("xolp", "normals") if self.augment_normals else ("xolp",), self.pol_angles)
         feats = self.models["rgb_encoder"](inputs["color_aug", 0, 0].float())
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None
         nf = self.models["normals_encoder"](inputs["xolp", 0, 0].float(), normals=normals) if self.augment_normals else None

@@ -31,7 +31,6 @@ from .layers import SSIM, compute_depth_errors, compute_depth_errors_numpy
 from manydepth import datasets, networks
 from polardepth import functional as PF
 from polardepth import polar as pdpolar
-from polardepth import resize as pdresize
 from polardepth import color as pdcolor
 from polardepth import ops
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
@@ -304,28 +303,11 @@ class Trainer:
     # ------------------------------------------------------------------ forward (trainer.py:469-648)
     def _polar_inputs(self, inputs):
         """On-device XOLP / normals from the raw planes when the loader hands them over (K1)."""
-        normals = None
-        if ("pol_mosaic", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
-            # un-split sensor frame (four polarizer images as quadrants): split on the device
-            inputs[("pol", 0, 0)] = pdpolar.split_mosaic(inputs[("pol_mosaic", 0, 0)])
-        if ("pol", 0, 0) in inputs and (self.opt.augment_xolp or self.opt.augment_normals):
+        want = []
+        if self.opt.augment_xolp or self.opt.augment_normals:
             want = ["xolp"] + (["normals"] if self.opt.augment_normals else [])
-            pol = inputs[("pol", 0, 0)]
-            if pol.shape[2] != self.opt.height or pol.shape[3] > self.opt.width:
-                if pol.dtype != torch.uint8:
-                    raise ValueError(f'("pol", 0, 0) is {pol.dtype} {tuple(pol.shape[2:])}: the device LANCZOS resize serves uint8 '
-                                     f"planes only -- hand over 16-bit / float planes at {self.opt.height} rows and at most "
-                                     f"{self.opt.width} columns")
-                # raw frames from the loader (HAMMER_Dataset(raw_pol=True)): Pillow-exact LANCZOS resize on the device
-                pol = pdresize.resize_lanczos_u8(pol, (self.opt.height, self.opt.width))
-            # planes narrower than the network width (512x612 frames -> 512x640): K1 pads on the fly
-            # (uint16 / float32 planes, or calibrated angles: the general kernel; otherwise the call is unchanged)
-            kw = {} if self.pol_angles is None else {"angles": self.pol_angles}
-            out = pdpolar.polar_forward(pol, want=tuple(want),
-                                        out_width=self.opt.width if pol.shape[3] < self.opt.width else None, **kw)
-            inputs[("xolp", 0, 0)] = out["xolp"]
-            normals = out.get("normals")
-        return normals
+        # raw frames from the loader (HAMMER_Dataset(raw_pol=True), uint8 / uint16 / float32) are resized on the device first
+        return pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles)
 
     def _forward_models(self, inputs):
         normals = self._polar_inputs(inputs)

@@ -180,9 +180,47 @@ def split_mosaic(mosaic):
     if H2 % 2 or W2 % 2:
         raise ValueError(f"split_mosaic: the quadrant frame must have even sides, got {H2}x{W2}")
     h, w = H2 // 2, W2 // 2
-    tl, tr = mosaic[..., :h, :w], mosaic[..., :h, w:]
-    bl, br = mosaic[..., h:, :w], mosaic[..., h:, w:]
-    return torch.stack((tl, tr, bl, br), dim=-3).contiguous()
+    # torch's unsigned 16 / 32 / 64-bit types have few kernels: the copy runs on the signed type of the same width
+    signed = {torch.uint16: torch.int16, torch.uint32: torch.int32, torch.uint64: torch.int64}.get(mosaic.dtype)
+    m = mosaic if signed is None else mosaic.view(signed)
+    tl, tr = m[..., :h, :w], m[..., :h, w:]
+    bl, br = m[..., h:, :w], m[..., h:, w:]
+    planes = torch.stack((tl, tr, bl, br), dim=-3).contiguous()
+    return planes if signed is None else planes.view(mosaic.dtype)
+
+
+def polar_inputs(inputs, size, want, angles=None):
+    """The loader's hand-over to K1, shared by Trainer._polar_inputs and Evaluation.predict.  ``inputs`` is a batch on the
+    device; size = (height, width) of the network input; want as for ``polar_forward`` (empty: only the split below).
+
+    An un-split sensor frame ("pol_mosaic", 0, 0) becomes ("pol", 0, 0) (``split_mosaic``).  Raw planes from
+    ``HAMMER_Dataset(raw_pol=True)`` -- any height but ``height``, or wider than ``width`` -- take the Pillow-exact LANCZOS
+    resize on the device (``polardepth.resize.resize_lanczos``: uint8, uint16 or float32); planes already at network size
+    take none.  uint16 / float32 planes with FEWER rows than ``height`` are a ValueError (raw frames are never shorter than the
+    network input; ``resize_lanczos`` itself enlarges any of the three types).  Planes narrower than ``width`` (512x612 frames -> 512x640) are padded by K1 on the fly.  Writes
+    ("xolp", 0, 0) into ``inputs`` and returns the normals [B,9,H,W] when wanted, else None."""
+    if ("pol_mosaic", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
+        inputs[("pol", 0, 0)] = split_mosaic(inputs[("pol_mosaic", 0, 0)])
+    if not want or ("pol", 0, 0) not in inputs:
+        return None
+    height, width = int(size[0]), int(size[1])
+    pol = inputs[("pol", 0, 0)]
+    if pol.shape[2] != height or pol.shape[3] > width:
+        from . import resize as pdresize
+        if pol.dtype not in _GENERAL_DTYPES:
+            raise ValueError(f'("pol", 0, 0) must be uint8, uint16 or float32, got {pol.dtype} {tuple(pol.shape)}')
+        if pol.dtype != torch.uint8 and pol.shape[2] < height:
+            # a loader's raw frame is never shorter than the network input: 16-bit / float planes with fewer rows are a
+            # mismatch between loader and options, not something to enlarge silently (uint8 planes keep what they had)
+            raise ValueError(f'("pol", 0, 0) is {pol.dtype} {tuple(pol.shape[2:])}, fewer rows than the network\'s {height}: this '
+                             f"hand-over enlarges uint8 planes only -- raw 16-bit / float frames are resized down on the device, "
+                             f"smaller ones must arrive at {height} rows and at most {width} columns")
+        pol = pdresize.resize_lanczos(pol, (height, width))
+    # (uint16 / float32 planes, or calibrated angles: the general kernel; otherwise the call is unchanged)
+    kw = {} if angles is None else {"angles": angles}
+    out = polar_forward(pol, want=tuple(want), out_width=width if pol.shape[3] < width else None, **kw)
+    inputs[("xolp", 0, 0)] = out["xolp"]
+    return out.get("normals")
 
 
 def normals_from_xolp(xolp, n=1.5, precise=False):

@@ -559,6 +559,32 @@ int pd_resize_u8_pass(const void* src, void* dst, const void* coeffs, const void
 int pd_resize_wide_pass(const void* src, void* dst, int dtype, const void* coeffs, const void* bounds, int ksize, int P,
                         int Hs, int Ws, int out_size, int vertical, void* stream);
 
+/* ---- demosaic of division-of-focal-plane (DoFP) polarizer frames (csrc/dofp.hip): the interleaved mosaic a polarization
+ * sensor emits -- every 2x2 super-pixel carries the four filters -- -> the four planes of ("pol", 0, 0).  Not in the
+ * reference, whose data arrive split into pol00 .. pol11 (polarisation/pol_split_and_save.py cuts QUADRANT frames).
+ * mosaic  [B][H2][W2] device, contiguous, element type `dtype` (PD_POLAR_U8 / _U16 / _F32); H2, W2 even and >= 2; rows need
+ *         no alignment (W2 = 6 uint8 is fine), the two base pointers must be 16-byte aligned
+ * layout  four HOST ints, a permutation of 0..3, read during the call: layout[2 r + c] = the plane that the site at row
+ *         parity r, column parity c feeds; r_p, c_p below are the site of plane p.  (2,1,3,0) is the Sony IMX250MZR
+ *         (90/45/135/0 degrees in reading order) with the planes in the nominal 0/45/90/135 order.
+ * PD_DOFP_SUPERPIXEL: planes [B][4][H2/2][W2/2] of the SAME dtype, planes[p][y][x] = mosaic[2y + r_p][2x + c_p]
+ * PD_DOFP_BILINEAR:   planes [B][4][H2][W2] fp32; with dy = (y - r_p) & 1, dx = (x - c_p) & 1 and m = the frame:
+ *           dy dx
+ *           0  0   m[y][x]
+ *           0  1   (m[y][x-1] + m[y][x+1]) * 0.5
+ *           1  0   (m[y-1][x] + m[y+1][x]) * 0.5
+ *           1  1   ((m[y-1][x-1] + m[y-1][x+1]) + (m[y+1][x-1] + m[y+1][x+1])) * 0.25
+ *         index -1 reads index 1 and index n reads index n-2 (a mirror about the edge sample: the site parity survives).
+ *         fp64 in exactly that order, rounded once to fp32: exact for the integer types, and for fp32 what makes the result
+ *         defined (a frame of FLT_MAX returns FLT_MAX, not infinity).  NaN and infinity reach the outputs whose stencil
+ *         holds them.
+ * B == 0 returns 0.  No allocation, copy or synchronisation: the call can be captured into a graph.  Frames beyond 2^30
+ * pixels (or 2^40 in the batch) are refused ("too large": in-frame offsets are 32-bit in the kernels). */
+#define PD_DOFP_SUPERPIXEL 0
+#define PD_DOFP_BILINEAR 1
+int pd_dofp_demosaic(const void* mosaic, int dtype, void* planes, int mode, const int* layout, int B, int H2, int W2,
+                     void* stream);
+
 /* ---- torchvision 0.8.2's PIL ColorJitter on uint8 planar RGB, Pillow-exact, fused with the loader's uint8 -> fp32 / 255
  * (indoor_dataset.py:92-106, 192-233, 404-407; csrc/color.hip, arithmetic in csrc/color_math.hpp).
  * src [B][3][H][W] uint8 (what pd_resize_u8_pass leaves for a [B,3,.,.] input), any H, W >= 1.

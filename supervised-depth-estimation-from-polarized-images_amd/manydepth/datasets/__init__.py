@@ -29,6 +29,11 @@ Opt-in (``pol_native=True`` / ``PD_POL_NATIVE=1``): the polarizer planes keep th
 ``convert("L")`` that clips a 16-bit file at 255.  The worker's resize is then PIL's LANCZOS in that mode, and with
 ``raw_pol`` the planes travel raw and ``polardepth.resize.resize_lanczos`` gives the same bits on the device.  K1's general
 kernel takes all three (polardepth/polar.py).
+
+Opt-in (``pol_dofp=True`` / ``PD_POL_DOFP=1``): a frame's polarizer data is the sensor's interleaved division-of-focal-plane
+mosaic, ONE file ``<scene>/<modality>/pol_dofp/%06d.png`` instead of ``pol00`` .. ``pol11``.  It is handed over raw at its
+file depth (``L`` uint8, ``I;16*`` uint16, ``F`` float32) as ``("pol_dofp", 0, 0)`` [1,H2,W2]; the item carries no
+``("pol", 0, 0)``.  ``polardepth.polar.polar_inputs`` reconstructs the planes on the device (polardepth/dofp.py).
 """
 import glob
 import os
@@ -71,7 +76,8 @@ def apply_color_jitter(img, params):
 class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
-                 depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None):
+                 depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None,
+                 pol_dofp=None):
         super().__init__()
         # raw_pol: hand the four polarizer images over at their native size; the Trainer resizes them on the device
         # with the Pillow-exact LANCZOS kernels before K1.  Default: $PD_DEVICE_RESIZE == "1".
@@ -82,6 +88,9 @@ class HAMMER_Dataset(Dataset):
         # pol_native: keep each polarizer file's depth (module docstring).  Default: $PD_POL_NATIVE == "1".  Synthetic items
         # are not affected.
         self.pol_native = (os.environ.get("PD_POL_NATIVE") == "1") if pol_native is None else bool(pol_native)
+        # pol_dofp: the polarizer data of a frame is one interleaved sensor mosaic, pol_dofp/%06d.png (module docstring).
+        # Default: $PD_POL_DOFP == "1".  Synthetic items are not affected.
+        self.pol_dofp = (os.environ.get("PD_POL_DOFP") == "1") if pol_dofp is None else bool(pol_dofp)
         self.data_path, self.modality, self.depth_modality, self.img_ext = data_path, modality, depth_modality, img_ext
         self.height, self.width, self.num_scales = height, width, num_scales
         self.is_train = is_train
@@ -97,19 +106,21 @@ class HAMMER_Dataset(Dataset):
             self.filenames = list(filenames or [])
             self.frames = self._discover(self.filenames)
             if self.filenames and not self.frames:
-                raise FileNotFoundError(f"no complete HAMMER frame (rgb, pol00/01/10/11, _gt, {depth_modality}) under "
+                raise FileNotFoundError(f"no complete HAMMER frame (rgb, {'pol_dofp' if self.pol_dofp else 'pol00/01/10/11'}, _gt, "
+                                        f"{depth_modality}) under "
                                         f"{data_path!r} for scenes {self.filenames[:3]}...")
             self.items = len(self.frames)
 
     # ---- real HAMMER tree -------------------------------------------------------------------------------
     def _discover(self, scenes):
-        """(folder, frame_index) of every frame that has rgb, the four polarizer images, _gt and depth_modality."""
+        """(folder, frame_index) of every frame that has rgb, the four polarizer images (``pol_dofp``: the one mosaic), _gt
+        and depth_modality."""
         frames = []
         for scene in scenes or []:
             folder = os.path.join(self.data_path, scene, self.modality)
             for f in sorted(glob.glob(os.path.join(folder, "rgb", "*" + self.img_ext))):
                 idx = int(os.path.basename(f).split('.')[0])
-                need = ["pol00", "pol01", "pol10", "pol11", "_gt", self.depth_modality]
+                need = (["pol_dofp"] if self.pol_dofp else ["pol00", "pol01", "pol10", "pol11"]) + ["_gt", self.depth_modality]
                 if all(os.path.isfile(os.path.join(folder, d, "{:06d}.png".format(idx))) for d in need):
                     frames.append((folder, idx))
         return frames
@@ -137,7 +148,9 @@ class HAMMER_Dataset(Dataset):
                 inputs[("color_aug", 0, s)] = to_t(apply_color_jitter(prev, jitter)) if (do_color_aug and not blank) \
                     else inputs[("color", 0, s)]
         pol_paths = [os.path.join(folder, d, name) for d in ("pol00", "pol01", "pol10", "pol11")]   # 0, 45, 90, 135 degrees
-        if self.pol_native:
+        if self.pol_dofp:
+            inputs[("pol_dofp", 0, 0)] = self._dofp_frame(os.path.join(folder, "pol_dofp", "{:06d}.png".format(idx)))
+        elif self.pol_native:
             inputs[("pol", 0, 0)] = self._native_planes(pol_paths)
         else:
             pol_imgs = [Image.open(p).convert("L") for p in pol_paths]
@@ -170,6 +183,18 @@ class HAMMER_Dataset(Dataset):
         inputs["stereo_T"] = torch.eye(4)
         inputs["stereo_T"][0, 3] = -0.0498921
         return inputs
+
+    @staticmethod
+    def _dofp_frame(path):
+        """The interleaved sensor mosaic, raw, at the depth it was written with: [1,H2,W2] uint8 (mode L), uint16 (I;16*) or
+        float32 (F)."""
+        from PIL import Image
+        im = Image.open(path)
+        kind = "I;16" if im.mode.startswith("I;16") else im.mode
+        dtypes = {"L": np.uint8, "I;16": np.uint16, "F": np.float32}
+        if kind not in dtypes:
+            raise ValueError(f"{path}: DoFP mosaic of mode {im.mode!r}; pol_dofp serves L, I;16 and F")
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(im).astype(dtypes[kind])))[None]
 
     def _native_planes(self, paths):
         """The four polarizer files at the depth they were written with: [4,h,w] uint8 (mode L), uint16 (I;16, I;16L, I;16B,

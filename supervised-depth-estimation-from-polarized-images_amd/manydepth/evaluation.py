@@ -10,6 +10,7 @@ from manydepth import datasets, networks
 from manydepth.utils import readlines
 from polardepth import ops
 from polardepth import polar as pdpolar
+from polardepth import dofp as pddofp
 from polardepth import color as pdcolor
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -19,12 +20,16 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
 
 class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
-                 augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None):
+                 augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
+                 pol_layout=None, pol_demosaic=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
         calibrated polarizer angles in degrees, in the order of the planes of ("pol", 0, 0) (or $PD_POL_ANGLES="a,b,c,d",
-        read here once); None = the nominal 0/45/90/135 set.  ("pol", 0, 0) may be uint8, uint16 or float32."""
+        read here once); None = the nominal 0/45/90/135 set.  ("pol", 0, 0) may be uint8, uint16 or float32.
+        ``pol_layout`` / ``pol_demosaic``: for batches that carry the interleaved sensor frame ("pol_dofp", 0, 0) instead --
+        the plane each site of the 2x2 super-pixel feeds (or $PD_POL_LAYOUT="2,1,3,0") and "bilinear" | "superpixel" (or
+        $PD_POL_DEMOSAIC); None = the IMX250MZR's layout, bilinear.  ``pol_angles`` then refer to the layout's planes."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -36,6 +41,8 @@ class Evaluation:
         self.augment_xolp, self.augment_normals = augment_xolp, augment_normals
         self.load_weights_folder = load_weights_folder
         self.pol_angles = pdpolar.angles_from_degrees(pol_angles if pol_angles is not None else os.environ.get("PD_POL_ANGLES"))
+        self.pol_dofp = pddofp.options(pol_layout if pol_layout is not None else os.environ.get("PD_POL_LAYOUT"),
+                                       pol_demosaic if pol_demosaic is not None else os.environ.get("PD_POL_DEMOSAIC"))
         self.device = torch.device("cuda")
         self.models = {"rgb_encoder": networks.ShallowResnetEncoder(18, False)}
         if augment_normals:
@@ -73,9 +80,10 @@ class Evaluation:
     @torch.no_grad()
     def predict(self, inputs):
         pdcolor.expand_batch(inputs, (self.height, self.width), 4)      # HAMMER_Dataset(raw_color=True) batches
-        # the Trainer's hand-over: un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
+        # the Trainer's hand-over: interleaved sensor frames (demosaic), un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
         normals = pdpolar.polar_inputs(inputs, (self.height, self.width),
-                                       ("xolp", "normals") if self.augment_normals else ("xolp",), self.pol_angles)
+                                       ("xolp", "normals") if self.augment_normals else ("xolp",), self.pol_angles,
+                                       dofp=self.pol_dofp)
         feats = self.models["rgb_encoder"](inputs["color_aug", 0, 0].float())
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None
         nf = self.models["normals_encoder"](inputs["xolp", 0, 0].float(), normals=normals) if self.augment_normals else None

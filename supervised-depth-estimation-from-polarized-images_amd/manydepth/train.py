@@ -21,6 +21,13 @@ def main():
     # (opt.pol_angles; default: the nominal 0/45/90/135 set) -- read here only, like PD_BF16
     if os.environ.get("PD_POL_ANGLES"):
         opts.pol_angles = [float(x) for x in os.environ["PD_POL_ANGLES"].split(",")]
+    # PD_POL_LAYOUT="2,1,3,0" / PD_POL_DEMOSAIC=bilinear|superpixel: interleaved sensor frames (PD_POL_DOFP=1 makes the loader
+    # serve them) -- the plane each site of the 2x2 super-pixel feeds, in reading order, and how the planes are reconstructed
+    # (opt.pol_layout / opt.pol_demosaic; defaults: the IMX250MZR's 2,1,3,0 and bilinear)
+    if os.environ.get("PD_POL_LAYOUT"):
+        opts.pol_layout = [int(x) for x in os.environ["PD_POL_LAYOUT"].split(",")]
+    if os.environ.get("PD_POL_DEMOSAIC"):
+        opts.pol_demosaic = os.environ["PD_POL_DEMOSAIC"]
     if int(os.environ.get("WORLD_SIZE", 1)) > 1 and not torch.distributed.is_initialized():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
         torch.distributed.init_process_group("nccl")      # "nccl" is RCCL on ROCm

@@ -31,6 +31,7 @@ from .layers import SSIM, compute_depth_errors, compute_depth_errors_numpy
 from manydepth import datasets, networks
 from polardepth import functional as PF
 from polardepth import polar as pdpolar
+from polardepth import dofp as pddofp
 from polardepth import color as pdcolor
 from polardepth import ops
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
@@ -115,6 +116,10 @@ class Trainer:
         # selected on the options object (``opt.pol_angles``; manydepth/train.py maps PD_POL_ANGLES="a,b,c,d" onto it).
         # None = the nominal 0/45/90/135 set; given, K1 runs its general kernel (polardepth.polar.polar_forward(angles=))
         self.pol_angles = pdpolar.angles_from_degrees(getattr(self.opt, "pol_angles", None))
+        # interleaved sensor frames (("pol_dofp", 0, 0), HAMMER_Dataset(pol_dofp=True)): which plane each site of the 2x2
+        # super-pixel feeds and how the planes are reconstructed (``opt.pol_layout`` / ``opt.pol_demosaic``; train.py maps
+        # PD_POL_LAYOUT / PD_POL_DEMOSAIC onto them).  None = IMX250MZR / bilinear; pol_angles refer to the layout's planes
+        self.pol_dofp = pddofp.options(getattr(self.opt, "pol_layout", None), getattr(self.opt, "pol_demosaic", None))
 
         timestamp = datetime.now()
         self.data_path, self.data_path_val, self.log_dir = self.opt.data_path, self.opt.data_path_val, self.opt.log_dir
@@ -307,7 +312,8 @@ class Trainer:
         if self.opt.augment_xolp or self.opt.augment_normals:
             want = ["xolp"] + (["normals"] if self.opt.augment_normals else [])
         # raw frames from the loader (HAMMER_Dataset(raw_pol=True), uint8 / uint16 / float32) are resized on the device first
-        return pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles)
+        return pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles,
+                                    dofp=self.pol_dofp)
 
     def _forward_models(self, inputs):
         normals = self._polar_inputs(inputs)

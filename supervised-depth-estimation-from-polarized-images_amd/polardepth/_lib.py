@@ -107,6 +107,7 @@ SIGNATURES = {
     "pd_softmax_rows_bwd": (_i, [_vp, _vp, _l, _l, _f, _vp]),
     "pd_resize_u8_pass": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pd_resize_wide_pass": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "pd_dofp_demosaic": (_i, [_vp, _i, _vp, _i, _ip, _i, _i, _i, _vp]),
     "pd_color_jitter_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pd_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pd_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),

@@ -189,7 +189,7 @@ def split_mosaic(mosaic):
     return planes if signed is None else planes.view(mosaic.dtype)
 
 
-def polar_inputs(inputs, size, want, angles=None):
+def polar_inputs(inputs, size, want, angles=None, dofp=None):
     """The loader's hand-over to K1, shared by Trainer._polar_inputs and Evaluation.predict.  ``inputs`` is a batch on the
     device; size = (height, width) of the network input; want as for ``polar_forward`` (empty: only the split below).
 
@@ -198,7 +198,16 @@ def polar_inputs(inputs, size, want, angles=None):
     resize on the device (``polardepth.resize.resize_lanczos``: uint8, uint16 or float32); planes already at network size
     take none.  uint16 / float32 planes with FEWER rows than ``height`` are a ValueError (raw frames are never shorter than the
     network input; ``resize_lanczos`` itself enlarges any of the three types).  Planes narrower than ``width`` (512x612 frames -> 512x640) are padded by K1 on the fly.  Writes
-    ("xolp", 0, 0) into ``inputs`` and returns the normals [B,9,H,W] when wanted, else None."""
+    ("xolp", 0, 0) into ``inputs`` and returns the normals [B,9,H,W] when wanted, else None.
+
+    An interleaved division-of-focal-plane frame ("pol_dofp", 0, 0) ([B,1,H2,W2] or [B,H2,W2], uint8 / uint16 / float32:
+    ``HAMMER_Dataset(pol_dofp=True)``) without ("pol", 0, 0) is demosaicked into ("pol", 0, 0) first
+    (``polardepth.dofp.demosaic``); ``dofp = (layout, mode)`` selects how, None = (IMX250MZR, "bilinear").  The planes come
+    out in the order the layout gives them -- the order ``angles`` refers to -- and then take the path above."""
+    if ("pol_dofp", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
+        from . import dofp as pddofp
+        layout, mode = (pddofp.IMX250MZR, "bilinear") if dofp is None else dofp
+        inputs[("pol", 0, 0)] = pddofp.demosaic(inputs[("pol_dofp", 0, 0)], layout, mode)
     if ("pol_mosaic", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
         inputs[("pol", 0, 0)] = split_mosaic(inputs[("pol_mosaic", 0, 0)])
     if not want or ("pol", 0, 0) not in inputs:

@@ -585,6 +585,40 @@ int pd_resize_wide_pass(const void* src, void* dst, int dtype, const void* coeff
 int pd_dofp_demosaic(const void* mosaic, int dtype, void* planes, int mode, const int* layout, int B, int H2, int W2,
                      void* stream);
 
+/* ---- demosaic of COLOUR division-of-focal-plane frames (csrc/cdofp.hip): the colour model of that sensor (Sony IMX250MYR
+ * class) has a Bayer colour filter over the polarizer array, so every 4x4 super-pixel is a 2x2 Bayer cell of 2x2 polarizer
+ * cells, and one raw frame holds the RGB picture and the four polarizer planes.  Not in the reference beyond the `L` weights
+ * and the shape of its 12-channel input (indoor_dataset.py:220-250).
+ * mosaic  [B][H4][W4] device, contiguous, element type `dtype` (PD_POLAR_U8 / _U16 / _F32); H4, W4 multiples of 4 and >= 4;
+ *         rows need no alignment beyond what that gives, every base pointer must be 16-byte aligned
+ * layout  four HOST ints, read during the call, as for pd_dofp_demosaic: a permutation of 0..3, layout[2 (y & 1) + (x & 1)]
+ *         = the polarizer plane the site feeds
+ * bayer   four HOST ints, read during the call: bayer[2 ((y >> 1) & 1) + ((x >> 1) & 1)] = the colour of the site, 0 = R,
+ *         1 = G, 2 = B; one of the four Bayer orders (one R, one B, two G on a diagonal); (0,1,1,2) is RGGB
+ * gains   three HOST doubles, finite: per-colour multipliers (white balance); NULL = (1,1,1)
+ * Definition -- every step fp64, in exactly this order.  The frame m is 16 sub-lattices (ry, rx) in {0..3}^2,
+ * L[i][j] = m[4i + ry][4j + rx], ny = H4 / 4, nx = W4 / 4.  For the output pixel (y, x): i0 = floor((y - ry) / 4),
+ * ty = (y - ry) mod 4, j0 = floor((x - rx) / 4), tx = (x - rx) mod 4; a, b, c, d = L[i0][j0], L[i0][j0+1], L[i0+1][j0],
+ * L[i0+1][j0+1] with every lattice index clamped to [0, n-1];
+ *     v = ((4 - ty) * ((4 - tx) * a + tx * b) + ty * ((4 - tx) * c + tx * d)) * 0.0625
+ * A zero weight still multiplies: a non-finite sample reaches every output whose lattice cell holds it.  For polarizer plane
+ * p and colour k, R and B come from one sub-lattice each and G from two, (v_first + v_second) * 0.5 with first the one in the
+ * upper Bayer row; then ch[p][k] = v * gains[k].
+ * Outputs (each may be NULL, not all three):
+ * planes      [B][4][H4][W4] fp32 = ((19595 R + 38470 G) + 7471 B) * (1 / 65536) of ch[p] (Pillow's `L` weights, which the
+ *             loader applies to the pol* files), rounded once to fp32
+ * color_u8    [B][3][H4][W4] uint8: c = ((ch[0][k] + ch[1][k]) + (ch[2][k] + ch[3][k])) * 0.25 * color_scale, stored as
+ *             clamp(floor(c + 0.5), 0, 255), NaN -> 0.  color_scale must be finite and > 0: 1 for 8-bit frames, 255 / 4095
+ *             for 12-bit ones
+ * rgb_planes  [B][4][3][H4][W4] fp32: ch rounded once (the per-colour polarizer images)
+ * B == 0 returns 0 before anything is looked at.  Every refusal is PD_EINVAL with a message, decided before any launch: null
+ * pointers, unknown dtype, bad layout, bad bayer, non-finite gains or scale, sides that are no multiples of 4, misalignment,
+ * frames beyond 2^30 pixels (or 2^40 in the batch: "too large", in-frame offsets are 32-bit in the kernel).  No allocation,
+ * copy or synchronisation: the call can be captured into a graph. */
+int pd_cdofp_demosaic(const void* mosaic, int dtype, const int* layout, const int* bayer, const double* gains,
+                      double color_scale, void* planes, void* color_u8, void* rgb_planes, int B, int H4, int W4,
+                      void* stream);
+
 /* ---- torchvision 0.8.2's PIL ColorJitter on uint8 planar RGB, Pillow-exact, fused with the loader's uint8 -> fp32 / 255
  * (indoor_dataset.py:92-106, 192-233, 404-407; csrc/color.hip, arithmetic in csrc/color_math.hpp).
  * src [B][3][H][W] uint8 (what pd_resize_u8_pass leaves for a [B,3,.,.] input), any H, W >= 1.

@@ -34,6 +34,13 @@ Opt-in (``pol_dofp=True`` / ``PD_POL_DOFP=1``): a frame's polarizer data is the 
 mosaic, ONE file ``<scene>/<modality>/pol_dofp/%06d.png`` instead of ``pol00`` .. ``pol11``.  It is handed over raw at its
 file depth (``L`` uint8, ``I;16*`` uint16, ``F`` float32) as ``("pol_dofp", 0, 0)`` [1,H2,W2]; the item carries no
 ``("pol", 0, 0)``.  ``polardepth.polar.polar_inputs`` reconstructs the planes on the device (polardepth/dofp.py).
+
+Opt-in (``pol_cdofp=True`` / ``PD_POL_CDOFP=1``): a frame is ONE file of the COLOUR polarization sensor (a Bayer filter over the
+polarizer array), ``<scene>/<modality>/pol_cdofp/%06d.png``; frames are discovered by that folder plus ``_gt`` and the depth
+modality, and neither ``rgb/`` nor ``pol00`` .. ``pol11`` is needed.  The frame is handed over raw at its file depth as
+``("pol_cdofp", 0, 0)`` [1,H4,W4] with the augmentation draw ``"color_jitter"`` (the draw of ``raw_color``); the item carries
+no colour pyramid and no ``("pol", 0, 0)``: Trainer.process_batch / Evaluation.predict make both on the device
+(polardepth/cdofp.py).  The intrinsics are scaled by the frame's own size.
 """
 import glob
 import os
@@ -77,7 +84,7 @@ class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
                  depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None,
-                 pol_dofp=None):
+                 pol_dofp=None, pol_cdofp=None):
         super().__init__()
         # raw_pol: hand the four polarizer images over at their native size; the Trainer resizes them on the device
         # with the Pillow-exact LANCZOS kernels before K1.  Default: $PD_DEVICE_RESIZE == "1".
@@ -91,6 +98,11 @@ class HAMMER_Dataset(Dataset):
         # pol_dofp: the polarizer data of a frame is one interleaved sensor mosaic, pol_dofp/%06d.png (module docstring).
         # Default: $PD_POL_DOFP == "1".  Synthetic items are not affected.
         self.pol_dofp = (os.environ.get("PD_POL_DOFP") == "1") if pol_dofp is None else bool(pol_dofp)
+        # pol_cdofp: a frame is one raw file of the colour polarization sensor, pol_cdofp/%06d.png (module docstring).
+        # Default: $PD_POL_CDOFP == "1".  Synthetic items are not affected.
+        self.pol_cdofp = (os.environ.get("PD_POL_CDOFP") == "1") if pol_cdofp is None else bool(pol_cdofp)
+        if self.pol_cdofp and self.pol_dofp:
+            raise ValueError("HAMMER_Dataset: pol_dofp and pol_cdofp name two different sensors; choose one")
         self.data_path, self.modality, self.depth_modality, self.img_ext = data_path, modality, depth_modality, img_ext
         self.height, self.width, self.num_scales = height, width, num_scales
         self.is_train = is_train
@@ -106,6 +118,9 @@ class HAMMER_Dataset(Dataset):
             self.filenames = list(filenames or [])
             self.frames = self._discover(self.filenames)
             if self.filenames and not self.frames:
+                if self.pol_cdofp:
+                    raise FileNotFoundError(f"no complete HAMMER frame (pol_cdofp, _gt, {depth_modality}) under "
+                                            f"{data_path!r} for scenes {self.filenames[:3]}...")
                 raise FileNotFoundError(f"no complete HAMMER frame (rgb, {'pol_dofp' if self.pol_dofp else 'pol00/01/10/11'}, _gt, "
                                         f"{depth_modality}) under "
                                         f"{data_path!r} for scenes {self.filenames[:3]}...")
@@ -114,13 +129,14 @@ class HAMMER_Dataset(Dataset):
     # ---- real HAMMER tree -------------------------------------------------------------------------------
     def _discover(self, scenes):
         """(folder, frame_index) of every frame that has rgb, the four polarizer images (``pol_dofp``: the one mosaic), _gt
-        and depth_modality."""
+        and depth_modality; with ``pol_cdofp`` every frame that has the colour sensor file, _gt and depth_modality."""
         frames = []
         for scene in scenes or []:
             folder = os.path.join(self.data_path, scene, self.modality)
-            for f in sorted(glob.glob(os.path.join(folder, "rgb", "*" + self.img_ext))):
+            for f in sorted(glob.glob(os.path.join(folder, "pol_cdofp" if self.pol_cdofp else "rgb", "*" + self.img_ext))):
                 idx = int(os.path.basename(f).split('.')[0])
-                need = (["pol_dofp"] if self.pol_dofp else ["pol00", "pol01", "pol10", "pol11"]) + ["_gt", self.depth_modality]
+                need = [] if self.pol_cdofp else (["pol_dofp"] if self.pol_dofp else ["pol00", "pol01", "pol10", "pol11"])
+                need = need + ["_gt", self.depth_modality]
                 if all(os.path.isfile(os.path.join(folder, d, "{:06d}.png".format(idx))) for d in need):
                     frames.append((folder, idx))
         return frames
@@ -131,12 +147,20 @@ class HAMMER_Dataset(Dataset):
         name = "{:06d}{}".format(idx, self.img_ext)
         to_t = lambda im: torch.from_numpy(np.asarray(im, dtype=np.float32).transpose(2, 0, 1) / 255.0)
         inputs = {}
-        color = Image.open(os.path.join(folder, "rgb", name)).convert("RGB")
-        full_w, full_h = color.size
-        prev = color
+        if self.pol_cdofp:                        # the sensor frame is picture and polarizer data at once
+            frame = self._dofp_frame(os.path.join(folder, "pol_cdofp", "{:06d}.png".format(idx)), "pol_cdofp")
+            full_h, full_w = frame.shape[-2:]
+        else:
+            color = Image.open(os.path.join(folder, "rgb", name)).convert("RGB")
+            full_w, full_h = color.size
+            prev = color
         do_color_aug = self.is_train and random.random() > 0.5                     # indoor_dataset.py:300
         jitter = color_jitter_params() if do_color_aug else None                   # :404-405, one draw per item
-        if self.raw_color:                        # resizes, jitter and / 255 happen on the device (polardepth/color.py)
+        if self.pol_cdofp:                        # demosaic, resizes, jitter and / 255 happen on the device (polardepth/cdofp.py)
+            from polardepth.color import pack_jitter
+            inputs[("pol_cdofp", 0, 0)] = frame
+            inputs["color_jitter"] = torch.from_numpy(pack_jitter(jitter))
+        elif self.raw_color:                        # resizes, jitter and / 255 happen on the device (polardepth/color.py)
             from polardepth.color import pack_jitter
             inputs[("color_raw", 0, 0)] = torch.from_numpy(np.ascontiguousarray(np.asarray(color, dtype=np.uint8).transpose(2, 0, 1)))
             inputs["color_jitter"] = torch.from_numpy(pack_jitter(jitter))
@@ -148,7 +172,9 @@ class HAMMER_Dataset(Dataset):
                 inputs[("color_aug", 0, s)] = to_t(apply_color_jitter(prev, jitter)) if (do_color_aug and not blank) \
                     else inputs[("color", 0, s)]
         pol_paths = [os.path.join(folder, d, name) for d in ("pol00", "pol01", "pol10", "pol11")]   # 0, 45, 90, 135 degrees
-        if self.pol_dofp:
+        if self.pol_cdofp:
+            pass                                  # the frame above carries the polarizer data too
+        elif self.pol_dofp:
             inputs[("pol_dofp", 0, 0)] = self._dofp_frame(os.path.join(folder, "pol_dofp", "{:06d}.png".format(idx)))
         elif self.pol_native:
             inputs[("pol", 0, 0)] = self._native_planes(pol_paths)
@@ -185,15 +211,15 @@ class HAMMER_Dataset(Dataset):
         return inputs
 
     @staticmethod
-    def _dofp_frame(path):
+    def _dofp_frame(path, option="pol_dofp"):
         """The interleaved sensor mosaic, raw, at the depth it was written with: [1,H2,W2] uint8 (mode L), uint16 (I;16*) or
-        float32 (F)."""
+        float32 (F).  ``option``: the loader setting the error message names."""
         from PIL import Image
         im = Image.open(path)
         kind = "I;16" if im.mode.startswith("I;16") else im.mode
         dtypes = {"L": np.uint8, "I;16": np.uint16, "F": np.float32}
         if kind not in dtypes:
-            raise ValueError(f"{path}: DoFP mosaic of mode {im.mode!r}; pol_dofp serves L, I;16 and F")
+            raise ValueError(f"{path}: DoFP mosaic of mode {im.mode!r}; {option} serves L, I;16 and F")
         return torch.from_numpy(np.ascontiguousarray(np.asarray(im).astype(dtypes[kind])))[None]
 
     def _native_planes(self, paths):

@@ -11,6 +11,7 @@ from manydepth.utils import readlines
 from polardepth import ops
 from polardepth import polar as pdpolar
 from polardepth import dofp as pddofp
+from polardepth import cdofp as pdcdofp
 from polardepth import color as pdcolor
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -21,7 +22,7 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
 class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
-                 pol_layout=None, pol_demosaic=None):
+                 pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -29,7 +30,11 @@ class Evaluation:
         read here once); None = the nominal 0/45/90/135 set.  ("pol", 0, 0) may be uint8, uint16 or float32.
         ``pol_layout`` / ``pol_demosaic``: for batches that carry the interleaved sensor frame ("pol_dofp", 0, 0) instead --
         the plane each site of the 2x2 super-pixel feeds (or $PD_POL_LAYOUT="2,1,3,0") and "bilinear" | "superpixel" (or
-        $PD_POL_DEMOSAIC); None = the IMX250MZR's layout, bilinear.  ``pol_angles`` then refer to the layout's planes."""
+        $PD_POL_DEMOSAIC); None = the IMX250MZR's layout, bilinear.  ``pol_angles`` then refer to the layout's planes.
+        ``pol_bayer`` / ``pol_gains`` / ``pol_color_scale``: for batches that carry the COLOUR sensor frame ("pol_cdofp", 0, 0)
+        -- the Bayer order (or $PD_POL_BAYER), white-balance gains r,g,b (or $PD_POL_GAINS) and the factor to the 0..255 of
+        the colour picture (or $PD_POL_COLOR_SCALE; 255 / 4095 for 12-bit frames); ``pol_layout`` is shared.  None = RGGB, no
+        gains, 1 for 8-bit frames."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -43,6 +48,11 @@ class Evaluation:
         self.pol_angles = pdpolar.angles_from_degrees(pol_angles if pol_angles is not None else os.environ.get("PD_POL_ANGLES"))
         self.pol_dofp = pddofp.options(pol_layout if pol_layout is not None else os.environ.get("PD_POL_LAYOUT"),
                                        pol_demosaic if pol_demosaic is not None else os.environ.get("PD_POL_DEMOSAIC"))
+        self.pol_cdofp = pdcdofp.options(pol_layout if pol_layout is not None else os.environ.get("PD_POL_LAYOUT"),
+                                         pol_bayer if pol_bayer is not None else os.environ.get("PD_POL_BAYER"),
+                                         pol_gains if pol_gains is not None else os.environ.get("PD_POL_GAINS"),
+                                         pol_color_scale if pol_color_scale is not None
+                                         else os.environ.get("PD_POL_COLOR_SCALE"))
         self.device = torch.device("cuda")
         self.models = {"rgb_encoder": networks.ShallowResnetEncoder(18, False)}
         if augment_normals:
@@ -79,11 +89,12 @@ class Evaluation:
 
     @torch.no_grad()
     def predict(self, inputs):
-        pdcolor.expand_batch(inputs, (self.height, self.width), 4)      # HAMMER_Dataset(raw_color=True) batches
+        # HAMMER_Dataset(raw_color=True) batches; colour sensor frames are demosaicked here, for polar_inputs too
+        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp)
         # the Trainer's hand-over: interleaved sensor frames (demosaic), un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
         normals = pdpolar.polar_inputs(inputs, (self.height, self.width),
                                        ("xolp", "normals") if self.augment_normals else ("xolp",), self.pol_angles,
-                                       dofp=self.pol_dofp)
+                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp)
         feats = self.models["rgb_encoder"](inputs["color_aug", 0, 0].float())
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None
         nf = self.models["normals_encoder"](inputs["xolp", 0, 0].float(), normals=normals) if self.augment_normals else None

@@ -28,6 +28,16 @@ def main():
         opts.pol_layout = [int(x) for x in os.environ["PD_POL_LAYOUT"].split(",")]
     if os.environ.get("PD_POL_DEMOSAIC"):
         opts.pol_demosaic = os.environ["PD_POL_DEMOSAIC"]
+    # PD_POL_BAYER=RGGB|BGGR|GRBG|GBRG / PD_POL_GAINS="r,g,b" / PD_POL_COLOR_SCALE: colour sensor frames (PD_POL_CDOFP=1 makes
+    # the loader serve them) -- the Bayer order over the polarizer array, white-balance gains and the factor from frame values
+    # to the 0..255 of the colour picture, 255/4095 for 12-bit frames (opt.pol_bayer / opt.pol_gains / opt.pol_color_scale;
+    # defaults: RGGB, none, 1 for 8-bit frames); PD_POL_LAYOUT is shared
+    if os.environ.get("PD_POL_BAYER"):
+        opts.pol_bayer = os.environ["PD_POL_BAYER"]
+    if os.environ.get("PD_POL_GAINS"):
+        opts.pol_gains = [float(x) for x in os.environ["PD_POL_GAINS"].split(",")]
+    if os.environ.get("PD_POL_COLOR_SCALE"):
+        opts.pol_color_scale = float(os.environ["PD_POL_COLOR_SCALE"])
     if int(os.environ.get("WORLD_SIZE", 1)) > 1 and not torch.distributed.is_initialized():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
         torch.distributed.init_process_group("nccl")      # "nccl" is RCCL on ROCm

@@ -32,6 +32,7 @@ from manydepth import datasets, networks
 from polardepth import functional as PF
 from polardepth import polar as pdpolar
 from polardepth import dofp as pddofp
+from polardepth import cdofp as pdcdofp
 from polardepth import color as pdcolor
 from polardepth import ops
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
@@ -120,6 +121,12 @@ class Trainer:
         # super-pixel feeds and how the planes are reconstructed (``opt.pol_layout`` / ``opt.pol_demosaic``; train.py maps
         # PD_POL_LAYOUT / PD_POL_DEMOSAIC onto them).  None = IMX250MZR / bilinear; pol_angles refer to the layout's planes
         self.pol_dofp = pddofp.options(getattr(self.opt, "pol_layout", None), getattr(self.opt, "pol_demosaic", None))
+        # colour sensor frames (("pol_cdofp", 0, 0), HAMMER_Dataset(pol_cdofp=True)): ``opt.pol_layout`` again, the Bayer order,
+        # white-balance gains and the factor to the 0..255 of the colour picture (``opt.pol_bayer`` / ``opt.pol_gains`` /
+        # ``opt.pol_color_scale``; train.py maps PD_POL_BAYER / PD_POL_GAINS / PD_POL_COLOR_SCALE onto them).  None = RGGB, no
+        # gains, scale 1 for 8-bit frames (wider ones need one)
+        self.pol_cdofp = pdcdofp.options(getattr(self.opt, "pol_layout", None), getattr(self.opt, "pol_bayer", None),
+                                         getattr(self.opt, "pol_gains", None), getattr(self.opt, "pol_color_scale", None))
 
         timestamp = datetime.now()
         self.data_path, self.data_path_val, self.log_dir = self.opt.data_path, self.opt.data_path_val, self.opt.log_dir
@@ -313,7 +320,7 @@ class Trainer:
             want = ["xolp"] + (["normals"] if self.opt.augment_normals else [])
         # raw frames from the loader (HAMMER_Dataset(raw_pol=True), uint8 / uint16 / float32) are resized on the device first
         return pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles,
-                                    dofp=self.pol_dofp)
+                                    dofp=self.pol_dofp, cdofp=self.pol_cdofp)
 
     def _forward_models(self, inputs):
         normals = self._polar_inputs(inputs)
@@ -373,7 +380,7 @@ class Trainer:
             inputs[key] = ipt.to(self.device, non_blocking=True)
         # raw frames + jitter rows from the loader (HAMMER_Dataset(raw_color=True)): the colour pyramids on the device,
         # 4 scales like the loaders above; inside the captured step under PD_STEP_GRAPH=1, like the raw_pol resize
-        pdcolor.expand_batch(inputs, (self.opt.height, self.opt.width), 4)
+        pdcolor.expand_batch(inputs, (self.opt.height, self.opt.width), 4, cdofp=self.pol_cdofp)
         if self.train_teacher_and_pose and is_train and self.bf16:
             with _Bf16Step():
                 mono_outputs = self._forward_models(inputs)

@@ -189,7 +189,7 @@ def split_mosaic(mosaic):
     return planes if signed is None else planes.view(mosaic.dtype)
 
 
-def polar_inputs(inputs, size, want, angles=None, dofp=None):
+def polar_inputs(inputs, size, want, angles=None, dofp=None, cdofp=None):
     """The loader's hand-over to K1, shared by Trainer._polar_inputs and Evaluation.predict.  ``inputs`` is a batch on the
     device; size = (height, width) of the network input; want as for ``polar_forward`` (empty: only the split below).
 
@@ -203,7 +203,14 @@ def polar_inputs(inputs, size, want, angles=None, dofp=None):
     An interleaved division-of-focal-plane frame ("pol_dofp", 0, 0) ([B,1,H2,W2] or [B,H2,W2], uint8 / uint16 / float32:
     ``HAMMER_Dataset(pol_dofp=True)``) without ("pol", 0, 0) is demosaicked into ("pol", 0, 0) first
     (``polardepth.dofp.demosaic``); ``dofp = (layout, mode)`` selects how, None = (IMX250MZR, "bilinear").  The planes come
-    out in the order the layout gives them -- the order ``angles`` refers to -- and then take the path above."""
+    out in the order the layout gives them -- the order ``angles`` refers to -- and then take the path above.
+
+    A COLOUR sensor frame ("pol_cdofp", 0, 0) (``HAMMER_Dataset(pol_cdofp=True)``) in a batch with neither ("pol", 0, 0) nor
+    ("color_raw", 0, 0) gives both in one launch (``polardepth.cdofp.expand``; ``cdofp`` = its options, None = the defaults);
+    ``polardepth.color.expand_batch`` makes the same call, and whichever runs first serves the other."""
+    if ("pol_cdofp", 0, 0) in inputs:
+        from . import cdofp as pdcdofp
+        pdcdofp.expand(inputs, cdofp)
     if ("pol_dofp", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
         from . import dofp as pddofp
         layout, mode = (pddofp.IMX250MZR, "bilinear") if dofp is None else dofp

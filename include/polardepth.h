@@ -144,6 +144,46 @@ int pd_polar_general_fwd(const void* pol, int dtype, const double* coef, void* i
                          void* normals, const void* tables, size_t tables_bytes,
                          int B, int H, int W, int Wout, int flags, void* stream);
 
+/* XOLP statistics (csrc/xolp_stats.hip): the DoLP / AoLP distribution of the tensor the network sees, in one read pass on the
+ * device.  Replaces polarisation/xolp_mean_and_std_dev.py:10-32 (np.mean / np.std over a stack of .npy frames, whose output
+ * are the constants of normalizeInput('XOLP')) for any input K1 accepts, and counts what lies outside the zenith tables.
+ *
+ * xolp       fp32 [B,2,H,ld] device, ch0 = DoLP (rho), ch1 = AoLP (phi): what pd_polar_fwd / pd_polar_general_fwd write, or
+ *            any other fp32 tensor.  The first W <= ld columns of a row are data; the ld - W padding columns are never read
+ *            into a statistic (612 -> 640).  ld % 4 == 0; W is arbitrary.
+ * mask       uint8 [B,H,ld] device or NULL; non-zero = the pixel counts
+ * stats      the record below, on the device (PD_XOLP_STATS_BYTES)
+ * workspace  caller-owned, >= pd_xolp_stats_workspace(B, H, W) bytes (monotone in each argument, never 0); scratch
+ * thresholds two finite HOST floats, read during the call: over[i] counts rho > thresholds[i] (strictly greater)
+ * accumulate 0: `stats` is overwritten; otherwise this call's finalised values are added to it (one fp64 add per sum,
+ *            integer adds, min / max), so a whole data set accumulates on the device without a host read
+ *
+ * A pixel is INCLUDED when it is inside W, passes the mask and both its values are finite.  A pixel that fails only the
+ * finiteness test adds 1 to `nonfinite` and to nothing else.  The record, byte offsets:
+ *      0  int64   n             included pixels
+ *      8  int64   nonfinite
+ *     16  int64   over[2]       included pixels with rho > thresholds[0] / thresholds[1]
+ *     32  double  sum_rho, sum_rho2, sum_phi, sum_phi2      over included pixels; every fp32 value is converted to fp64 first
+ *                               (its square is then exact)
+ *     64  float   min_rho, max_rho, min_phi, max_phi        +inf / -inf / +inf / -inf while n == 0
+ *     80  uint64  hist_dolp[257]   k = rho < 0 ? 0 : (rho >= 1 ? 256 : (int)(rho * 256.0f)): 256 bins over [0,1), one for
+ *                               rho >= 1; the product is exact in fp32 and -0.0 lands in bin 0
+ *   2136  uint64  hist_aolp[256]   t = (phi + C1) * C2 in fp32, in that order, C1 = (float)(pi / 2), C2 = (float)(256 / pi);
+ *                               k = t < 0 ? 0 : (t >= 256 ? 255 : (int)t)
+ * The four sums are bit-reproducible from run to run: lanes, waves and workgroups add their partial sums in a fixed order
+ * that depends on the shape only, the per-workgroup partials go through `workspace`, and a second small launch adds them in
+ * index order in fp64 -- no floating-point atomics.  Any order of N exactly converted terms errs by at most
+ * (N - 1) 2^-53 sum|x|.  The integer fields and the extrema do not depend on the order.
+ * B == 0 returns PD_OK (accumulate == 0: writes the empty record).  Two launches per 2^30 tensor elements, no allocation,
+ * copy or synchronisation: the call can be captured into a graph.  Element offsets are 32-bit in the kernel; a batch beyond
+ * 2^30 elements is split by frames on the host, a single frame beyond that is refused ("too large").  Every refusal is
+ * PD_EINVAL with a message, decided before the device is touched: null xolp / stats / workspace, ws_bytes too small,
+ * W > ld, ld % 4 != 0, a pointer that is not 16-byte aligned, non-finite thresholds, bad shape. */
+#define PD_XOLP_STATS_BYTES 4184
+size_t pd_xolp_stats_workspace(int B, int H, int W);
+int pd_xolp_stats(const void* xolp, const void* mask, void* stats, void* workspace, size_t ws_bytes,
+                  int B, int H, int W, int ld, const float thresholds[2], int accumulate, void* stream);
+
 /* ------------------------------------------------------------------------- K2
  * Implicit-GEMM convolution on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
  *

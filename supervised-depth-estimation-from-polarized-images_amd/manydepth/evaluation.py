@@ -22,7 +22,7 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
 class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
-                 pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None):
+                 pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -34,7 +34,9 @@ class Evaluation:
         ``pol_bayer`` / ``pol_gains`` / ``pol_color_scale``: for batches that carry the COLOUR sensor frame ("pol_cdofp", 0, 0)
         -- the Bayer order (or $PD_POL_BAYER), white-balance gains r,g,b (or $PD_POL_GAINS) and the factor to the 0..255 of
         the colour picture (or $PD_POL_COLOR_SCALE; 255 / 4095 for 12-bit frames); ``pol_layout`` is shared.  None = RGGB, no
-        gains, 1 for 8-bit frames."""
+        gains, 1 for 8-bit frames.  ``xolp_norm``: the (mean, std) pair (or "mean,std") that standardises the XOLP encoder's
+        input; None looks at $PD_XOLP_NORM, then at a trainer_state.pth in ``load_weights_folder`` that carries the pair the
+        weights were trained with, and ends at the reference's HAMMER constants."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -53,12 +55,16 @@ class Evaluation:
                                          pol_gains if pol_gains is not None else os.environ.get("PD_POL_GAINS"),
                                          pol_color_scale if pol_color_scale is not None
                                          else os.environ.get("PD_POL_COLOR_SCALE"))
+        self.xolp_norm = pdpolar.parse_xolp_norm(xolp_norm if xolp_norm is not None else os.environ.get("PD_XOLP_NORM"))
+        state_path = os.path.join(load_weights_folder, "trainer_state.pth") if load_weights_folder is not None else None
+        if self.xolp_norm is None and state_path is not None and os.path.isfile(state_path):
+            self.xolp_norm = pdpolar.parse_xolp_norm(torch.load(state_path, map_location="cpu").get("xolp_norm"))
         self.device = torch.device("cuda")
         self.models = {"rgb_encoder": networks.ShallowResnetEncoder(18, False)}
         if augment_normals:
             self.models["normals_encoder"] = networks.ShallowNormalsEncoder(9, 0.0)
         if augment_xolp:
-            self.models["xolp_encoder"] = networks.ShallowEncoder('XOLP', 2, 0.0)
+            self.models["xolp_encoder"] = networks.ShallowEncoder('XOLP', 2, 0.0, xolp_norm=self.xolp_norm)
         self.models["joint_encoder"] = networks.JointEncoder(
             0.0, augment_normals, augment_xolp,
             attention=(os.environ.get("PD_JOINT_ATTENTION") == "1") if joint_attention is None else joint_attention)

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from polardepth import functional as PF
+from polardepth.polar import parse_xolp_norm
 from ..normals_vec import get_normals as _get_normals
 
 XOLP_MEAN, XOLP_STD = 0.08693199701957657, 0.44430732785457433
@@ -58,9 +59,15 @@ class ResidualBlock(nn.Module):
 
 
 class ShallowEncoder(nn.Module):
-    def __init__(self, mode, in_channels=2, dropout_rate=0.5):
+    def __init__(self, mode, in_channels=2, dropout_rate=0.5, xolp_norm=None):
+        """xolp_norm: (mean, std) of normalizeInput for mode 'XOLP' measured on the user's own sensor (polardepth.polar.
+        XolpStats, tools/xolp_stats.py); None = the reference's HAMMER constants (XOLP_MEAN, XOLP_STD).  Not in the reference's
+        constructor, and no state_dict key: the pair travels in the Trainer's options and trainer_state.pth."""
         super().__init__()
         self.in_channels, self.mode = in_channels, mode
+        xolp_norm = parse_xolp_norm(xolp_norm)
+        if xolp_norm is not None and mode != 'XOLP':
+            raise ValueError(f"xolp_norm = {xolp_norm!r} standardises the XOLP input only, not mode {mode!r}")
         self.Conv1 = ConvBlock(in_channels, 64, 7, 'stride2', 3, dropout_rate)
         self.ResBlock1 = ResidualBlock(64, 3, 1, dropout_rate)
         self.Conv2 = ConvBlock(64, 64, 5, 'maxpool', 2, dropout_rate)
@@ -69,7 +76,9 @@ class ShallowEncoder(nn.Module):
         self.ResBlock3 = ResidualBlock(64, 3, 1, dropout_rate)
         # normalizeInput (:75-83) is applied inside Conv1's gather: in-bounds taps become (x-m)/s,
         # padded taps stay 0 -- identical to normalising first and zero-padding after.
-        self.Conv1.in_affine = {'XOLP': (XOLP_MEAN, XOLP_STD), 'RGB': (0.45, 0.225)}.get(mode)
+        # (the pair is a launch constant of the stem's gather, ops.s2d_input / pd_stem_s2d_input: no convolution code differs)
+        self.Conv1.in_affine = {'XOLP': (XOLP_MEAN, XOLP_STD) if xolp_norm is None else xolp_norm,
+                                'RGB': (0.45, 0.225)}.get(mode)
 
     def forward(self, x):
         out = self.Conv1(x.float())

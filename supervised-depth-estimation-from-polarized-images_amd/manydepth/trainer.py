@@ -128,6 +128,11 @@ class Trainer:
         self.pol_cdofp = pdcdofp.options(getattr(self.opt, "pol_layout", None), getattr(self.opt, "pol_bayer", None),
                                          getattr(self.opt, "pol_gains", None), getattr(self.opt, "pol_color_scale", None))
 
+        # the (mean, std) pair that standardises the XOLP encoder's input (``opt.xolp_norm``: a pair or "mean,std"; train.py
+        # maps PD_XOLP_NORM onto it; tools/xolp_stats.py measures it).  None = the reference's HAMMER constants, or the pair
+        # of a loaded checkpoint (load_model).  A launch constant of the stem: the captured step needs nothing
+        self.xolp_norm = pdpolar.parse_xolp_norm(getattr(self.opt, "xolp_norm", None))
+
         timestamp = datetime.now()
         self.data_path, self.data_path_val, self.log_dir = self.opt.data_path, self.opt.data_path_val, self.opt.log_dir
         self.log_path = os.path.join(self.opt.log_dir, self.opt.model_name + '_' + timestamp.strftime("%m-%d_%H-%M-%S"))
@@ -148,7 +153,7 @@ class Trainer:
                                                                             dropout_rate=self.opt.dropout_rate)
         if self.opt.augment_xolp:
             self.models["xolp_encoder"] = networks.ShallowEncoder(mode='XOLP', in_channels=2,
-                                                                  dropout_rate=self.opt.dropout_rate)
+                                                                  dropout_rate=self.opt.dropout_rate, xolp_norm=self.xolp_norm)
         self.models["joint_encoder"] = networks.JointEncoder(dropout_rate=self.opt.dropout_rate,
                                                              include_normals=self.opt.augment_normals,
                                                              include_xolp=self.opt.augment_xolp,
@@ -568,7 +573,9 @@ class Trainer:
             _save({"epoch": self.epoch, "step": self.step, "epoch_complete": bool(epoch_complete),
                    "batch_idx": int(batch_idx), "lr_scheduler": self.model_lr_scheduler.state_dict(),
                    "dropout_seed": PF.DropoutState.seed,
-                   "dropout_step": PF.DropoutState.get_step(getattr(self, "device", None))}, "trainer_state.pth")
+                   "dropout_step": PF.DropoutState.get_step(getattr(self, "device", None)),
+                   "xolp_norm": None if getattr(self, "xolp_norm", None) is None else list(self.xolp_norm)},
+                  "trainer_state.pth")
         if self.distributed:
             torch.distributed.barrier()
 
@@ -600,8 +607,20 @@ class Trainer:
             except (ValueError, KeyError, RuntimeError) as e:
                 print("Can't load Adam - using random ({})".format(e))
         state_path = os.path.join(folder, "trainer_state.pth")
-        if os.path.isfile(state_path) and getattr(self.opt, "resume_state", True):
-            st = torch.load(state_path, map_location="cpu")
+        st = torch.load(state_path, map_location="cpu") if os.path.isfile(state_path) else None
+        if st is not None:
+            # the weights were trained behind the checkpoint's standardisation: adopt it, or refuse a different one
+            theirs = pdpolar.parse_xolp_norm(st.get("xolp_norm"))
+            mine = getattr(self, "xolp_norm", None)
+            if theirs is not None and mine is not None and tuple(theirs) != tuple(mine):
+                raise ValueError(f"xolp_norm = {tuple(mine)!r} is set, but the checkpoint in {folder} was trained with "
+                                 f"{tuple(theirs)!r}: unset the option to adopt the checkpoint's pair")
+            if theirs is not None and mine is None:
+                self.xolp_norm = theirs
+                self.opt.xolp_norm = list(theirs)
+                if "xolp_encoder" in self.models:
+                    self.models["xolp_encoder"].Conv1.in_affine = theirs
+        if st is not None and getattr(self.opt, "resume_state", True):
             if st.get("epoch_complete", True):       # written by train() after run_epoch (scheduler already stepped)
                 self.resume_epoch, self.resume_step, self.resume_batch = int(st["epoch"]) + 1, int(st["step"]), 0
             else:                                    # written inside run_epoch: same epoch, next batch, next step

@@ -37,6 +37,8 @@ SIGNATURES = {
     "pd_polar_calc_normals": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _vp]),
     "pd_polar_fit_matrix": (_i, [_dp, _dp]),
     "pd_polar_general_fwd": (_i, [_vp, _i, _dp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "pd_xolp_stats_workspace": (_sz, [_i, _i, _i]),
+    "pd_xolp_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _c.POINTER(_f), _i, _vp]),
     "pd_conv2d_tile_m": (_i, [_l, _i]),
     "pd_conv2d_stats_rows": (_l, [_l, _i]),
     "pd_conv2d_uses_x3": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u]),

@@ -133,6 +133,10 @@ def polar_forward(pol, n=1.5, mode=MODE_LS, mask=None, want=("xolp",), tables=No
     kernel (pd_polar_general_fwd: fp64 least-squares fit per pixel instead of the look-up tables; ``angles=None`` then means
     0/45/90/135 deg).  It also serves want "iun" ([B,1,H,W], the unpolarised intensity); it has no Stokes mode, mask,
     "ints", ieee_rho or nt_loads (ValueError).  uint8 planes without ``angles`` take K1 exactly as before.
+
+    "xolp_std" is standardised with the reference's HAMMER constants in both kernels, whatever ``xolp_norm`` a
+    ShallowEncoder was given: the kernels' correctly rounded division shortcut was verified exhaustively for those two
+    constants only, and the training path does not use this output (the stem's gather standardises, with the run-time pair).
     """
     if not (isinstance(pol, torch.Tensor) and pol.is_cuda):
         raise RuntimeError("polar_forward needs a CUDA(HIP) uint8 tensor; there is no CPU fallback")
@@ -290,3 +294,126 @@ def calc_normals(phi, theta):
         check(lib.pd_polar_calc_normals(ptr(phi), ptr(theta), ptr(out), B, P, int(phi.dtype == torch.float64),
                                         int(theta.dtype == torch.float64), stream_ptr()), "pd_polar_calc_normals")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ XOLP statistics
+STATS_BYTES = 4184                                # PD_XOLP_STATS_BYTES
+HIST_DOLP_BINS, HIST_AOLP_BINS = 257, 256
+_MASK_DTYPES = (torch.bool, torch.uint8, torch.int32)
+
+
+def parse_xolp_norm(spec):
+    """The (mean, std) pair of ShallowEncoder.normalizeInput('XOLP') from a pair or the string "mean,std" (the form of
+    $PD_XOLP_NORM); None and "" stay None.  ValueError unless mean is finite and std finite and > 0."""
+    if spec is None or (isinstance(spec, str) and not spec.strip()):
+        return None
+    try:
+        vals = [float(x) for x in spec.split(",")] if isinstance(spec, str) else [float(x) for x in spec]
+    except (TypeError, ValueError):
+        vals = []
+    if len(vals) != 2:
+        raise ValueError(f'xolp_norm must be a (mean, std) pair or the string "mean,std", got {spec!r}')
+    mean, std = vals
+    if not (np.isfinite(mean) and np.isfinite(std) and std > 0):
+        raise ValueError(f"xolp_norm needs a finite mean and a finite std > 0, got {spec!r}")
+    return mean, std
+
+
+def format_xolp_norm(pair):
+    """(mean, std) -> the "mean,std" string ``parse_xolp_norm`` reads back to the same two doubles."""
+    return f"{float(pair[0])!r},{float(pair[1])!r}"
+
+
+class XolpStats:
+    """DoLP / AoLP statistics of XOLP tensors, accumulated on the device (pd_xolp_stats): moments, extrema, histograms and
+    the counts of DoLP beyond the zenith tables.  Holds the device record and a grow-on-demand workspace; ``add`` enqueues
+    one call and never synchronises, ``result`` makes the only host read.  n: the refractive index whose diffuse table
+    gives the first threshold."""
+
+    def __init__(self, device, n=1.5):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("XolpStats needs a CUDA(HIP) device; there is no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.thresholds = (float(np.float32(theta_tables_numpy(n)[0][0].max())), 1.0)
+        self._thr = (ctypes.c_float * 2)(*self.thresholds)
+        self._record = torch.empty(STATS_BYTES, dtype=torch.uint8, device=self.device)
+        self._ws = torch.empty(int(lib.pd_xolp_stats_workspace(1, 1, 1)), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def _call(self, xolp, mask, B, H, W, ld, accumulate):
+        need = int(lib.pd_xolp_stats_workspace(B, H, W))
+        if self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib.pd_xolp_stats(ptr(xolp), ptr(mask), ptr(self._record), ptr(self._ws), self._ws.numel(), B, H, W, ld,
+                                    self._thr, accumulate, stream_ptr()), "pd_xolp_stats")
+
+    def reset(self):
+        """Clear the record (an empty batch with accumulate = 0)."""
+        self._call(None, None, 0, 1, 1, 4, 0)
+
+    def add(self, xolp, width=None, mask=None):
+        """Add fp32 ``xolp`` [B,2,H,Wp] (ch0 DoLP, ch1 AoLP; Wp % 4 == 0).  width: the data columns of a padded tensor
+        (612 of 640), None = all.  mask: bool, uint8 or int32, [B,H,Wp] or [B,1,H,Wp]; non-zero = the pixel counts."""
+        if not (isinstance(xolp, torch.Tensor) and xolp.is_cuda):
+            raise RuntimeError("XolpStats.add needs a CUDA(HIP) tensor; there is no CPU fallback")
+        if xolp.dim() != 4 or xolp.shape[1] != 2 or xolp.dtype != torch.float32:
+            raise ValueError(f"xolp must be float32 [B,2,H,W], got {xolp.dtype} {tuple(xolp.shape)}")
+        if xolp.device != self.device:
+            raise ValueError(f"xolp is on {xolp.device}, the record on {self.device}")
+        B, _, H, ld = xolp.shape
+        W = ld if width is None else int(width)
+        if mask is not None:
+            if not (isinstance(mask, torch.Tensor) and mask.is_cuda):
+                raise RuntimeError("XolpStats.add needs the mask on the device")
+            if mask.dim() == 4 and mask.shape[1] == 1:
+                mask = mask[:, 0]
+            if mask.dtype not in _MASK_DTYPES or tuple(mask.shape) != (B, H, ld):
+                raise ValueError(f"mask must be bool, uint8 or int32 [B,H,W] or [B,1,H,W] matching xolp {tuple(xolp.shape)}, "
+                                 f"got {mask.dtype} {tuple(mask.shape)}")
+            mask = (mask if mask.dtype == torch.bool else mask != 0).to(torch.uint8).contiguous()
+        if B == 0 or H == 0 or ld == 0:
+            return self
+        self._call(xolp.contiguous(), mask, B, H, W, ld, 1)
+        return self
+
+    def result(self):
+        """The one host read.  dict: n, nonfinite, dolp_mean / dolp_std / aolp_mean / aolp_std (population std, like
+        ndarray.std(), formed in fp64 from the four sums and n; NaN while n == 0), xolp_mean / xolp_std (the reference's
+        pair, xolp_mean_and_std_dev.py:29-30: the mean of the two channels' values), the extrema, both histograms,
+        frac_over_diffuse / frac_over_one and the two thresholds."""
+        raw = self._record.cpu().numpy()
+        cnt = raw[0:32].view(np.int64)
+        sums = raw[32:64].view(np.float64)
+        ext = raw[64:80].view(np.float32)
+        n = int(cnt[0])
+
+        def moments(s1, s2):
+            if n == 0:
+                return float("nan"), float("nan")
+            mean = float(s1) / n
+            return mean, float(np.sqrt(max(float(s2) / n - mean * mean, 0.0)))
+
+        dolp_mean, dolp_std = moments(sums[0], sums[1])
+        aolp_mean, aolp_std = moments(sums[2], sums[3])
+        frac = lambda c: int(c) / n if n else float("nan")
+        return {
+            "n": n, "nonfinite": int(cnt[1]), "over_diffuse": int(cnt[2]), "over_one": int(cnt[3]),
+            "sums": sums.copy(),
+            "dolp_mean": dolp_mean, "dolp_std": dolp_std, "aolp_mean": aolp_mean, "aolp_std": aolp_std,
+            "xolp_mean": 0.5 * (dolp_mean + aolp_mean), "xolp_std": 0.5 * (dolp_std + aolp_std),
+            "dolp_min": float(ext[0]), "dolp_max": float(ext[1]), "aolp_min": float(ext[2]), "aolp_max": float(ext[3]),
+            "hist_dolp": raw[80:80 + 8 * HIST_DOLP_BINS].view(np.uint64).copy(),
+            "hist_aolp": raw[80 + 8 * HIST_DOLP_BINS:STATS_BYTES].view(np.uint64).copy(),
+            "frac_over_diffuse": frac(cnt[2]), "frac_over_one": frac(cnt[3]),
+            "thresholds": self.thresholds,
+        }
+
+
+def xolp_stats(xolp, width=None, mask=None, n=1.5):
+    """One-shot form of ``XolpStats``: the statistics of one fp32 [B,2,H,Wp] tensor as ``XolpStats.result`` returns them."""
+    if not (isinstance(xolp, torch.Tensor) and xolp.is_cuda):
+        raise RuntimeError("xolp_stats needs a CUDA(HIP) tensor; there is no CPU fallback")
+    return XolpStats(xolp.device, n).add(xolp, width, mask).result()

@@ -659,6 +659,69 @@ int pd_cdofp_demosaic(const void* mosaic, int dtype, const int* layout, const in
                       double color_scale, void* planes, void* color_u8, void* rgb_planes, int B, int H4, int W4,
                       void* stream);
 
+/* ---- super-pixel calibration of DoFP frames (csrc/dofp_cal.hip; Powell & Gruev, "Calibration methods for division-of-focal-
+ * plane polarimeters", Opt. Express 2013): a dark frame plus one 4x4 matrix per 2x2 polarizer cell that maps the four measured
+ * samples to what an ideal cell would have measured.  Not in the reference, which assumes an ideal sensor.  Three calls: the
+ * moments of a stack of frames, the matrices from the moments of a flat-field series behind a rotating linear polarizer, and
+ * dark + matrix applied to incoming frames before pd_dofp_demosaic / pd_cdofp_demosaic (both take float32).
+ * Site of a pixel: s = 2 (y & 1) + (x & 1); cell (i, j) holds rows 2i, 2i+1 and columns 2j, 2j+1.  In a colour frame every
+ * such cell lies under one Bayer colour, so one definition serves both sensors; the matrices are in SITE order, independent
+ * of any layout.  All arithmetic is fp64 in exactly the stated order (no contraction, division as division), rounded once
+ * where a narrower type is stored; tests/dofp_cal_ref.py restates it in NumPy and the results agree bit for bit.
+ * Common: H2, W2 even and >= 2; every base pointer 16-byte aligned (rows need no alignment: W2 = 6 uint8 is fine); frames
+ * beyond 2^30 pixels (or 2^40 in the stack / batch) are refused ("too large": in-frame offsets are 32-bit in the kernels);
+ * every refusal is PD_EINVAL with a message, decided before any launch.  No allocation, copy or synchronisation: all three
+ * calls can be captured into a graph.
+ *
+ * pd_frame_moments
+ * frames   [N][H2][W2] device, contiguous, element type `dtype` (PD_POLAR_U8 / _U16 / _F32), N >= 1
+ * dark     fp32 [H2][W2] device, or NULL (then e = (double)f)
+ * weights  fp64 [N][Q], a DEVICE pointer, Q in 1..4
+ * out      fp64 [Q][H2][W2] device
+ *   out[q][y][x] = (accumulate ? out[q][y][x] : 0) + sum_n w[n][q] * ((double)f[n][y][x] - (double)dark[y][x]),
+ * n ascending, each term formed as e = f - d; t = w * e; acc = acc + t.  A thread owns its pixels and loops over n: there is
+ * no reduction across threads, the result is deterministic by construction.  Q = 1, w = 1 / N, no dark: the mean frame.
+ *
+ * pd_dofp_cal_solve
+ * moments  fp64 [3][H2][W2] device: pd_frame_moments of the flat-field series with w[n] = (1, p cos 2a_n, p sin 2a_n) times
+ *          the relative intensity of frame n (a_n: the polarizer's angle, p: its degree of polarization)
+ * rinv     nine HOST doubles, row-major, finite: the inverse of R1 = sum_n w[n] w[n]^T, divided by the radiometric level
+ * a_nom    twelve HOST doubles [4 sites][3], finite: row s = 1/2 (1, cos 2 theta_s, sin 2 theta_s), theta_s the nominal angle
+ *          of site s
+ * qmin     HOST double, finite
+ * gain     fp32 [H2/2][W2/2][4][4] device; quality fp32 [H2/2][W2/2] device or NULL
+ * Per cell, with m[s][k] = moments[k][2i + (s >> 1)][2j + (s & 1)]:
+ *   A[s][l]  = (m[s][0] rinv[0][l] + m[s][1] rinv[1][l]) + m[s][2] rinv[2][l]              (the cell's analyzer vectors)
+ *   N[k][l]  = ((A[0][k] A[0][l] + A[1][k] A[1][l]) + A[2][k] A[2][l]) + A[3][k] A[3][l]   for k <= l, mirrored
+ *   C00 = N11 N22 - N12 N12   C01 = N02 N12 - N01 N22   C02 = N01 N12 - N02 N11
+ *   C11 = N00 N22 - N02 N02   C12 = N01 N02 - N00 N12   C22 = N00 N11 - N01 N01            (C symmetric)
+ *   det = (N00 C00 + N01 C01) + N02 C02;   V[k][l] = C[k][l] / det
+ *   P[k][s]  = (V[k][0] A[s][0] + V[k][1] A[s][1]) + V[k][2] A[s][2]                       (the pseudo-inverse of A)
+ *   G[t][s]  = (a_nom[t][0] P[0][s] + a_nom[t][1] P[1][s]) + a_nom[t][2] P[2][s], stored as fp32
+ *   q        = det / ((N00 * N11) * N22)      (Hadamard's ratio: 1 for the nominal cell, 0 or NaN for a cell that cannot see
+ *              three Stokes components, such as one with two dead sites)
+ * If !(q >= qmin) the cell's G is the 4x4 identity and its quality 0; otherwise quality is (float)q.  G has rank 3 by design
+ * (a_nom . pinv(A)): a cell with ONE dead site still gets a valid G that rebuilds the dead sample from the other three.
+ *
+ * pd_dofp_calibrate
+ * mosaic   [B][H2][W2] device, contiguous, element type `dtype`;  dark fp32 [H2][W2] device or NULL (then e = (double)m)
+ * gain     PD_DOFP_CAL_CELL: fp32 [H2/2][W2/2][4][4] as above; PD_DOFP_CAL_PIXEL: fp32 [H2][W2], the classical flat-field
+ *          gain (the diagonal case)
+ * out      fp32 [B][H2][W2] device
+ * With e_s = (double)m - (double)dark at site s of the cell:
+ *   CELL:  the sample at site t becomes fp32(((G[t][0] e_0 + G[t][1] e_1) + G[t][2] e_2) + G[t][3] e_3)
+ *   PIXEL: fp32((double)g * e)
+ * No clamping (a dark-subtracted sample may be negative); NaN and infinity reach exactly the outputs whose sum holds them; a
+ * zero matrix entry still multiplies.  B == 0 returns 0 before anything is looked at. */
+#define PD_DOFP_CAL_CELL 0
+#define PD_DOFP_CAL_PIXEL 1
+int pd_frame_moments(const void* frames, int dtype, const void* dark, const double* weights, double* out, int N, int Q,
+                     int H2, int W2, int accumulate, void* stream);
+int pd_dofp_cal_solve(const double* moments, const double* rinv, const double* a_nom, double qmin, float* gain,
+                      float* quality, int H2, int W2, void* stream);
+int pd_dofp_calibrate(const void* mosaic, int dtype, const void* dark, const void* gain, int gain_kind, void* out, int B,
+                      int H2, int W2, void* stream);
+
 /* ---- torchvision 0.8.2's PIL ColorJitter on uint8 planar RGB, Pillow-exact, fused with the loader's uint8 -> fp32 / 255
  * (indoor_dataset.py:92-106, 192-233, 404-407; csrc/color.hip, arithmetic in csrc/color_math.hpp).
  * src [B][3][H][W] uint8 (what pd_resize_u8_pass leaves for a [B,3,.,.] input), any H, W >= 1.

@@ -12,6 +12,7 @@ from polardepth import ops
 from polardepth import polar as pdpolar
 from polardepth import dofp as pddofp
 from polardepth import cdofp as pdcdofp
+from polardepth import calibration as pdcal
 from polardepth import color as pdcolor
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -22,7 +23,8 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
 class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
-                 pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None):
+                 pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
+                 pol_calibration=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -36,7 +38,9 @@ class Evaluation:
         the colour picture (or $PD_POL_COLOR_SCALE; 255 / 4095 for 12-bit frames); ``pol_layout`` is shared.  None = RGGB, no
         gains, 1 for 8-bit frames.  ``xolp_norm``: the (mean, std) pair (or "mean,std") that standardises the XOLP encoder's
         input; None looks at $PD_XOLP_NORM, then at a trainer_state.pth in ``load_weights_folder`` that carries the pair the
-        weights were trained with, and ends at the reference's HAMMER constants."""
+        weights were trained with, and ends at the reference's HAMMER constants.  ``pol_calibration``: the sensor's super-pixel
+        calibration (a ``polardepth.calibration.Calibration`` or the path of a saved one, or $PD_POL_CALIBRATION), applied to
+        both kinds of sensor frame before their demosaic; its layout must be ``pol_layout``.  None = none."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -56,6 +60,11 @@ class Evaluation:
                                          pol_color_scale if pol_color_scale is not None
                                          else os.environ.get("PD_POL_COLOR_SCALE"))
         self.xolp_norm = pdpolar.parse_xolp_norm(xolp_norm if xolp_norm is not None else os.environ.get("PD_XOLP_NORM"))
+        self.pol_calibration = pdcal.parse(pol_calibration if pol_calibration is not None
+                                           else os.environ.get("PD_POL_CALIBRATION"), torch.device("cuda"))
+        if self.pol_calibration is not None and tuple(self.pol_calibration.layout) != tuple(self.pol_dofp[0]):
+            raise ValueError(f"pol_calibration was fitted for the layout {tuple(self.pol_calibration.layout)}, pol_layout is "
+                             f"{tuple(self.pol_dofp[0])}")
         state_path = os.path.join(load_weights_folder, "trainer_state.pth") if load_weights_folder is not None else None
         if self.xolp_norm is None and state_path is not None and os.path.isfile(state_path):
             self.xolp_norm = pdpolar.parse_xolp_norm(torch.load(state_path, map_location="cpu").get("xolp_norm"))
@@ -83,6 +92,8 @@ class Evaluation:
                 raise FileNotFoundError("splits/HAMMER_unseen/test_files.txt not found (evaluation.py:96)")
             files = []
         ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0], 4, is_train=False)
+        if self.pol_calibration is not None:                  # a calibration of another frame size is refused here, not in predict
+            pdcal.check_dataset(self.pol_calibration, ds, "the test loader")
         self.test_loader = DataLoader(ds, batch_size, False, num_workers=num_workers, drop_last=True)
 
     def load_mono_model(self):
@@ -96,11 +107,11 @@ class Evaluation:
     @torch.no_grad()
     def predict(self, inputs):
         # HAMMER_Dataset(raw_color=True) batches; colour sensor frames are demosaicked here, for polar_inputs too
-        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp)
+        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
         # the Trainer's hand-over: interleaved sensor frames (demosaic), un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
         normals = pdpolar.polar_inputs(inputs, (self.height, self.width),
                                        ("xolp", "normals") if self.augment_normals else ("xolp",), self.pol_angles,
-                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp)
+                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
         feats = self.models["rgb_encoder"](inputs["color_aug", 0, 0].float())
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None
         nf = self.models["normals_encoder"](inputs["xolp", 0, 0].float(), normals=normals) if self.augment_normals else None

@@ -38,6 +38,10 @@ def options_from_environment(opts, env=os.environ):
         opts.pol_gains = [float(x) for x in env["PD_POL_GAINS"].split(",")]
     if env.get("PD_POL_COLOR_SCALE"):
         opts.pol_color_scale = float(env["PD_POL_COLOR_SCALE"])
+    # PD_POL_CALIBRATION=cal.npz: the sensor's super-pixel calibration (tools/dofp_calibrate.py writes it), applied to
+    # ("pol_dofp", 0, 0) / ("pol_cdofp", 0, 0) frames on the device before their demosaic (opt.pol_calibration; default: none)
+    if env.get("PD_POL_CALIBRATION"):
+        opts.pol_calibration = env["PD_POL_CALIBRATION"]
     # PD_XOLP_NORM="mean,std": the pair that standardises the XOLP encoder's input, measured on the user's own data by
     # tools/xolp_stats.py (opt.xolp_norm; default: the reference's HAMMER constants, or a loaded checkpoint's pair)
     if env.get("PD_XOLP_NORM"):

@@ -20,6 +20,7 @@ import json
 import logging
 import os
 import time
+import warnings
 from datetime import datetime
 
 import numpy as np
@@ -33,6 +34,7 @@ from polardepth import functional as PF
 from polardepth import polar as pdpolar
 from polardepth import dofp as pddofp
 from polardepth import cdofp as pdcdofp
+from polardepth import calibration as pdcal
 from polardepth import color as pdcolor
 from polardepth import ops
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
@@ -127,6 +129,14 @@ class Trainer:
         # gains, scale 1 for 8-bit frames (wider ones need one)
         self.pol_cdofp = pdcdofp.options(getattr(self.opt, "pol_layout", None), getattr(self.opt, "pol_bayer", None),
                                          getattr(self.opt, "pol_gains", None), getattr(self.opt, "pol_color_scale", None))
+        # the sensor's super-pixel calibration (``opt.pol_calibration``: the path of a saved ``polardepth.calibration.Calibration``
+        # or the object; train.py maps PD_POL_CALIBRATION onto it): loaded once to this device and applied to ("pol_dofp", 0, 0)
+        # / ("pol_cdofp", 0, 0) frames before their demosaic, inside the captured step too.  None = frames are taken as they
+        # come.  Its matrices are in site order, but its nominal cell must be the one ``opt.pol_layout`` names
+        self.pol_calibration = pdcal.parse(getattr(self.opt, "pol_calibration", None), self.device)
+        if self.pol_calibration is not None and tuple(self.pol_calibration.layout) != tuple(self.pol_dofp[0]):
+            raise ValueError(f"opt.pol_calibration was fitted for the layout {tuple(self.pol_calibration.layout)}, "
+                             f"opt.pol_layout is {tuple(self.pol_dofp[0])}")
 
         # the (mean, std) pair that standardises the XOLP encoder's input (``opt.xolp_norm``: a pair or "mean,std"; train.py
         # maps PD_XOLP_NORM onto it; tools/xolp_stats.py measures it).  None = the reference's HAMMER constants, or the pair
@@ -208,6 +218,8 @@ class Trainer:
                                                   depth_modality=self.opt.depth_modality)
         train_dataset, val_dataset, test_dataset = mk(self.data_path, train_files, True), \
             mk(self.data_path, val_files, False), mk(self.data_path_val, test_files, False)
+        if self.pol_calibration is not None:
+            self._check_calibration((("training", train_dataset), ("validation", val_dataset), ("test", test_dataset)))
         sampler = torch.utils.data.distributed.DistributedSampler(train_dataset) if self.distributed else None
         self.train_loader = DataLoader(train_dataset, self.opt.batch_size, sampler is None, sampler=sampler,
                                        num_workers=self.opt.num_workers, pin_memory=True, drop_last=True)
@@ -256,6 +268,15 @@ class Trainer:
         logging.info('Run started at: %s', str(timestamp))
         for arg, value in sorted(vars(self.opt).items()):
             logging.info("%s: %r", arg, value)
+
+    def _check_calibration(self, datasets):
+        """A calibration serves one sensor: the first sensor frame of the training, validation and test loaders must have its
+        size (``polardepth.calibration.check_dataset``).  Loaders that serve no sensor frames make the option idle: one
+        warning."""
+        served = [pdcal.check_dataset(self.pol_calibration, ds, f"the {name} loader") for name, ds in datasets]
+        if not any(served):
+            warnings.warn('opt.pol_calibration is set, but the loaders serve no ("pol_dofp", 0, 0) / ("pol_cdofp", 0, 0) frames '
+                          "(PD_POL_DOFP / PD_POL_CDOFP): it applies only to batches that carry one")
 
     def set_train(self):
         for m in self.models.values():
@@ -325,7 +346,7 @@ class Trainer:
             want = ["xolp"] + (["normals"] if self.opt.augment_normals else [])
         # raw frames from the loader (HAMMER_Dataset(raw_pol=True), uint8 / uint16 / float32) are resized on the device first
         return pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles,
-                                    dofp=self.pol_dofp, cdofp=self.pol_cdofp)
+                                    dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
 
     def _forward_models(self, inputs):
         normals = self._polar_inputs(inputs)
@@ -376,7 +397,7 @@ class Trainer:
 
     def _encoder_stream(self, i):
         while len(self._enc_streams) <= i:
-            self._enc_streams.append(torch.cuda.Stream(device=self.device))
+            self._enc_streams.append(PF.side_stream(self.device, self._enc_streams + [torch.cuda.current_stream(self.device)]))
             PF.register_producer_stream(self._enc_streams[-1])      # the gradient reducer / Adam wait for it too
         return self._enc_streams[i]
 
@@ -385,7 +406,8 @@ class Trainer:
             inputs[key] = ipt.to(self.device, non_blocking=True)
         # raw frames + jitter rows from the loader (HAMMER_Dataset(raw_color=True)): the colour pyramids on the device,
         # 4 scales like the loaders above; inside the captured step under PD_STEP_GRAPH=1, like the raw_pol resize
-        pdcolor.expand_batch(inputs, (self.opt.height, self.opt.width), 4, cdofp=self.pol_cdofp)
+        pdcolor.expand_batch(inputs, (self.opt.height, self.opt.width), 4, cdofp=self.pol_cdofp,
+                             calibration=self.pol_calibration)
         if self.train_teacher_and_pose and is_train and self.bf16:
             with _Bf16Step():
                 mono_outputs = self._forward_models(inputs)
@@ -551,7 +573,10 @@ class Trainer:
         models_dir = os.path.join(self.log_path, "models")
         os.makedirs(models_dir, exist_ok=True)
         with open(os.path.join(models_dir, 'opt.json'), 'w') as f:
-            json.dump(self.opt.__dict__.copy(), f, indent=2)
+            to_save = self.opt.__dict__.copy()
+            if not isinstance(to_save.get("pol_calibration"), (str, type(None))):      # the calibration travels as its path only
+                to_save["pol_calibration"] = None
+            json.dump(to_save, f, indent=2)
 
     def save_model(self, epoch_complete=True, batch_idx=-1):
         """trainer.py:1597-1617 layout (<model>.pth + adam.pth) plus trainer_state.pth.  Only rank 0 writes; every file

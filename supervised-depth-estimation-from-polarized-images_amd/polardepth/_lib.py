@@ -111,6 +111,9 @@ SIGNATURES = {
     "pd_resize_wide_pass": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pd_dofp_demosaic": (_i, [_vp, _i, _vp, _i, _ip, _i, _i, _i, _vp]),
     "pd_cdofp_demosaic": (_i, [_vp, _i, _ip, _ip, _dp, _dbl, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "pd_frame_moments": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "pd_dofp_cal_solve": (_i, [_vp, _dp, _dp, _dbl, _vp, _vp, _i, _i, _vp]),
+    "pd_dofp_calibrate": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "pd_color_jitter_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pd_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pd_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),

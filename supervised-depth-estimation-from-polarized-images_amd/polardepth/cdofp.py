@@ -110,13 +110,22 @@ def demosaic(mosaic, layout=IMX250MYR_POL, bayer=RGGB, gains=None, color_scale=N
     return out
 
 
-def expand(inputs, opts=None):
+def expand(inputs, opts=None, calibration=None):
     """A batch that carries the colour sensor frame ("pol_cdofp", 0, 0) (``HAMMER_Dataset(pol_cdofp=True)``) and neither
     ("pol", 0, 0) nor ("color_raw", 0, 0) gets both from ONE demosaic call; anything else is left as it is, so a second call
-    does nothing.  ``opts``: what ``options`` returns, None = its defaults."""
+    does nothing.  ``opts``: what ``options`` returns, None = its defaults.  ``calibration``
+    (``polardepth.calibration.Calibration``): the frame is calibrated first (every 2x2 polarizer cell lies under one Bayer
+    colour, so the same per-cell matrices serve); the calibration keeps the raw frame's level, so ``color_scale`` keeps
+    referring to the raw scale, and None still means 1 for a uint8 frame."""
     if KEY in inputs and ("pol", 0, 0) not in inputs and ("color_raw", 0, 0) not in inputs:
         layout, bayer, gains, color_scale = options() if opts is None else opts
-        out = demosaic(inputs[KEY], layout, bayer, gains, color_scale, want=("planes", "color"))
+        frame = inputs[KEY]
+        if calibration is not None:
+            from . import calibration as pdcal
+            if color_scale is None and frame.dtype == torch.uint8:
+                color_scale = 1.0
+            frame = pdcal.apply(frame, calibration)
+        out = demosaic(frame, layout, bayer, gains, color_scale, want=("planes", "color"))
         inputs[("pol", 0, 0)] = out["planes"]
         inputs[("color_raw", 0, 0)] = out["color"]
     return inputs

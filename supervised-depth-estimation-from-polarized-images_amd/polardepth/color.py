@@ -86,14 +86,15 @@ def color_pyramid(raw_u8, jitter, size, num_scales=4):
     return out
 
 
-def expand_batch(inputs, size, num_scales=4, cdofp=None):
+def expand_batch(inputs, size, num_scales=4, cdofp=None, calibration=None):
     """What Trainer.process_batch / Evaluation.predict do with a raw-colour batch (HAMMER_Dataset(raw_color=True)): when
     ("color_raw", 0, 0) is there and ("color", 0, 0) is not, add the eight pyramid tensors to ``inputs``.  A colour sensor
     frame ("pol_cdofp", 0, 0) is demosaicked into ("color_raw", 0, 0) and ("pol", 0, 0) first (``polardepth.cdofp.expand``,
-    ``cdofp`` = its options): one launch, shared with ``polardepth.polar.polar_inputs``."""
+    ``cdofp`` = its options, ``calibration`` = the sensor's ``polardepth.calibration.Calibration``, applied before the
+    demosaic): one launch, shared with ``polardepth.polar.polar_inputs``."""
     if ("pol_cdofp", 0, 0) in inputs:
         from . import cdofp as pdcdofp
-        pdcdofp.expand(inputs, cdofp)
+        pdcdofp.expand(inputs, cdofp, calibration=calibration)
     if ("color_raw", 0, 0) in inputs and ("color", 0, 0) not in inputs:
         inputs.update(color_pyramid(inputs[("color_raw", 0, 0)], inputs.get("color_jitter"), size, num_scales))
     return inputs

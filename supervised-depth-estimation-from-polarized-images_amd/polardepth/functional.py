@@ -86,10 +86,26 @@ USE_DISP_HEADS = os.environ.get("PD_DISP_HEADS", "1") != "0"     # direct kernel
 USE_S2D_STEMS = os.environ.get("PD_S2D_STEMS", "1") == "1"
 
 
+def side_stream(device, taken=()):
+    """A stream for side work that is none of ``taken``, of the weight-gradient / attention streams or of the stream graphs are
+    captured on.  torch hands out its 32 pool streams per device round-robin, so a process that has built several Trainers is
+    given a stream it already uses for something else: the overlap is lost, and a stream that waits for ITSELF while it is
+    forked into a capture makes hipStreamEndCapture crash (seen when an encoder stream was the weight-gradient stream)."""
+    device = torch.device(device)
+    taken = list(taken) + list(_WGRAD_STREAMS.values()) + list(_ATTN_STREAMS.values())
+    if torch.cuda.graph.default_capture_stream is not None:
+        taken.append(torch.cuda.graph.default_capture_stream)
+    for _ in range(32):                           # one round of the pool
+        st = torch.cuda.Stream(device=device)
+        if all(st != q for q in taken):
+            return st
+    raise RuntimeError(f"side_stream: all of torch's pool streams on {device} are among the {len(taken)} streams to avoid")
+
+
 def wgrad_stream(device):
     st = _WGRAD_STREAMS.get(device.index)
     if st is None:
-        st = torch.cuda.Stream(device=device)
+        st = side_stream(device)
         _WGRAD_STREAMS[device.index] = st
     return st
 
@@ -102,7 +118,7 @@ def _attn_side_stream(device):
     earlier kernels, which would delay the join)."""
     st = _ATTN_STREAMS.get(device.index)
     if st is None:
-        st = _ATTN_STREAMS[device.index] = torch.cuda.Stream(device=device)
+        st = _ATTN_STREAMS[device.index] = side_stream(device)
     return st
 
 
@@ -144,6 +160,9 @@ def _wgrad_async(x, dz, fn):
         torch.autograd.Variable._execution_engine.queue_callback(_join_after_backward)
         _join_queued = True
     side = wgrad_stream(dz.device)
+    if side == torch.cuda.current_stream():       # already there: no wait of a stream for itself (see side_stream)
+        fn()
+        return
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         fn()

@@ -193,7 +193,7 @@ def split_mosaic(mosaic):
     return planes if signed is None else planes.view(mosaic.dtype)
 
 
-def polar_inputs(inputs, size, want, angles=None, dofp=None, cdofp=None):
+def polar_inputs(inputs, size, want, angles=None, dofp=None, cdofp=None, calibration=None):
     """The loader's hand-over to K1, shared by Trainer._polar_inputs and Evaluation.predict.  ``inputs`` is a batch on the
     device; size = (height, width) of the network input; want as for ``polar_forward`` (empty: only the split below).
 
@@ -211,14 +211,22 @@ def polar_inputs(inputs, size, want, angles=None, dofp=None, cdofp=None):
 
     A COLOUR sensor frame ("pol_cdofp", 0, 0) (``HAMMER_Dataset(pol_cdofp=True)``) in a batch with neither ("pol", 0, 0) nor
     ("color_raw", 0, 0) gives both in one launch (``polardepth.cdofp.expand``; ``cdofp`` = its options, None = the defaults);
-    ``polardepth.color.expand_batch`` makes the same call, and whichever runs first serves the other."""
+    ``polardepth.color.expand_batch`` makes the same call, and whichever runs first serves the other.
+
+    ``calibration`` (a ``polardepth.calibration.Calibration`` on the batch's device): both kinds of sensor frame are
+    calibrated -- dark subtracted, every 2x2 polarizer cell multiplied by its matrix -- BEFORE their demosaic, which then
+    takes the float32 frame.  None: nothing changes.  Batches without a sensor frame ignore it."""
     if ("pol_cdofp", 0, 0) in inputs:
         from . import cdofp as pdcdofp
-        pdcdofp.expand(inputs, cdofp)
+        pdcdofp.expand(inputs, cdofp, calibration=calibration)
     if ("pol_dofp", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
         from . import dofp as pddofp
         layout, mode = (pddofp.IMX250MZR, "bilinear") if dofp is None else dofp
-        inputs[("pol", 0, 0)] = pddofp.demosaic(inputs[("pol_dofp", 0, 0)], layout, mode)
+        frame = inputs[("pol_dofp", 0, 0)]
+        if calibration is not None:
+            from . import calibration as pdcal
+            frame = pdcal.apply(frame, calibration)
+        inputs[("pol", 0, 0)] = pddofp.demosaic(frame, layout, mode)
     if ("pol_mosaic", 0, 0) in inputs and ("pol", 0, 0) not in inputs:
         inputs[("pol", 0, 0)] = split_mosaic(inputs[("pol_mosaic", 0, 0)])
     if not want or ("pol", 0, 0) not in inputs:

@@ -7,7 +7,8 @@ reference's polarisation/xolp_mean_and_std_dev.py printed for 46 HAMMER frames, 
 Builds HAMMER_Dataset the way the Trainer does and hands every batch to ``polardepth.polar.polar_inputs`` exactly as
 Trainer.process_batch does, so the loader switches (PD_POL_NATIVE, PD_DEVICE_RESIZE, PD_POL_DOFP, PD_POL_CDOFP, read by the
 data set) and the options manydepth/train.py reads (PD_POL_ANGLES, PD_POL_LAYOUT, PD_POL_DEMOSAIC, PD_POL_BAYER, PD_POL_GAINS,
-PD_POL_COLOR_SCALE) apply unchanged.  Prints the reference's six lines, the share of pixels whose DoLP lies beyond the diffuse
+PD_POL_COLOR_SCALE) apply unchanged; ``--pol_calibration cal.npz`` (or PD_POL_CALIBRATION) applies the sensor's super-pixel
+calibration to sensor frames before their demosaic, as ``opt.pol_calibration`` does.  Prints the reference's six lines, the share of pixels whose DoLP lies beyond the diffuse
 zenith table and beyond 1 (a wrong layout, wrong angles, a wrong colour scale or a saturating sensor show up here first), the
 non-finite count and a ready-to-paste PD_XOLP_NORM.  The statistics accumulate on the device; the one host read is at the end.
 
@@ -59,6 +60,10 @@ def measure(args):
         raise RuntimeError("tools/xolp_stats.py needs the GPU; there is no CPU fallback")
     device = torch.device("cuda")
     angles, dofp_opts, cdofp_opts = options_from_env()
+    from polardepth import calibration as pdcal
+    cal = pdcal.parse(args.pol_calibration or os.environ.get("PD_POL_CALIBRATION") or None, device)
+    if cal is not None and tuple(cal.layout) != tuple(dofp_opts[0]):
+        raise ValueError(f"--pol_calibration was fitted for the layout {tuple(cal.layout)}, PD_POL_LAYOUT is {tuple(dofp_opts[0])}")
     ds = datasets.HAMMER_Dataset(args.data_path, split_files(args.data_path, args.split), args.height, args.width, [0], 4,
                                  is_train=False)
     if args.every > 1:
@@ -70,7 +75,8 @@ def measure(args):
         if args.batches and i >= args.batches:
             break
         inputs = {k: v.to(device, non_blocking=True) for k, v in inputs.items()}
-        polar.polar_inputs(inputs, (args.height, args.width), ("xolp",), angles, dofp=dofp_opts, cdofp=cdofp_opts)
+        polar.polar_inputs(inputs, (args.height, args.width), ("xolp",), angles, dofp=dofp_opts, cdofp=cdofp_opts,
+                           calibration=cal)
         if ("xolp", 0, 0) not in inputs:
             raise KeyError('the loader served neither polarizer planes nor ("xolp", 0, 0)')
         xolp = inputs[("xolp", 0, 0)]
@@ -192,6 +198,7 @@ def main(argv=None):
     ap.add_argument("--num_workers", type=int, default=0)
     ap.add_argument("--every", type=int, default=1, help="take every N-th item")
     ap.add_argument("--batches", type=int, default=0, help="stop after this many batches (0: the whole split)")
+    ap.add_argument("--pol_calibration", default=None, help="a calibration file of tools/dofp_calibrate.py (or $PD_POL_CALIBRATION)")
     ap.add_argument("--json", default=None, help="write the result to this file")
     ap.add_argument("--hist", action="store_true", help="print coarse histograms")
     ap.add_argument("--time", action="store_true", help="measure instead (see the head of this file)")

@@ -567,6 +567,62 @@ int pd_ssim_bwd(const void* x, const void* y, const void* gout, void* coef_ws, v
 int pd_depth_metrics(const void* gt, const void* pred, const void* mask, int mask_value, void* partial_ws,
                      void* metrics, int N, long P, float min_depth, float max_depth, void* stream);
 
+/* Surface-normal accuracy per pixel class (csrc/normals_stats.hip): the angular error of predicted normals against the
+ * normals of the ground-truth depth, for K classes of the instance mask at once, in one read of the batch.  The reference
+ * stops at depth (evaluation.py:120-288); this is the standard normals report (mean / median / RMS angle, share of pixels
+ * within 11.25 / 22.5 / 30 degrees) as per-image, per-class records from which all of these follow.
+ *
+ * pred       fp32 device, pixel-major, pixel stride ld >= 3 floats (x, y, z first): ld = 3 is a channels-last [N,3,H,W]
+ *            tensor, ld = 4 what pd_gt_normals writes.  Need not be unit length.
+ * gtn        fp32 [N,H,W,4] from pd_gt_normals
+ * gt         fp32 [N,H,W] ground-truth depth
+ * mask       int32 [N,H,W] or NULL
+ * classes    HOST int[K][2], read during the call and passed as kernel arguments; 1 <= K <= PD_NSTAT_MAX_CLASSES.  Class k
+ *            holds the pixels with lo <= mask <= hi (evaluation.py:242-267: mask_gt >= thres1 & mask_gt <= thres2);
+ *            lo > hi = every pixel.  A pixel may be in several classes.
+ * cos_edges  DEVICE double[719], cos_edges[j-1] = cos(j * 0.25 degrees) for j = 1 .. 719, strictly decreasing.  The caller
+ *            supplies it, so that whoever checks a histogram bins against the same 719 doubles whatever libm built them.
+ * gate       0: the pixel's depth gt is inside [min_depth, max_depth] (>=, <=: the gate of pd_gt_normals).  1: all nine
+ *            depths of the replicate-clamped 3x3 window are -- the Sobel normal of a pixel beside a hole of the depth map
+ *            is an artefact of the hole.
+ * err_deg    NULL, or fp32 [N,H,W]: the angle in degrees where the pixel passes the gate and is valid (below), NaN
+ *            elsewhere, whatever its class
+ * stats      [N][K] records on the device, written whole by every call; byte offsets:
+ *      0  int64   n          valid pixels of the class
+ *      8  int64   bad        pixels of the class that pass the gate but are not valid
+ *     16  double  sum_deg    sum of the angle in degrees over the valid pixels
+ *     24  double  sum_deg2   sum of its square
+ *     32  uint32  hist[720]  0.25-degree bins over [0, 180]
+ * workspace  caller-owned, >= pd_normals_stats_workspace(N, H, W, K) bytes (monotone in each argument, never 0, a multiple
+ *            of 16); scratch
+ *
+ * Per pixel that passes the gate, every fp32 component converted to fp64 first (all products are then exact), in this order:
+ *     d  = (px gx + py gy) + pz gz,   a2 = (px px + py py) + pz pz,   b2 = (gx gx + gy gy) + gz gz,
+ *     c  = d / (sqrt(a2) sqrt(b2)).
+ * The pixel is VALID when a2 > 0, b2 > 0 and c is finite; otherwise it adds 1 to `bad` of each of its classes and to nothing
+ * else (a NaN or zero prediction is counted, not averaged).  For a valid pixel c is clamped to [-1, 1]; its bin is
+ * #{ j : c <= cos_edges[j-1] }, found by binary search -- no acos takes part in a bin decision; exactly parallel normals
+ * land in bin 0, exactly orthogonal ones in bin 360, antiparallel ones in bin 719.  theta = acos(c) * 57.29577951308232 is
+ * added to sum_deg and theta * theta to sum_deg2 of each of its classes.
+ * n, bad and hist are integer sums and do not depend on any order (LDS atomics, then one global add per non-empty bin per
+ * workgroup).  The two fp64 sums are bit-reproducible from run to run: lanes, waves and workgroups add in an order fixed by
+ * the shape, per-workgroup partials go through `workspace`, and a small last launch adds them in index order -- the scheme
+ * of pd_xolp_stats; no floating-point atomics, no cross-workgroup ticket.  Any order of n exactly converted terms errs by at
+ * most (n - 1) 2^-53 of the sum.
+ * Three launches per 2^20 images, no allocation, copy or synchronisation: the call can be captured into a graph.  Offsets
+ * inside a frame are 32-bit; a frame beyond 2^30 pixels is refused ("too large").  N == 0 returns PD_OK.  Every refusal is
+ * PD_EINVAL with a message, decided before the device is touched: a null pred / gtn / gt / classes / cos_edges / stats /
+ * workspace, ws_bytes too small, K outside 1 .. 16, a ranged class with mask == NULL, ld < 3, gate not 0 or 1, gtn / stats /
+ * workspace not 16-byte aligned, bad shape. */
+#define PD_NSTAT_BINS         720      /* 0.25 degree bins over [0, 180] */
+#define PD_NSTAT_MAX_CLASSES  16
+#define PD_NSTAT_RECORD_BYTES 2912     /* 32 + 4 * 720 */
+size_t pd_normals_stats_workspace(int N, int H, int W, int K);
+int pd_normals_stats(const void* pred, long ld, const void* gtn, const void* gt, const void* mask,
+                     const int* classes, int K, const void* cos_edges, int gate, void* err_deg,
+                     void* stats, void* workspace, size_t ws_bytes, int N, int H, int W,
+                     float min_depth, float max_depth, void* stream);
+
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward
  * dp[r][:] <- scale * p * (dp - sum(dp * p)).  The score GEMMs (Q K^T, P V and their gradients) are pd_conv2d /

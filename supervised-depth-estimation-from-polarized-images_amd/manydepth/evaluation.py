@@ -14,6 +14,7 @@ from polardepth import dofp as pddofp
 from polardepth import cdofp as pdcdofp
 from polardepth import calibration as pdcal
 from polardepth import color as pdcolor
+from polardepth import normals_eval
 from polardepth._lib import lib, check, ptr, stream_ptr
 
 _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, "teapot": 120, "cutlery": 140,
@@ -24,7 +25,7 @@ class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
-                 pol_calibration=None):
+                 pol_calibration=None, normals_decoder=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -40,7 +41,9 @@ class Evaluation:
         input; None looks at $PD_XOLP_NORM, then at a trainer_state.pth in ``load_weights_folder`` that carries the pair the
         weights were trained with, and ends at the reference's HAMMER constants.  ``pol_calibration``: the sensor's super-pixel
         calibration (a ``polardepth.calibration.Calibration`` or the path of a saved one, or $PD_POL_CALIBRATION), applied to
-        both kinds of sensor frame before their demosaic; its layout must be ``pol_layout``.  None = none."""
+        both kinds of sensor frame before their demosaic; its layout must be ``pol_layout``.  None = none.  ``normals_decoder``:
+        build the `arch1++_separate_normals_dec` variant's NormalsDecoder behind the normals encoder (``predict_all``,
+        ``test_normals``); None reads $PD_NORMALS_DECODER == "1", as the Trainer does."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -78,6 +81,10 @@ class Evaluation:
             0.0, augment_normals, augment_xolp,
             attention=(os.environ.get("PD_JOINT_ATTENTION") == "1") if joint_attention is None else joint_attention)
         self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.scales)
+        if (os.environ.get("PD_NORMALS_DECODER") == "1") if normals_decoder is None else normals_decoder:
+            if not augment_normals:
+                raise ValueError("the separate normals decoder sits behind the normals encoder: it needs augment_normals")
+            self.models["normals_decoder"] = networks.NormalsDecoder(64)
         for m in self.models.values():
             m.to(self.device).eval()
         # evaluation.py:96 reads ../splits (cwd = manydepth/); the repository root works too
@@ -101,11 +108,22 @@ class Evaluation:
             return
         for n, m in self.models.items():
             path = os.path.join(self.load_weights_folder, f"{n}.pth")
+            if n == "normals_decoder" and not os.path.isfile(path):      # weights of a run without the variant: it keeps its initialisation
+                continue
             sd = torch.load(path, map_location="cpu")
             m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()})
 
     @torch.no_grad()
     def predict(self, inputs):
+        return self._forward(inputs, False)["depth"]
+
+    @torch.no_grad()
+    def predict_all(self, inputs):
+        """{"depth": what ``predict`` returns, "normals_pred": the NormalsDecoder's [N,3,H,W] output} -- the latter only with
+        the decoder, wired as Trainer._forward_models wires it (on the normals encoder's features)."""
+        return self._forward(inputs, True)
+
+    def _forward(self, inputs, with_normals_pred):
         # HAMMER_Dataset(raw_color=True) batches; colour sensor frames are demosaicked here, for polar_inputs too
         pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
         # the Trainer's hand-over: interleaved sensor frames (demosaic), un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
@@ -121,7 +139,10 @@ class Evaluation:
         depth = torch.empty((N, 1, self.height, self.width), device=disp.device)
         check(lib.pd_disp_to_depth(ptr(disp), ptr(depth), None, N, disp.shape[2], disp.shape[3], self.height, self.width,
                                    self.min_depth, self.max_depth, stream_ptr()), "pd_disp_to_depth")
-        return depth.clamp(self.min_depth, self.max_depth)
+        out = {"depth": depth.clamp(self.min_depth, self.max_depth)}
+        if with_normals_pred and "normals_decoder" in self.models:
+            out["normals_pred"] = self.models["normals_decoder"](nf)
+        return out
 
     def test(self):
         """evaluation.py:120-288: mean over images of the 7 masked depth metrics, for the whole frame and per material
@@ -145,4 +166,49 @@ class Evaluation:
             if counts[o].item() > 0:
                 results[o] = (sums[o] / counts[o]).cpu().numpy()
                 print(o, ("&{: 8.5f}  " * 7).format(*results[o].tolist()))
+        return results
+
+    @torch.no_grad()
+    def test_normals(self, source="auto"):
+        """Surface-normal accuracy per class (polardepth.normals_eval; the reference stops at depth): the angular error against
+        the normals of the ground-truth depth for the whole frame, all objects and each material, one pd_normals_stats call
+        per batch.  ``source``: "depth" scores the normals of the predicted depth, "decoder" the NormalsDecoder's output,
+        "auto" the decoder where it exists, else depth.  Prints, and returns {class: {"per_image": [7], "pooled": [7],
+        "bad": int}} with mean, median, rmse (degrees), the shares within 11.25 / 22.5 / 30 degrees and the pixel count:
+        "per_image" is the mean over images of the per-image figures (this project's convention for depth; images without a
+        pixel of the class do not count), "pooled" takes all pixels of all images as one set (the normals literature's).  The
+        records stay on the device until the loop is over."""
+        if source not in ("auto", "depth", "decoder"):
+            raise ValueError(f'source must be "auto", "depth" or "decoder", got {source!r}')
+        if source == "auto":
+            source = "decoder" if "normals_decoder" in self.models else "depth"
+        if source == "decoder" and "normals_decoder" not in self.models:
+            raise ValueError('source="decoder" needs Evaluation(normals_decoder=True) (or PD_NORMALS_DECODER=1)')
+        total, sums, counts = None, None, None
+        for inputs in self.test_loader:
+            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+            out = self._forward(inputs, source == "decoder")
+            st = normals_eval.normals_stats(out["normals_pred" if source == "decoder" else "depth"], inputs["depth_gt"],
+                                            inputs[("K", 0)], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
+                                            max_depth=self.max_depth)
+            m = st.metrics()
+            valid = st.n > 0
+            s = torch.where(valid[..., None], m, torch.zeros_like(m)).sum(0)
+            if total is None:
+                total, sums, counts = st, s, valid.sum(0)
+            else:
+                total += st
+                sums += s
+                counts += valid.sum(0)
+        if total is None:
+            return {}
+        per_image = sums / counts[:, None].double()
+        per_image, pooled, bad = per_image.cpu().numpy(), total.pooled().cpu().numpy(), total.pooled_bad().cpu().numpy()
+        results = {}
+        print(f"normals ({source}) " + ("{:>9} " * 7).format(*normals_eval.METRIC_NAMES))
+        for k, name in enumerate(total.names):
+            results[name] = {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k])}
+            if pooled[k][6] > 0:
+                print(f"{name:>8} per-image " + ("&{: 9.4f} " * 7).format(*per_image[k].tolist()))
+                print(f"{name:>8} pooled    " + ("&{: 9.4f} " * 7).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
         return results

@@ -1,4 +1,6 @@
-"""reference manydepth/evaluation_main.py:7-10."""
+"""reference manydepth/evaluation_main.py:7-10; PD_EVAL_NORMALS=1 adds the surface-normal report (Evaluation.test_normals)."""
+import os
+
 from manydepth.evaluation import Evaluation
 
 
@@ -6,6 +8,8 @@ def main():
     ev = Evaluation()
     ev.load_mono_model()
     ev.test()
+    if os.environ.get("PD_EVAL_NORMALS") == "1":
+        ev.test_normals()
 
 
 if __name__ == "__main__":

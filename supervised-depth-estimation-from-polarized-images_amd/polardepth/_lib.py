@@ -129,6 +129,8 @@ SIGNATURES = {
     "pd_ssim_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pd_ssim_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pd_depth_metrics": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _f, _f, _vp]),
+    "pd_normals_stats_workspace": (_sz, [_i, _i, _i, _i]),
+    "pd_normals_stats": (_i, [_vp, _l, _vp, _vp, _vp, _ip, _i, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
 }
 
 

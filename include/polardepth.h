@@ -623,6 +623,82 @@ int pd_normals_stats(const void* pred, long ld, const void* gtn, const void* gt,
                      void* stats, void* workspace, size_t ws_bytes, int N, int H, int W,
                      float min_depth, float max_depth, void* stream);
 
+/* Point-cloud accuracy (csrc/pointcloud.hip): the surface distance between the cloud of a predicted depth map and the cloud
+ * of the ground truth -- accuracy, completeness, Chamfer distance, precision / recall / F-score at 5 / 10 / 20 mm -- per
+ * image and pixel class.  The reference back-projects both depth maps through the camera matrix
+ * (pointcloud/eval_pointcloud.py:256-291, :83-85) and shows them in a viewer; these three calls measure what that demo is
+ * looked at for.  tests/pointcloud_ref.py states the definition in NumPy.
+ *
+ * TILED CLOUD.  The cloud of one image is T tiles of PD_PCD_TILE = 256 point slots:
+ *   points  fp32 [N][T * 256][4] = (x, y, z, w), 16-byte aligned.  w = 1: a point.  w = 0: no point (outside the image, or
+ *           gated out), x = y = z = 0.  w = -1: a "bad" point (inside the gate, but its depth is non-finite or <= 0),
+ *           x = y = z = 0.
+ *   boxes   [N][T] records of 32 bytes, 16-byte aligned:
+ *              0  float lo[3]   min of x, y, z over the w = 1 slots of the tile (+inf each for an empty tile)
+ *             12  float hi[3]   max of x, y, z (-inf each for an empty tile)
+ *             24  int32 count   the number of w = 1 slots
+ *             28  int32 0
+ * pd_cloud_nn does not care what the tiles are: any partition of a cloud into 256-slot tiles with correct boxes gives the
+ * same distances; compact tiles only make the boxes tight.
+ *
+ * pd_backproject: depth fp32 [N,H,W], K fp32 [N,4,4] (fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]), gate fp32
+ * [N,H,W] or NULL -> points and boxes with T = ceil(H/16) * ceil(W/16): the 16x16 pixel tiles in row-major tile order, slots
+ * row-major inside the tile, slots outside the image w = 0.  A pixel is in the cloud iff the gate depth (gate == NULL: the
+ * depth itself) is inside [min_depth, max_depth] (>=, <=, NaN fails: the gate of pd_gt_normals).  Inside the gate a depth
+ * that is non-finite or <= 0 gives w = -1.  Otherwise z = depth (copied), x = ((u - cx) / fx) * z, y = ((v - cy) / fy) * z
+ * with u, v the integer column and row, every operation rounded to fp32: the pinhole model of create_from_rgbd_image without
+ * the reference's display flip.  One launch.
+ *
+ * pd_cloud_nn: d2 fp32 [N][Tq * 256].  For a w = 1 query, d2 = the minimum over the w = 1 targets of the same image of
+ *     ((dx * dx + dy * dy) + dz * dz),   dx = qx - tx, dy = qy - ty, dz = qz - tz,
+ * every operation rounded to fp32, nothing fused; +inf when the target cloud of that image has no point.  For a query with
+ * w != 1: NaN.  A minimum does not depend on the order of its terms, so this is a bit-exact definition.
+ * flags: 0 = pruned, PD_PCD_BRUTE = scan every target tile.  visited: NULL or int32 [N][Tq], the number of target tiles
+ * scanned for that query tile.
+ * Pruning (exact).  One wave owns a query tile and keeps R = the maximum over the tile's w = 1 queries of their best d2 so
+ * far (+inf until each of them has a finite one).  It scans the target tile of the same index first (if there is one and it
+ * holds a point) and any other target tile only if it holds a point and boxd2 <= R at that moment, where
+ *     boxd2 = ((gx * gx + gy * gy) + gz * gz),   g = max(0, lo_t - hi_q, lo_q - hi_t) per axis,
+ * in fp32 and in the operation order of the point distance.  fp32 rounding is monotone, so boxd2 is a lower bound of the
+ * COMPUTED d2 of every pair of points from the two boxes, and a skipped tile cannot hold a smaller value for any query of
+ * the tile.  R is refreshed after every scanned tile.  A query tile without a w = 1 slot writes its NaNs and leaves (visited
+ * 0); under PD_PCD_BRUTE every query tile scans all Tt tiles (visited = Tt).
+ *
+ * pd_cloud_stats: one direction's records.  d2 and points are the query side of pd_cloud_nn with the tiling of
+ * pd_backproject for H x W (the slot -> pixel map); mask int32 [N,H,W] or NULL; classes HOST int[K][2] as in
+ * pd_normals_stats (lo > hi = every pixel; a ranged class needs a mask); edges2 DEVICE float[511], edges2[j-1] = the fp32
+ * rounding of (j * 0.0005 m)^2 computed in fp64, supplied by the caller; dist NULL or fp32 [N,H,W].
+ * stats: [N][K] records, written whole by every call; byte offsets:
+ *      0  int64   n           slots of the class with w = 1 and a finite d2 (the sum of the bins)
+ *      8  int64   bad         slots of the class with w = -1
+ *     16  int64   unmatched   slots of the class with w = 1 and d2 = +inf
+ *     24  double  sum_d       sum of sqrt((double)d2) in metres over the n slots
+ *     32  double  sum_d2      sum of (double)d2
+ *     40  8 bytes of zero
+ *     48  uint32  hist[512]   bin = #{ j : edges2[j-1] <= d2 }: 0.5 mm bins, the last one open-ended; 5 / 10 / 20 mm are
+ *                             bin edges (bins 0..9, 0..19, 0..39 lie below them).  No square root takes part in a bin.
+ * dist: (float)sqrt((double)d2) where the pixel's slot has w = 1 (+inf where unmatched), NaN elsewhere.
+ * The integer fields are exact; the two sums are bit-reproducible (fixed lane, wave and workgroup order, partials through
+ * `workspace`, no floating-point atomics, no cross-workgroup ticket: the scheme of pd_normals_stats).
+ * workspace: >= pd_cloud_stats_workspace(N, H, W, K) bytes (never 0, a multiple of 16, monotone), 16-byte aligned.
+ *
+ * No call synchronises, allocates or reads the environment.  N == 0 returns PD_OK after the checks.  Every refusal is
+ * PD_EINVAL with a message, decided before the device is touched: null pointers, points / boxes / stats / workspace not
+ * 16-byte aligned, K outside 1 .. 16, a ranged class with mask == NULL, non-positive shapes or tile counts, a frame whose
+ * slot offsets exceed 32 bits ("too large"), unknown flag bits, a too-small workspace (naming the needed size). */
+#define PD_PCD_TILE         256
+#define PD_PCD_BINS         512       /* 0.5 mm bins, the last one open-ended */
+#define PD_PCD_MAX_CLASSES  16
+#define PD_PCD_RECORD_BYTES 2096      /* 48 + 4 * 512 */
+#define PD_PCD_BRUTE        1u
+int pd_backproject(const void* depth, const void* K, const void* gate, void* points, void* boxes, int N, int H, int W,
+                   float min_depth, float max_depth, void* stream);
+int pd_cloud_nn(const void* q_points, const void* q_boxes, int Tq, const void* t_points, const void* t_boxes, int Tt,
+                void* d2, void* visited, unsigned flags, int N, void* stream);
+size_t pd_cloud_stats_workspace(int N, int H, int W, int K);
+int pd_cloud_stats(const void* d2, const void* points, const void* mask, const int* classes, int K, const void* edges2,
+                   void* dist, void* stats, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward
  * dp[r][:] <- scale * p * (dp - sum(dp * p)).  The score GEMMs (Q K^T, P V and their gradients) are pd_conv2d /

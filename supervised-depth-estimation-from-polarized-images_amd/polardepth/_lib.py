@@ -131,6 +131,10 @@ SIGNATURES = {
     "pd_depth_metrics": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _f, _f, _vp]),
     "pd_normals_stats_workspace": (_sz, [_i, _i, _i, _i]),
     "pd_normals_stats": (_i, [_vp, _l, _vp, _vp, _vp, _ip, _i, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
+    "pd_backproject": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
+    "pd_cloud_nn": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _u, _i, _vp]),
+    "pd_cloud_stats_workspace": (_sz, [_i, _i, _i, _i]),
+    "pd_cloud_stats": (_i, [_vp, _vp, _vp, _ip, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 

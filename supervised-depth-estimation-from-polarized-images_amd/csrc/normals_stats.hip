@@ -1,47 +1,26 @@
 // Angular error of predicted surface normals against the normals of the ground-truth depth, for up to 16 pixel classes
 // (the whole frame, all objects, each material of the instance mask) in ONE read of the batch: counts, fp64 sums of the
 // angle and its square, and a 0.25-degree histogram per image and class.  Definition and record: include/polardepth.h,
-// pd_normals_stats.
+// pd_normals_stats.  The records, their three launches and why the sums are bit-reproducible: class_records.hpp.
 //
-// Three launches:
-//   nstat_zero_kernel      clears the [N][K] records (the integer fields are filled by atomic adds).
-//   nstat_kernel           a workgroup belongs to one image; one work item = one quad (4 consecutive pixels of a row: per
-//                          pixel three pred floats, one 16-byte gtn load, the depth, the mask value; with gate 1 the 3 x 6
-//                          depths around the quad from L1 / L2).  Items go round-robin over the image's workgroups.  Per
-//                          workgroup: an LDS histogram [K][720] and `bad` counters [K], filled with LDS integer atomics and
-//                          flushed with one global add per non-empty word.  Per lane: fp64 sums of the angle and its square
-//                          for every class, reduced lane -> wave by a fixed shuffle tree and wave -> workgroup in order;
-//                          the workgroup's [K][2] partial sums go to the workspace with plain stores.
-//   nstat_finalize_kernel  one workgroup per record: n = the sum of the record's bins, and the two fp64 sums from the
-//                          image's partials in index order.
-// n, bad and hist are integer sums: no order can change them.  The two fp64 sums are bit-reproducible: the item -> lane
-// assignment depends on the shape only, a lane adds its items in order, and every later step has a fixed order.  No
-// floating-point atomics, no cross-workgroup ticket.
+// nstat_kernel: one work item = one quad (4 consecutive pixels of a row: per pixel three pred floats, one 16-byte gtn load,
+// the depth, the mask value; with gate 1 the 3 x 6 depths around the quad from L1 / L2).  The one counter is `bad`.
 //
 // The bin of a pixel is the number of table entries cos_edges[j] >= c, found by a ten-step binary search over a copy of the
 // caller's 719 doubles in LDS: acos takes no part in a bin decision.
-#include "pd_common.h"
+#include "class_records.hpp"
 
-#include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxGroups = 64;                      // workgroups per image
-constexpr long kQuadsPerGroup = 4L * kThreads;      // below the cap a lane gets about four quads
-constexpr int kBins = PD_NSTAT_BINS;
+using Rec = Layout<PD_NSTAT_BINS, 1, 8>;            // one counter (`bad`), the histogram starts at byte 32
+constexpr int kBins = Rec::kBins;
 constexpr int kEdges = kBins - 1;
-constexpr int kMaxK = PD_NSTAT_MAX_CLASSES;
-constexpr int kRecWords = PD_NSTAT_RECORD_BYTES / 4;
-constexpr int kHistWord = 8;                        // the histogram starts at byte 32
-constexpr long kMaxImagesPerLaunch = 1L << 20;      // keeps gridDim.x = images * groups below 2^31
 constexpr double kDegPerRad = 57.29577951308232;
 
-static_assert(32 + 4 * kBins == PD_NSTAT_RECORD_BYTES && PD_NSTAT_RECORD_BYTES % 16 == 0, "record layout");
-
-struct Classes { int lo[kMaxK], hi[kMaxK]; };       // by value in the kernel arguments: wave-uniform
+static_assert(32 + 4 * kBins == PD_NSTAT_RECORD_BYTES && Rec::kBytes == PD_NSTAT_RECORD_BYTES, "record layout");
+static_assert(kMaxK == PD_NSTAT_MAX_CLASSES, "class limit");
 
 struct Geo {
     unsigned H, W, Q, items;      // rows, columns, quads per row, quads per image
@@ -50,13 +29,6 @@ struct Geo {
     long ld;
     float min_d, max_d;
 };
-
-__global__ __launch_bounds__(kThreads) void nstat_zero_kernel(uint4* __restrict__ stats, long n16) {
-    for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n16; i += (long)gridDim.x * kThreads)
-        stats[i] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-__device__ __forceinline__ bool in_range(float d, float lo, float hi) { return d >= lo && d <= hi; }      // NaN fails
 
 __global__ __launch_bounds__(kThreads) void nstat_kernel(const float* __restrict__ pred, const float4* __restrict__ gtn,
                                                          const float* __restrict__ gt, const int* __restrict__ mask,
@@ -68,7 +40,7 @@ __global__ __launch_bounds__(kThreads) void nstat_kernel(const float* __restrict
     double* wsum = edges + kBins;                                                     // [kWaves][kMaxK][2]
     unsigned* bad = reinterpret_cast<unsigned*>(wsum + kWaves * kMaxK * 2);           // [kMaxK]
     unsigned* hist = bad + kMaxK;                                                     // [K][720]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int K = g.K;
     for (int i = tid; i < kBins; i += kThreads) edges[i] = i < kEdges ? cos_edges[i] : -2.0;
     if (tid < kMaxK) bad[tid] = 0;
@@ -162,8 +134,7 @@ __global__ __launch_bounds__(kThreads) void nstat_kernel(const float* __restrict
 #pragma unroll
             for (int k = 0; k < kMaxK; ++k) {
                 if (k < K) {
-                    const bool in = cls.lo[k] > cls.hi[k] || (m[j] >= cls.lo[k] && m[j] <= cls.hi[k]);
-                    if (in) {
+                    if (in_class(cls, k, m[j])) {
                         if (valid[j]) {
                             atomicAdd(&hist[k * kBins + lo[j]], 1u);
                             s[k][0] += th;
@@ -177,69 +148,10 @@ __global__ __launch_bounds__(kThreads) void nstat_kernel(const float* __restrict
         }
     }
 
-    // lanes -> wave by a fixed tree, waves -> workgroup in order
-#pragma unroll
-    for (int k = 0; k < kMaxK; ++k) {
-        if (k < K) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                s[k][0] += __shfl_down(s[k][0], off);
-                s[k][1] += __shfl_down(s[k][1], off);
-            }
-            if (lane == 0) {
-                wsum[(wave * kMaxK + k) * 2] = s[k][0];
-                wsum[(wave * kMaxK + k) * 2 + 1] = s[k][1];
-            }
-        }
-    }
-    __syncthreads();
-    if (tid < 2 * K) {
-        double t = 0.0;
-        for (int w = 0; w < kWaves; ++w) t += wsum[w * kMaxK * 2 + tid];
-        ws[((size_t)blockIdx.x * K) * 2 + tid] = t;      // [img][grp][k][2]
-    }
-    unsigned* rec = stats + (size_t)img * K * kRecWords;
-    if (tid < K && bad[tid])
-        atomicAdd(reinterpret_cast<unsigned long long*>(rec + (size_t)tid * kRecWords + 2), (unsigned long long)bad[tid]);
-    for (int i = tid; i < K * kBins; i += kThreads) {
-        const unsigned v = hist[i];
-        if (v) {
-            const int k = i / kBins;
-            atomicAdd(rec + (size_t)k * kRecWords + kHistWord + (i - k * kBins), v);
-        }
-    }
+    flush_records<Rec>(s, wsum, bad, hist, stats, ws, img, K);
 }
 
-// one workgroup per record [img][k]
-__global__ __launch_bounds__(kThreads) void nstat_finalize_kernel(unsigned* __restrict__ stats, const double* __restrict__ ws,
-                                                                  int K, int G) {
-    __shared__ unsigned long long red[kThreads];
-    const int tid = threadIdx.x;
-    const unsigned img = blockIdx.x / K, k = blockIdx.x - img * K;
-    unsigned* rec = stats + (size_t)blockIdx.x * kRecWords;
-    unsigned long long acc = 0;
-    for (int i = tid; i < kBins; i += kThreads) acc += rec[kHistWord + i];
-    red[tid] = acc;
-    __syncthreads();
-    for (int off = kThreads / 2; off > 0; off >>= 1) {
-        if (tid < off) red[tid] += red[tid + off];
-        __syncthreads();
-    }
-    if (tid == 0) *reinterpret_cast<long long*>(rec) = (long long)red[0];
-    if (tid == 64 || tid == 128) {                     // the two fp64 sums, workgroups in index order
-        const int which = tid == 64 ? 0 : 1;
-        double t = 0.0;
-        for (int gi = 0; gi < G; ++gi) t += ws[(((size_t)img * G + gi) * K + k) * 2 + which];
-        reinterpret_cast<double*>(rec)[2 + which] = t;
-    }
-}
-
-inline int groups_for(int H, int W) {
-    if (H <= 0 || W <= 0) return 1;
-    const long quads = (long)H * ((W + 3L) / 4);
-    const long b = (quads + kQuadsPerGroup - 1) / kQuadsPerGroup;
-    return (int)std::min<long>(kMaxGroups, std::max<long>(1, b));
-}
+inline int groups_of(int H, int W) { return groups_for(H > 0 && W > 0 ? (long)H * ((W + 3L) / 4) : 0); }      // items: quads
 
 inline size_t lds_bytes(int K) {
     return (size_t)kBins * 8 + (size_t)kWaves * kMaxK * 2 * 8 + (size_t)kMaxK * 4 + (size_t)K * kBins * 4;
@@ -248,8 +160,7 @@ inline size_t lds_bytes(int K) {
 }  // namespace
 
 extern "C" size_t pd_normals_stats_workspace(int N, int H, int W, int K) {
-    const size_t n = N > 0 ? (size_t)N : 1, k = (size_t)std::min(std::max(K, 1), kMaxK);
-    return n * (size_t)groups_for(H, W) * k * 16;
+    return records_workspace(N, K, groups_of(H, W));
 }
 
 extern "C" int pd_normals_stats(const void* pred, long ld, const void* gtn, const void* gt, const void* mask,
@@ -259,16 +170,10 @@ extern "C" int pd_normals_stats(const void* pred, long ld, const void* gtn, cons
     PD_REQUIRE(N >= 0 && H > 0 && W > 0, "pd_normals_stats: bad shape (N = %d, H = %d, W = %d)", N, H, W);
     PD_REQUIRE(pred && gtn && gt && classes && cos_edges && stats && workspace,
                "pd_normals_stats: pred, gtn, gt, classes, cos_edges, stats and workspace must not be null");
-    PD_REQUIRE(K >= 1 && K <= kMaxK, "pd_normals_stats: K = %d classes, 1 .. %d are supported", K, kMaxK);
+    Classes cls;
+    if (int e = parse_classes("pd_normals_stats", classes, K, mask != nullptr, &cls)) return e;
     PD_REQUIRE(ld >= 3, "pd_normals_stats: the pixel stride ld = %ld must be at least 3", ld);
     PD_REQUIRE(gate == 0 || gate == 1, "pd_normals_stats: gate = %d, must be 0 (centre) or 1 (3x3 window)", gate);
-    Classes cls;
-    for (int k = 0; k < kMaxK; ++k) {
-        cls.lo[k] = k < K ? classes[2 * k] : 1;
-        cls.hi[k] = k < K ? classes[2 * k + 1] : 0;
-        PD_REQUIRE(k >= K || mask || cls.lo[k] > cls.hi[k],
-                   "pd_normals_stats: class %d is the range [%d, %d] of the mask value, but mask is null", k, cls.lo[k], cls.hi[k]);
-    }
     PD_REQUIRE(pd::aligned16(gtn) && pd::aligned16(stats) && pd::aligned16(workspace),
                "pd_normals_stats: gtn, stats and workspace must be 16-byte aligned");
     PD_REQUIRE((long)H * W <= (1L << 30), "pd_normals_stats: a frame of %d x %d is too large for the kernel's index arithmetic",
@@ -280,25 +185,16 @@ extern "C" int pd_normals_stats(const void* pred, long ld, const void* gtn, cons
     hipStream_t st = (hipStream_t)stream;
     Geo g;
     g.H = (unsigned)H; g.W = (unsigned)W; g.Q = (unsigned)((W + 3) / 4); g.items = g.H * g.Q;
-    g.G = (unsigned)groups_for(H, W);
+    g.G = (unsigned)groups_of(H, W);
     g.K = K; g.gate = gate; g.ld = ld; g.min_d = min_depth; g.max_d = max_depth;
     const size_t frame = (size_t)H * W;
-    for (long n0 = 0; n0 < N; n0 += kMaxImagesPerLaunch) {
-        const long nb = std::min<long>(kMaxImagesPerLaunch, N - n0);
-        unsigned char* rec = static_cast<unsigned char*>(stats) + (size_t)n0 * K * PD_NSTAT_RECORD_BYTES;
-        double* part = static_cast<double*>(workspace) + (size_t)n0 * g.G * K * 2;
-        const long n16 = nb * K * (PD_NSTAT_RECORD_BYTES / 16);
-        const int zgrid = (int)std::min<long>(1024, (n16 + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(nstat_zero_kernel, dim3(zgrid), dim3(kThreads), 0, st, reinterpret_cast<uint4*>(rec), n16);
+    run_records<Rec>(stats, workspace, N, K, (int)g.G, st, [&](long n0, long nb, unsigned* rec, double* part) {
         hipLaunchKernelGGL(nstat_kernel, dim3((unsigned)(nb * g.G)), dim3(kThreads), lds_bytes(K), st,
                            static_cast<const float*>(pred) + (size_t)n0 * frame * (size_t)ld,
                            static_cast<const float4*>(gtn) + (size_t)n0 * frame, static_cast<const float*>(gt) + (size_t)n0 * frame,
                            mask ? static_cast<const int*>(mask) + (size_t)n0 * frame : nullptr,
                            static_cast<const double*>(cos_edges),
-                           err_deg ? static_cast<float*>(err_deg) + (size_t)n0 * frame : nullptr,
-                           reinterpret_cast<unsigned*>(rec), part, cls, g);
-        hipLaunchKernelGGL(nstat_finalize_kernel, dim3((unsigned)(nb * K)), dim3(kThreads), 0, st,
-                           reinterpret_cast<unsigned*>(rec), part, K, (int)g.G);
-    }
+                           err_deg ? static_cast<float*>(err_deg) + (size_t)n0 * frame : nullptr, rec, part, cls, g);
+    });
     return pd::check_launch("pd_normals_stats");
 }

@@ -10,37 +10,29 @@
 //                        no LDS, no barrier.  Target tiles are tested 64 at a time (one box per lane, one ballot); the
 //                        ballot is re-taken against the current R after every scanned tile, R by a wave max reduction.
 //                        Every branch is wave-uniform.
-//   pcd_stat_kernel      the scheme of nstat_kernel (csrc/normals_stats.hip): LDS histogram [K][512], per-lane fp64 sums,
-//                        partials through the workspace, pcd_finalize_kernel adds them in index order.
-#include "pd_common.h"
+//   pcd_stat_kernel      the per-class records of class_records.hpp (their three launches, and why the sums are
+//                        bit-reproducible, are described there): one work item = one slot; the counters are `bad` and
+//                        `unmatched`.  The bin of a distance is the number of table entries edges2[j] <= d2, by a nine-step
+//                        binary search over a copy of the caller's 511 floats in LDS.
+#include "class_records.hpp"
 
-#include <algorithm>
 #include <cmath>
 
 namespace {
 
+using Rec = Layout<PD_PCD_BINS, 2, 12>;             // two counters (`bad`, `unmatched`), the histogram starts at byte 48
 constexpr int kTile = PD_PCD_TILE;
-constexpr int kBins = PD_PCD_BINS;
+constexpr int kBins = Rec::kBins;
 constexpr int kEdges = kBins - 1;
-constexpr int kMaxK = PD_PCD_MAX_CLASSES;
-constexpr int kRecWords = PD_PCD_RECORD_BYTES / 4;
-constexpr int kHistWord = 12;                       // the histogram starts at byte 48
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxGroups = 64;                      // workgroups per image of the stats kernel
-constexpr long kSlotsPerGroup = 4L * kThreads;
 constexpr long kMaxBlocks = 1L << 30;               // per launch
 constexpr long kMaxSlots = 1L << 30;                // per image: slot offsets inside a frame are 32-bit
 
-static_assert(48 + 4 * kBins == PD_PCD_RECORD_BYTES && PD_PCD_RECORD_BYTES % 16 == 0, "record layout");
+static_assert(48 + 4 * kBins == PD_PCD_RECORD_BYTES && Rec::kBytes == PD_PCD_RECORD_BYTES, "record layout");
+static_assert(kMaxK == PD_PCD_MAX_CLASSES, "class limit");
 static_assert(kTile == 256, "a tile is 16 x 16 pixels, four slots per lane of a wave");
 
 struct Box { float lo[3], hi[3]; int count, pad; };
 static_assert(sizeof(Box) == 32, "box record");
-
-struct Classes { int lo[kMaxK], hi[kMaxK]; };
-
-__device__ __forceinline__ bool in_range(float d, float lo, float hi) { return d >= lo && d <= hi; }      // NaN fails
 
 __global__ __launch_bounds__(kThreads) void backproject_kernel(const float* __restrict__ depth, const float* __restrict__ Kmat,
                                                                const float* __restrict__ gate, float4* __restrict__ points,
@@ -203,11 +195,6 @@ struct Geo {
     int K;
 };
 
-__global__ __launch_bounds__(kThreads) void pcd_zero_kernel(uint4* __restrict__ stats, long n16) {
-    for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n16; i += (long)gridDim.x * kThreads)
-        stats[i] = make_uint4(0u, 0u, 0u, 0u);
-}
-
 __global__ __launch_bounds__(kThreads) void pcd_stat_kernel(const float* __restrict__ d2, const float4* __restrict__ pts,
                                                             const int* __restrict__ mask, const float* __restrict__ edges2,
                                                             float* __restrict__ dist, unsigned* __restrict__ stats,
@@ -215,10 +202,10 @@ __global__ __launch_bounds__(kThreads) void pcd_stat_kernel(const float* __restr
     extern __shared__ __align__(16) unsigned char smem[];
     double* wsum = reinterpret_cast<double*>(smem);                                   // [kWaves][kMaxK][2]
     float* edges = reinterpret_cast<float*>(wsum + kWaves * kMaxK * 2);               // [512], the last one is padding
-    unsigned* bad = reinterpret_cast<unsigned*>(edges + kBins);                       // [kMaxK]
+    unsigned* bad = reinterpret_cast<unsigned*>(edges + kBins);                       // [kMaxK]: the counters [2][kMaxK]
     unsigned* unm = bad + kMaxK;                                                      // [kMaxK]
     unsigned* hist = unm + kMaxK;                                                     // [K][512]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int K = g.K;
     for (int i = tid; i < kBins; i += kThreads) edges[i] = i < kEdges ? edges2[i] : INFINITY;
     if (tid < kMaxK) bad[tid] = unm[tid] = 0;
@@ -265,8 +252,7 @@ __global__ __launch_bounds__(kThreads) void pcd_stat_kernel(const float* __restr
 #pragma unroll
         for (int k = 0; k < kMaxK; ++k) {
             if (k < K) {
-                const bool in = cls.lo[k] > cls.hi[k] || (m >= cls.lo[k] && m <= cls.hi[k]);
-                if (in) {
+                if (in_class(cls, k, m)) {
                     if (fin) {
                         atomicAdd(&hist[k * kBins + lo], 1u);
                         s[k][0] += dd;
@@ -281,74 +267,12 @@ __global__ __launch_bounds__(kThreads) void pcd_stat_kernel(const float* __restr
         }
     }
 
-    // lanes -> wave by a fixed tree, waves -> workgroup in order
-#pragma unroll
-    for (int k = 0; k < kMaxK; ++k) {
-        if (k < K) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                s[k][0] += __shfl_down(s[k][0], off);
-                s[k][1] += __shfl_down(s[k][1], off);
-            }
-            if (lane == 0) {
-                wsum[(wave * kMaxK + k) * 2] = s[k][0];
-                wsum[(wave * kMaxK + k) * 2 + 1] = s[k][1];
-            }
-        }
-    }
-    __syncthreads();
-    if (tid < 2 * K) {
-        double t = 0.0;
-        for (int w = 0; w < kWaves; ++w) t += wsum[w * kMaxK * 2 + tid];
-        ws[((size_t)blockIdx.x * K) * 2 + tid] = t;      // [img][grp][k][2]
-    }
-    unsigned* rec = stats + (size_t)img * K * kRecWords;
-    if (tid < K && bad[tid])
-        atomicAdd(reinterpret_cast<unsigned long long*>(rec + (size_t)tid * kRecWords + 2), (unsigned long long)bad[tid]);
-    if (tid < K && unm[tid])
-        atomicAdd(reinterpret_cast<unsigned long long*>(rec + (size_t)tid * kRecWords + 4), (unsigned long long)unm[tid]);
-    for (int i = tid; i < K * kBins; i += kThreads) {
-        const unsigned v = hist[i];
-        if (v) {
-            const int k = i / kBins;
-            atomicAdd(rec + (size_t)k * kRecWords + kHistWord + (i - k * kBins), v);
-        }
-    }
-}
-
-// one workgroup per record [img][k]
-__global__ __launch_bounds__(kThreads) void pcd_finalize_kernel(unsigned* __restrict__ stats, const double* __restrict__ ws,
-                                                                int K, int G) {
-    __shared__ unsigned long long red[kThreads];
-    const int tid = threadIdx.x;
-    const unsigned img = blockIdx.x / K, k = blockIdx.x - img * K;
-    unsigned* rec = stats + (size_t)blockIdx.x * kRecWords;
-    unsigned long long acc = 0;
-    for (int i = tid; i < kBins; i += kThreads) acc += rec[kHistWord + i];
-    red[tid] = acc;
-    __syncthreads();
-    for (int off = kThreads / 2; off > 0; off >>= 1) {
-        if (tid < off) red[tid] += red[tid + off];
-        __syncthreads();
-    }
-    if (tid == 0) *reinterpret_cast<long long*>(rec) = (long long)red[0];
-    if (tid == 64 || tid == 128) {                     // the two fp64 sums, workgroups in index order
-        const int which = tid == 64 ? 0 : 1;
-        double t = 0.0;
-        for (int gi = 0; gi < G; ++gi) t += ws[(((size_t)img * G + gi) * K + k) * 2 + which];
-        reinterpret_cast<double*>(rec)[3 + which] = t;
-    }
+    flush_records<Rec>(s, wsum, bad, hist, stats, ws, img, K);
 }
 
 inline long tiles_x(int W) { return (W + 15L) / 16; }
 inline long tiles_of(int H, int W) { return ((H + 15L) / 16) * tiles_x(W); }
-
-inline int groups_for(int H, int W) {
-    if (H <= 0 || W <= 0) return 1;
-    const long slots = tiles_of(H, W) * kTile;
-    const long b = (slots + kSlotsPerGroup - 1) / kSlotsPerGroup;
-    return (int)std::min<long>(kMaxGroups, std::max<long>(1, b));
-}
+inline int groups_of(int H, int W) { return groups_for(H > 0 && W > 0 ? tiles_of(H, W) * kTile : 0); }      // items: slots
 
 inline size_t lds_bytes(int K) {
     return (size_t)kWaves * kMaxK * 2 * 8 + (size_t)kBins * 4 + (size_t)kMaxK * 8 + (size_t)K * kBins * 4;
@@ -405,8 +329,7 @@ extern "C" int pd_cloud_nn(const void* q_points, const void* q_boxes, int Tq, co
 }
 
 extern "C" size_t pd_cloud_stats_workspace(int N, int H, int W, int K) {
-    const size_t n = N > 0 ? (size_t)N : 1, k = (size_t)std::min(std::max(K, 1), kMaxK);
-    return n * (size_t)groups_for(H, W) * k * 16;
+    return records_workspace(N, K, groups_of(H, W));
 }
 
 extern "C" int pd_cloud_stats(const void* d2, const void* points, const void* mask, const int* classes, int K,
@@ -415,14 +338,8 @@ extern "C" int pd_cloud_stats(const void* d2, const void* points, const void* ma
     PD_REQUIRE(N >= 0 && H > 0 && W > 0, "pd_cloud_stats: bad shape (N = %d, H = %d, W = %d)", N, H, W);
     PD_REQUIRE(d2 && points && classes && edges2 && stats && workspace,
                "pd_cloud_stats: d2, points, classes, edges2, stats and workspace must not be null");
-    PD_REQUIRE(K >= 1 && K <= kMaxK, "pd_cloud_stats: K = %d classes, 1 .. %d are supported", K, kMaxK);
     Classes cls;
-    for (int k = 0; k < kMaxK; ++k) {
-        cls.lo[k] = k < K ? classes[2 * k] : 1;
-        cls.hi[k] = k < K ? classes[2 * k + 1] : 0;
-        PD_REQUIRE(k >= K || mask || cls.lo[k] > cls.hi[k],
-                   "pd_cloud_stats: class %d is the range [%d, %d] of the mask value, but mask is null", k, cls.lo[k], cls.hi[k]);
-    }
+    if (int e = parse_classes("pd_cloud_stats", classes, K, mask != nullptr, &cls)) return e;
     PD_REQUIRE(pd::aligned16(points) && pd::aligned16(stats) && pd::aligned16(workspace),
                "pd_cloud_stats: points, stats and workspace must be 16-byte aligned");
     const long T = tiles_of(H, W);
@@ -434,25 +351,16 @@ extern "C" int pd_cloud_stats(const void* d2, const void* points, const void* ma
     hipStream_t st = (hipStream_t)stream;
     Geo g;
     g.H = (unsigned)H; g.W = (unsigned)W; g.TX = (unsigned)tiles_x(W); g.slots = (unsigned)(T * kTile);
-    g.G = (unsigned)groups_for(H, W);
+    g.G = (unsigned)groups_of(H, W);
     g.K = K;
     const size_t frame = (size_t)H * W;
-    const long per = 1L << 20;                           // keeps gridDim.x = images * groups below 2^31
-    for (long n0 = 0; n0 < N; n0 += per) {
-        const long nb = std::min<long>(per, N - n0);
-        unsigned char* rec = static_cast<unsigned char*>(stats) + (size_t)n0 * K * PD_PCD_RECORD_BYTES;
-        double* part = static_cast<double*>(workspace) + (size_t)n0 * g.G * K * 2;
-        const long n16 = nb * K * (PD_PCD_RECORD_BYTES / 16);
-        const int zgrid = (int)std::min<long>(1024, (n16 + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(pcd_zero_kernel, dim3(zgrid), dim3(kThreads), 0, st, reinterpret_cast<uint4*>(rec), n16);
+    run_records<Rec>(stats, workspace, N, K, (int)g.G, st, [&](long n0, long nb, unsigned* rec, double* part) {
         hipLaunchKernelGGL(pcd_stat_kernel, dim3((unsigned)(nb * g.G)), dim3(kThreads), lds_bytes(K), st,
                            static_cast<const float*>(d2) + (size_t)n0 * g.slots,
                            static_cast<const float4*>(points) + (size_t)n0 * g.slots,
                            mask ? static_cast<const int*>(mask) + (size_t)n0 * frame : nullptr,
                            static_cast<const float*>(edges2), dist ? static_cast<float*>(dist) + (size_t)n0 * frame : nullptr,
-                           reinterpret_cast<unsigned*>(rec), part, cls, g);
-        hipLaunchKernelGGL(pcd_finalize_kernel, dim3((unsigned)(nb * K)), dim3(kThreads), 0, st,
-                           reinterpret_cast<unsigned*>(rec), part, K, (int)g.G);
-    }
+                           rec, part, cls, g);
+    });
     return pd::check_launch("pd_cloud_stats");
 }

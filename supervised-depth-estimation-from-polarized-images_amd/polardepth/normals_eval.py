@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, ptr, stream_ptr
+from ._records import Pool, device_table, frames, hist_median, need_cuda
 
 BINS = 720                  # PD_NSTAT_BINS: 0.25-degree bins over [0, 180]
 MAX_CLASSES = 16            # PD_NSTAT_MAX_CLASSES
@@ -26,7 +27,6 @@ MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, "
 DEFAULT_CLASSES = (("all", None), ("objects", (20, 160))) + tuple((m, (g, g)) for m, g in MATERIAL_GREY.items())
 
 _F32_MAX = float(np.finfo(np.float32).max)
-_EDGES = {}                 # device -> the 719 doubles
 
 
 def cos_edges_numpy():
@@ -43,12 +43,7 @@ def cos_edges_numpy():
 
 def cos_edges(device):
     """The table on ``device``: built once with NumPy, cached."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _EDGES:
-        _EDGES[device] = torch.from_numpy(cos_edges_numpy()).to(device)
-    return _EDGES[device]
+    return device_table(cos_edges_numpy, device)
 
 
 def class_table(classes):
@@ -71,16 +66,12 @@ def metrics_from_fields(n, sum_deg, sum_deg2, hist):
     nf = n.double()
     hist = hist.long()
     cs = hist.cumsum(-1)
-    half = nf / 2
-    b = (cs.double() < half[..., None]).sum(-1).clamp(max=BINS - 1)
-    hb = hist.gather(-1, b[..., None])[..., 0]
-    below = cs.gather(-1, b[..., None])[..., 0] - hb
-    median = (b.double() + (half - below.double()) / hb.double()) * BIN_DEG
     share = lambda k: cs[..., k - 1].double() / nf
-    return torch.stack([sum_deg / nf, median, (sum_deg2 / nf).sqrt(), share(45), share(90), share(120), nf], -1)
+    return torch.stack([sum_deg / nf, hist_median(n, hist, BIN_DEG), (sum_deg2 / nf).sqrt(), share(45), share(90), share(120),
+                        nf], -1)
 
 
-class NormalsStats:
+class NormalsStats(Pool):
     """The [N][K] records of one ``normals_stats`` call, on the device, plus a device-side pool: ``a += b`` adds b's images
     to a's pool (int64 counts, fp64 sums, histograms widened to int64).  Nothing reaches the host until the caller asks."""
 
@@ -88,7 +79,6 @@ class NormalsStats:
         self.records = records                # uint8 [N, K, RECORD_BYTES]
         self.names = list(names)
         self.err_deg = err_deg                # fp32 [N, H, W] or None
-        self._pool = None
 
     # ---- the fields of the records, as views
     @property
@@ -115,18 +105,8 @@ class NormalsStats:
         """[N, K, 7] float64 on the device: mean, median, rmse, the three shares, n -- per image and class."""
         return metrics_from_fields(self.n, self.sum_deg, self.sum_deg2, self.hist)
 
-    def _totals(self):
-        if self._pool is None:
-            self._pool = [self.n.sum(0), self.bad.sum(0), self.sum_deg.sum(0), self.sum_deg2.sum(0), self.hist.long().sum(0)]
-        return self._pool
-
-    def __iadd__(self, other):
-        if other.names != self.names:
-            raise ValueError(f"cannot pool the classes {other.names} into {self.names}")
-        mine = self._totals()
-        for i, t in enumerate(other._totals()):
-            mine[i] = mine[i] + t
-        return self
+    def _pool_fields(self):
+        return self.n, self.bad, self.sum_deg, self.sum_deg2, self.hist.long()
 
     def pooled(self):
         """[K, 7] float64 on the device: the same seven figures over all pixels of all images pooled so far (this call's,
@@ -162,22 +142,16 @@ def normals_stats(pred, gt_depth, K, mask=None, classes=DEFAULT_CLASSES, gate=Tr
     classes    (name, None | (lo, hi)) pairs, at most 16
     gate       True: a pixel counts when all nine depths of its 3x3 window are inside [min_depth, max_depth]; False: its own
     err_map    also return the per-pixel angle in degrees (NaN where the pixel does not count) as ``.err_deg``"""
-    for t in (pred, gt_depth, K, mask):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError("normals_stats needs CUDA(HIP) tensors; there is no CPU fallback")
+    need_cuda("normals_stats", pred, gt_depth, K, mask)
     if pred.dim() != 4 or pred.shape[1] not in (1, 3):
         raise ValueError(f"pred must be [N,3,H,W] normals or [N,1,H,W] depth, got {tuple(pred.shape)}")
     N, C, H, W = pred.shape
     names, table = class_table(classes)
     nk = len(names)
     dev = pred.device
-    gt = gt_depth.float().contiguous()
-    if gt.numel() != N * H * W:
-        raise ValueError(f"gt_depth {tuple(gt_depth.shape)} does not match pred {tuple(pred.shape)}")
+    gt = frames(gt_depth, "gt_depth", N, H, W).float().contiguous()
     if mask is not None:
-        if mask.numel() != N * H * W:
-            raise ValueError(f"mask {tuple(mask.shape)} does not match pred {tuple(pred.shape)}")
-        mask = mask.to(torch.int32).contiguous()
+        mask = frames(mask, "mask", N, H, W).to(torch.int32).contiguous()
     records = torch.empty((N, nk, RECORD_BYTES), dtype=torch.uint8, device=dev)
     err = torch.empty((N, H, W), dtype=torch.float32, device=dev) if err_map else None
     if N == 0 or H == 0 or W == 0:

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, check, ptr, stream_ptr
+from ._records import Pool, device_table, frames as _frames, hist_median, need_cuda as _need_cuda
 from .normals_eval import DEFAULT_CLASSES, class_table
 
 TILE = 256                  # PD_PCD_TILE
@@ -22,8 +23,6 @@ BIN_MM = 0.5
 THRESHOLD_BINS = (10, 20, 40)      # 5 / 10 / 20 mm: the bins below them
 METRIC_NAMES = ("acc", "comp", "chamfer", "acc_med", "comp_med", "f5", "f10", "f20", "n")
 
-_EDGES = {}                 # device -> the 511 floats
-
 
 def edges2_numpy():
     """The bin edges as squared distances: e[j-1] = fp32((j * 0.0005 m)^2 computed in fp64), j = 1 .. 511, strictly
@@ -35,12 +34,7 @@ def edges2_numpy():
 
 def edges2(device):
     """The table on ``device``: built once with NumPy, cached."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if device not in _EDGES:
-        _EDGES[device] = torch.from_numpy(edges2_numpy()).to(device)
-    return _EDGES[device]
+    return device_table(edges2_numpy, device)
 
 
 def tiles_of(H, W):
@@ -76,22 +70,6 @@ class Cloud:
         t, r = s // TILE, s % TILE
         v, u = (t // tx) * 16 + r // 16, (t % tx) * 16 + r % 16
         return np.where((v < H) & (u < W), v * W + u, -1)
-
-
-def _need_cuda(what, *tensors):
-    for t in tensors:
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"{what} needs CUDA(HIP) tensors; there is no CPU fallback")
-
-
-def _frames(t, what, N=None, H=None, W=None):
-    """[N,1,H,W] or [N,H,W] -> contiguous fp32 [N,H,W]."""
-    if t.dim() == 4 and t.shape[1] == 1:
-        t = t[:, 0]
-    if t.dim() != 3 or (N is not None and tuple(t.shape) != (N, H, W)):
-        raise ValueError(f"{what} must be [N,1,H,W] or [N,H,W]" + (f" = {(N, H, W)}" if N is not None else "") +
-                         f", got {tuple(t.shape)}")
-    return t
 
 
 def backproject(depth, K, gate=None, min_depth=0.1, max_depth=2.0):
@@ -136,17 +114,6 @@ def nearest(query, target, prune=True, visited=False):
     return (d2, seen) if visited else d2
 
 
-def _median_mm(n, hist):
-    """The median in millimetres, interpolated linearly inside the bin that holds the n/2-th value (the scheme of
-    normals_eval.metrics_from_fields)."""
-    cs = hist.cumsum(-1)
-    half = n.double() / 2
-    b = (cs.double() < half[..., None]).sum(-1).clamp(max=BINS - 1)
-    hb = hist.gather(-1, b[..., None])[..., 0]
-    below = cs.gather(-1, b[..., None])[..., 0] - hb
-    return (b.double() + (half - below.double()) / hb.double()) * BIN_MM
-
-
 def shares_from_fields(n, unmatched, hist):
     """[..., 3] float64: the share of the direction's points within 5 / 10 / 20 mm -- exact integer ratios, the three
     thresholds being bin edges.  Unmatched points (an empty target cloud) are points that miss."""
@@ -164,7 +131,8 @@ def metrics_from_fields(acc, comp):
     a, c = sa / na.double() * 1000.0, sc / nc.double() * 1000.0
     P, R = shares_from_fields(na, ua, ha), shares_from_fields(nc, uc, hc)
     F = torch.where(P + R > 0, 2 * P * R / (P + R), P + R)          # 0 where both are 0, NaN where either is
-    return torch.stack([a, c, a + c, _median_mm(na, ha), _median_mm(nc, hc), F[..., 0], F[..., 1], F[..., 2], na.double()], -1)
+    return torch.stack([a, c, a + c, hist_median(na, ha, BIN_MM), hist_median(nc, hc, BIN_MM), F[..., 0], F[..., 1], F[..., 2],
+                        na.double()], -1)
 
 
 class _Direction:
@@ -183,12 +151,11 @@ class _Direction:
     def fields(self):
         return self.n, self.unmatched, self.sum_d, self.hist
 
-    def totals(self):
-        return [self.n.sum(0), self.bad.sum(0), self.unmatched.sum(0), self.sum_d.sum(0), self.sum_d2.sum(0),
-                self.hist.long().sum(0)]
+    def pool_fields(self):
+        return self.n, self.bad, self.unmatched, self.sum_d, self.sum_d2, self.hist.long()
 
 
-class CloudStats:
+class CloudStats(Pool):
     """Both directions' records of one ``cloud_stats`` call, on the device: ``acc`` (predicted -> true) and ``comp`` (true ->
     predicted), each with the field views n, bad, unmatched, sum_d, sum_d2, hist; plus a device-side pool: ``a += b`` adds
     b's images to a's.  Nothing reaches the host until the caller asks."""
@@ -197,7 +164,6 @@ class CloudStats:
         self.acc, self.comp = _Direction(acc_records), _Direction(comp_records)
         self.names = list(names)
         self.dist_acc, self.dist_comp = dist_acc, dist_comp      # fp32 [N, H, W] metres, or None
-        self._pool = None
 
     def metrics(self):
         """[N, K, 9] float64 on the device, per image and class: METRIC_NAMES."""
@@ -208,36 +174,25 @@ class CloudStats:
         return (shares_from_fields(self.acc.n, self.acc.unmatched, self.acc.hist),
                 shares_from_fields(self.comp.n, self.comp.unmatched, self.comp.hist))
 
-    def _totals(self):
-        if self._pool is None:
-            self._pool = [self.acc.totals(), self.comp.totals()]
-        return self._pool
-
-    def __iadd__(self, other):
-        if other.names != self.names:
-            raise ValueError(f"cannot pool the classes {other.names} into {self.names}")
-        mine = self._totals()
-        for d, theirs in enumerate(other._totals()):
-            for i, t in enumerate(theirs):
-                mine[d][i] = mine[d][i] + t
-        return self
+    def _pool_fields(self):
+        return self.acc.pool_fields() + self.comp.pool_fields()      # six per direction
 
     def pooled(self):
         """[K, 9] float64 on the device: the same figures over all points of all images pooled so far."""
-        (na, _, ua, sa, _, ha), (nc, _, uc, sc, _, hc) = self._totals()
+        na, _, ua, sa, _, ha, nc, _, uc, sc, _, hc = self._totals()
         return metrics_from_fields((na, ua, sa, ha), (nc, uc, sc, hc))
 
     def pooled_shares(self):
-        (na, _, ua, _, _, ha), (nc, _, uc, _, _, hc) = self._totals()
+        na, _, ua, _, _, ha, nc, _, uc, _, _, hc = self._totals()
         return shares_from_fields(na, ua, ha), shares_from_fields(nc, uc, hc)
 
     def pooled_bad(self):
         """[K] int64 on the device: predicted points without a usable depth (`bad` of the accuracy direction) over the pool."""
-        return self._totals()[0][1]
+        return self._totals()[1]
 
     def pooled_unmatched(self):
         """[K] int64 on the device: points of either cloud whose image has no point in the other cloud, over the pool."""
-        return self._totals()[0][2] + self._totals()[1][2]
+        return self._totals()[2] + self._totals()[8]
 
 
 def direction_stats(d2, cloud, mask=None, classes=DEFAULT_CLASSES, dist_map=False):

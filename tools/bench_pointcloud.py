@@ -4,6 +4,7 @@ The scene is synthetic: a smooth surface with a few raised boxes ("objects") and
 1 % relative noise and a handful of depth spikes per image.  Timed, warm, with HIP events (one event pair per call, median of
 ``--iters`` calls; ``--brute-iters`` for the brute route):
   cloud_stats   the whole measurement: two back-projections, nearest neighbours both ways (pruned), two record calls
+  stats         the two record calls (pd_cloud_stats) alone, on distances found beforehand
   nn_pruned     the two pd_cloud_nn calls alone, pruned;  nn_brute: the same with PD_PCD_BRUTE
   copy          a device copy that moves the bytes the two pd_cloud_nn calls must touch once (both clouds' points and boxes
                 read, d2 written, per direction)
@@ -94,11 +95,18 @@ def bench(N, H, W, iters, brute_iters):
     def whole():
         pc.cloud_stats(pred, gt, K, mask=mask)
 
-    for f in (lambda: both(True), whole):
+    d2_acc, d2_comp = pc.nearest(p, t), pc.nearest(t, p)
+
+    def stats():
+        pc.direction_stats(d2_acc, p, mask)
+        pc.direction_stats(d2_comp, t, mask)
+
+    for f in (lambda: both(True), whole, stats):
         f()
     torch.cuda.synchronize()
     out = {"op": "pointcloud", "N": N, "H": H, "W": W, "tiles": T}
     out["cloud_stats_ms"] = round(_median_ms(whole, iters), 4)
+    out["stats_ms"] = round(_median_ms(stats, iters), 4)
     out["nn_pruned_ms"] = round(_median_ms(lambda: both(True), iters), 4)
     both(False)
     torch.cuda.synchronize()

@@ -699,6 +699,78 @@ size_t pd_cloud_stats_workspace(int N, int H, int W, int K);
 int pd_cloud_stats(const void* d2, const void* points, const void* mask, const int* classes, int K, const void* edges2,
                    void* dist, void* stats, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
 
+/* Depth accuracy per pixel class (csrc/depth_stats.hip): the figures of compute_depth_errors (layers.py:539-577) -- abs_rel,
+ * sq_rel, rmse, rmse_log, a1, a2, a3 -- and the distribution of the absolute error, for K classes of the instance mask at
+ * once, in one read of the batch; and the exact per-class medians that median scaling needs (trainer.py:1344, :1416).
+ * tests/depth_stats_ref.py states the definition in NumPy.
+ *
+ * gt, pred   fp32 [N,H,W] on the device; mask int32 [N,H,W] or NULL; classes HOST int[K][2] as in pd_normals_stats
+ *            (lo > hi = every pixel; a ranged class needs a mask); 1 <= K <= PD_DSTAT_MAX_CLASSES.
+ * PIXEL SET  S(n,k) = the pixels of image n with min_depth < gt < max_depth (strict, NaN fails: the gate of
+ *            pd_depth_metrics and of the reference), in class k, with a finite pred.  A pixel that passes the gate and the
+ *            class but whose pred is NaN or +-inf adds 1 to `bad` of that class and takes part in nothing else.
+ *            p0 = fminf(fmaxf(pred, min_depth), max_depth).  min_depth > 0 and max_depth > min_depth are required;
+ *            max_depth = +inf is allowed.
+ *
+ * pd_depth_medians: count int64 [N][K] = |S(n,k)|; med fp32 [N][K][4] = the order statistics of rank (n-1)/2 and n/2
+ * (integer division) of gt, then of rank (n-1)/2 and n/2 of p0, over S(n,k): the very bit patterns a sort would put at those
+ * ranks.  NaN where n = 0.  Every value is positive, so the unsigned order of the bit patterns is the order of the floats:
+ * a radix selection, eight bits a pass from the top, four passes.  A pass is two launches: a histogram kernel (the image's
+ * pixels round-robin over its workgroups; a workgroup counts, in LDS with integer atomics, the current digit of the values
+ * that match the digits already chosen -- one 256-bin histogram per class, quantity and rank -- and adds its non-zero bins
+ * to the global histogram with integer atomics), and a one-workgroup-per-(n,k) kernel that finds the bin holding the rank
+ * and narrows the prefix.  The first pass yields n, from which the device derives the two ranks.  Nine launches per 2^20
+ * images; no sort, no allocation, no synchronisation, no floating-point atomics, no cross-workgroup ticket: the call can be
+ * captured into a graph.  workspace: >= pd_depth_medians_workspace(N, K) bytes, 16-byte aligned.
+ *
+ * pd_depth_stats: scale NULL or DEVICE fp32 [N][K]; edges DEVICE double[511], edges[j-1] = j * 0.0005 (metres), supplied by
+ * the caller like the tables of the other two evaluators; err NULL or fp32 [N,H,W].
+ * Per pixel of S(n,k):  p = p0 without a scale, else p = fminf(fmaxf(p0 * scale[n][k], min_depth), max_depth), every
+ * operation in fp32 and in this order (trainer.py:1416-1419).  A non-finite scale[n][k] makes every pixel of the class that
+ * passes the gate `bad` for that image.  With g = gt:
+ *   a1, a2, a3   count fmaxf(g / p, p / g) < 1.25, 1.5625, 1.953125, decided in fp32 with IEEE division: the reference's own
+ *                expression, so the counts are exact against it.
+ *   the sums     g and p widened to fp64; d = g - p (exact); |d| / g, d * d / g, d * d and l * l with l = log1p(d / p), added
+ *                per class.  log1p of the exact difference instead of log g - log p: the same quantity, log(g / p), without
+ *                the cancellation between two logarithms that for g ~ p leaves an absolute error of an ulp of log g in a
+ *                value many orders smaller.
+ *   the bin      #{ j >= 1 : edges[j-1] <= |d| }, found by binary search: 0.5 mm bins, the last one open-ended; 5 / 10 /
+ *                20 mm are bin edges.  No division takes part in a bin decision.
+ * stats: [N][K] records, written whole by every call; byte offsets:
+ *      0  int64   n            |S(n,k)| (the sum of the bins)
+ *      8  int64   a1
+ *     16  int64   a2
+ *     24  int64   a3
+ *     32  int64   bad
+ *     40  double  sum_abs_rel  sum |d| / g
+ *     48  double  sum_sq_rel   sum d * d / g
+ *     56  double  sum_sq       sum d * d
+ *     64  double  sum_log2     sum l * l
+ *     72  8 bytes of zero
+ *     80  uint32  hist[512]
+ * err (only without a scale -- a scaled error is per class; err together with scale is refused): (float)|g - p0| in metres
+ * where the pixel passes the gate and pred is finite, whatever its class; NaN elsewhere.
+ * The integer fields are exact; the four sums are bit-reproducible (the scheme of pd_normals_stats: fixed lane, wave and
+ * workgroup order, partials through `workspace`).  Three launches per 2^20 images; capturable.
+ * workspace: >= pd_depth_stats_workspace(N, H, W, K) bytes (never 0, a multiple of 16, monotone), 16-byte aligned.
+ *
+ * Neither call synchronises, allocates or reads the environment.  N == 0 returns PD_OK after the checks.  Every refusal is
+ * PD_EINVAL with a message, decided before the device is touched: null pointers, bad shape, K outside 1 .. 16, a ranged class
+ * with mask == NULL, !(min_depth > 0) or !(max_depth > min_depth), stats / count / workspace not 16-byte aligned, a
+ * too-small workspace (naming the needed size), a frame beyond 2^30 pixels ("too large"), err together with scale. */
+#define PD_DSTAT_BINS         512      /* 0.5 mm bins over |gt - pred|, the last one open-ended */
+#define PD_DSTAT_MAX_CLASSES  16
+#define PD_DSTAT_COUNTERS     4        /* a1, a2, a3, bad */
+#define PD_DSTAT_SUMS         4
+#define PD_DSTAT_RECORD_BYTES 2128     /* 80 + 4 * 512 */
+size_t pd_depth_medians_workspace(int N, int K);
+int pd_depth_medians(const void* gt, const void* pred, const void* mask, const int* classes, int K, void* count, void* med,
+                     void* workspace, size_t ws_bytes, int N, int H, int W, float min_depth, float max_depth, void* stream);
+size_t pd_depth_stats_workspace(int N, int H, int W, int K);
+int pd_depth_stats(const void* gt, const void* pred, const void* mask, const int* classes, int K, const void* scale,
+                   const void* edges, void* err, void* stats, void* workspace, size_t ws_bytes, int N, int H, int W,
+                   float min_depth, float max_depth, void* stream);
+
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward
  * dp[r][:] <- scale * p * (dp - sum(dp * p)).  The score GEMMs (Q K^T, P V and their gradients) are pd_conv2d /

@@ -1,18 +1,19 @@
-// Per-image, per-class records: what pd_normals_stats (normals_stats.hip) and pd_cloud_stats (pointcloud.hip) share.
+// Per-image, per-class records: what pd_normals_stats (normals_stats.hip), pd_cloud_stats (pointcloud.hip) and pd_depth_stats
+// (depth_stats.hip) share.
 //
-// A record is: int64 n, `Counters` further int64 counters, two fp64 sums, padding to 16 bytes, a uint32 histogram of `Bins`
-// bins (Layout).  An evaluator fills its [N][K] records in three launches (run_records):
+// A record is: int64 n, `Counters` further int64 counters, `Sums` fp64 sums (two unless the evaluator asks for more), padding
+// to 16 bytes, a uint32 histogram of `Bins` bins (Layout).  An evaluator fills its [N][K] records in three launches (run_records):
 //   records_zero_kernel      clears the records (the integer fields are filled by atomic adds).
 //   the evaluator's kernel   a workgroup of kThreads lanes belongs to one image; the image's work items go round-robin over
 //                            its G workgroups (groups_for), a lane takes its items in increasing order.  Per workgroup: an
 //                            LDS histogram [K][Bins] and LDS counters [Counters][kMaxK], filled with LDS integer atomics.
-//                            Per lane: the two fp64 sums of every class.  flush_records ends the kernel: the sums are
+//                            Per lane: the fp64 sums of every class.  flush_records ends the kernel: the sums are
 //                            reduced lane -> wave by a fixed shuffle tree and wave -> workgroup in index order, the
-//                            workgroup's [K][2] partial sums go to the workspace with plain stores, and the counters and the
+//                            workgroup's [K][Sums] partial sums go to the workspace with plain stores, and the counters and the
 //                            histogram are flushed with one global add per non-zero word.
-//   records_finalize_kernel  one workgroup per record: n = the sum of the record's bins, and the two fp64 sums from the
+//   records_finalize_kernel  one workgroup per record: n = the sum of the record's bins, and the fp64 sums from the
 //                            image's partials in index order.
-// n, the counters and hist are integer sums: no order can change them.  The two fp64 sums are bit-reproducible: the item ->
+// n, the counters and hist are integer sums: no order can change them.  The fp64 sums are bit-reproducible: the item ->
 // lane assignment depends on the shape only, a lane adds its items in order, and every later step has a fixed order.  No
 // floating-point atomics, no cross-workgroup ticket.
 //
@@ -52,13 +53,14 @@ inline int parse_classes(const char* who, const int* classes, int K, bool have_m
     return PD_OK;
 }
 
-// Bins, the 64-bit counters after n, the 32-bit word where the histogram starts
-template <int Bins, int Counters, int HistWord>
+// Bins, the 64-bit counters after n, the 32-bit word where the histogram starts, the fp64 sums
+template <int Bins, int Counters, int HistWord, int Sums = 2>
 struct Layout {
-    static constexpr int kBins = Bins, kCounters = Counters, kHistWord = HistWord;
-    static constexpr int kSums = 1 + Counters;      // the two fp64 sums, in 8-byte units
+    static constexpr int kBins = Bins, kCounters = Counters, kHistWord = HistWord, kNumSums = Sums;
+    static constexpr int kSums = 1 + Counters;      // where the fp64 sums start, in 8-byte units
     static constexpr int kWords = HistWord + Bins, kBytes = 4 * kWords;
-    static_assert(4 * HistWord >= 8 * (kSums + 2) && kBytes % 16 == 0, "record layout");
+    static_assert(Sums >= 1 && Sums <= kWaves, "the finalize kernel adds one sum per wave");
+    static_assert(4 * HistWord >= 8 * (kSums + Sums) && kBytes % 16 == 0, "record layout");
 };
 
 __global__ __launch_bounds__(kThreads) void records_zero_kernel(uint4* __restrict__ stats, long n16) {
@@ -67,11 +69,12 @@ __global__ __launch_bounds__(kThreads) void records_zero_kernel(uint4* __restric
 }
 
 // The end of an evaluator's kernel, called by every lane of workgroup blockIdx.x = img * G + grp.  s: the lane's sums;
-// wsum: LDS [kWaves][kMaxK][2]; counters: LDS [Counters][kMaxK]; hist: LDS [K][Bins]; stats: the launch's records
+// wsum: LDS [kWaves][kMaxK][Sums]; counters: LDS [Counters][kMaxK]; hist: LDS [K][Bins]; stats: the launch's records
 template <class L>
-__device__ __forceinline__ void flush_records(double (&s)[kMaxK][2], double* wsum, const unsigned* counters,
+__device__ __forceinline__ void flush_records(double (&s)[kMaxK][L::kNumSums], double* wsum, const unsigned* counters,
                                               const unsigned* hist, unsigned* __restrict__ stats, double* __restrict__ ws,
                                               unsigned img, int K) {
+    constexpr int S = L::kNumSums;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // lanes -> wave by a fixed tree, waves -> workgroup in order
 #pragma unroll
@@ -79,20 +82,20 @@ __device__ __forceinline__ void flush_records(double (&s)[kMaxK][2], double* wsu
         if (k < K) {
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
-                s[k][0] += __shfl_down(s[k][0], off);
-                s[k][1] += __shfl_down(s[k][1], off);
+#pragma unroll
+                for (int j = 0; j < S; ++j) s[k][j] += __shfl_down(s[k][j], off);
             }
             if (lane == 0) {
-                wsum[(wave * kMaxK + k) * 2] = s[k][0];
-                wsum[(wave * kMaxK + k) * 2 + 1] = s[k][1];
+#pragma unroll
+                for (int j = 0; j < S; ++j) wsum[(wave * kMaxK + k) * S + j] = s[k][j];
             }
         }
     }
     __syncthreads();
-    if (tid < 2 * K) {
+    if (tid < S * K) {
         double t = 0.0;
-        for (int w = 0; w < kWaves; ++w) t += wsum[w * kMaxK * 2 + tid];
-        ws[((size_t)blockIdx.x * K) * 2 + tid] = t;      // [img][grp][k][2]
+        for (int w = 0; w < kWaves; ++w) t += wsum[w * kMaxK * S + tid];
+        ws[((size_t)blockIdx.x * K) * S + tid] = t;      // [img][grp][k][Sums]
     }
     unsigned* rec = stats + (size_t)img * K * L::kWords;
 #pragma unroll
@@ -126,10 +129,11 @@ __global__ __launch_bounds__(kThreads) void records_finalize_kernel(unsigned* __
         __syncthreads();
     }
     if (tid == 0) *reinterpret_cast<long long*>(rec) = (long long)red[0];
-    if (tid == 64 || tid == 128) {                     // the two fp64 sums, workgroups in index order
-        const int which = tid == 64 ? 0 : 1;
+    constexpr int S = L::kNumSums;
+    if ((tid & 63) == 0 && (tid >> 6) < S) {           // the first lane of wave j adds sum j, workgroups in index order
+        const int which = tid >> 6;
         double t = 0.0;
-        for (int gi = 0; gi < G; ++gi) t += ws[(((size_t)img * G + gi) * K + k) * 2 + which];
+        for (int gi = 0; gi < G; ++gi) t += ws[(((size_t)img * G + gi) * K + k) * S + which];
         reinterpret_cast<double*>(rec)[L::kSums + which] = t;
     }
 }
@@ -139,10 +143,10 @@ inline int groups_for(long items) {
     return (int)std::min<long>(kMaxGroups, std::max<long>(1, (items + kItemsPerGroup - 1) / kItemsPerGroup));
 }
 
-// [N][G][K][2] fp64 partial sums; never zero
-inline size_t records_workspace(int N, int K, int G) {
+// [N][G][K][sums] fp64 partial sums; never zero, a multiple of 16
+inline size_t records_workspace(int N, int K, int G, int sums = 2) {
     const size_t n = N > 0 ? (size_t)N : 1, k = (size_t)std::min(std::max(K, 1), kMaxK);
-    return n * (size_t)G * k * 16;
+    return n * (size_t)G * k * 8 * (size_t)((sums + 1) & ~1);
 }
 
 // zero -> stat -> finalize over the batch in chunks of kMaxImagesPerLaunch images.  stat(n0, nb, records, partials)
@@ -152,7 +156,7 @@ inline void run_records(void* stats, void* workspace, int N, int K, int G, hipSt
     for (long n0 = 0; n0 < N; n0 += kMaxImagesPerLaunch) {
         const long nb = std::min<long>(kMaxImagesPerLaunch, N - n0);
         unsigned* rec = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(stats) + (size_t)n0 * K * L::kBytes);
-        double* part = static_cast<double*>(workspace) + (size_t)n0 * G * K * 2;
+        double* part = static_cast<double*>(workspace) + (size_t)n0 * G * K * L::kNumSums;
         const long n16 = nb * K * (L::kBytes / 16);
         const int zgrid = (int)std::min<long>(1024, (n16 + kThreads - 1) / kThreads);
         hipLaunchKernelGGL(records_zero_kernel, dim3(zgrid), dim3(kThreads), 0, st, reinterpret_cast<uint4*>(rec), n16);

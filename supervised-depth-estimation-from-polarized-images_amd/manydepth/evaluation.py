@@ -15,6 +15,7 @@ from polardepth import cdofp as pdcdofp
 from polardepth import calibration as pdcal
 from polardepth import color as pdcolor
 from polardepth import normals_eval
+from polardepth import depth_eval
 from polardepth import pointcloud
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -212,6 +213,46 @@ class Evaluation:
             if pooled[k][6] > 0:
                 print(f"{name:>8} per-image " + ("&{: 9.4f} " * 7).format(*per_image[k].tolist()))
                 print(f"{name:>8} pooled    " + ("&{: 9.4f} " * 7).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
+        return results
+
+    @torch.no_grad()
+    def test_depth(self, median_scaling=None):
+        """Depth accuracy per class in one pass (polardepth.depth_eval): what ``test`` reports -- and the pooled figures, the
+        distribution of the absolute error and the count of unusable predictions -- for the whole frame, all objects and each
+        material, one pd_depth_stats call per batch.  ``median_scaling``: None, or "numpy" / "torch" to rescale the prediction
+        of every image and class by the ratio of the medians first (trainer.py:1416 / :1344), for models without metric
+        supervision.  Prints, and returns {class: {"per_image": [13], "pooled": [13], "bad": int}} with abs_rel, sq_rel, rmse,
+        rmse_log, a1, a2, a3, the mean and the median of |d| in millimetres, the shares of |d| below 5 / 10 / 20 mm and the
+        pixel count: "per_image" is the mean over images of the per-image figures (the reference's and ``test``'s convention;
+        images without a pixel of the class do not count), "pooled" takes all pixels of all images as one set.  The records
+        stay on the device until the loop is over."""
+        total, sums, counts = None, None, None
+        for inputs in self.test_loader:
+            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+            depth = self.predict(inputs)
+            st = depth_eval.depth_stats(depth, inputs["depth_gt"], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
+                                        max_depth=self.max_depth, median_scaling=median_scaling)
+            m = st.metrics()
+            valid = st.n > 0
+            s = torch.where(valid[..., None], m, torch.zeros_like(m)).sum(0)
+            if total is None:
+                total, sums, counts = st, s, valid.sum(0)
+            else:
+                total += st
+                sums += s
+                counts += valid.sum(0)
+        if total is None:
+            return {}
+        per_image = sums / counts[:, None].double()
+        per_image, pooled, bad = per_image.cpu().numpy(), total.pooled().cpu().numpy(), total.pooled_bad().cpu().numpy()
+        results = {}
+        nm = len(depth_eval.METRIC_NAMES)
+        print(f"depth ({median_scaling or 'unscaled'}) " + ("{:>9} " * nm).format(*depth_eval.METRIC_NAMES))
+        for k, name in enumerate(total.names):
+            results[name] = {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k])}
+            if pooled[k][nm - 1] > 0:
+                print(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
+                print(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
         return results
 
     @torch.no_grad()

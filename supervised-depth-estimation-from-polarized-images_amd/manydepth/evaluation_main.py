@@ -1,5 +1,6 @@
 """reference manydepth/evaluation_main.py:7-10; PD_EVAL_NORMALS=1 adds the surface-normal report (Evaluation.test_normals),
-PD_EVAL_POINTCLOUD=1 the point-cloud report (Evaluation.test_pointcloud)."""
+PD_EVAL_POINTCLOUD=1 the point-cloud report (Evaluation.test_pointcloud), PD_EVAL_DEPTH=1 the one-pass depth report
+(Evaluation.test_depth), median-scaled with PD_EVAL_MEDIAN_SCALING=numpy or torch."""
 import os
 
 from manydepth.evaluation import Evaluation
@@ -13,6 +14,8 @@ def main():
         ev.test_normals()
     if os.environ.get("PD_EVAL_POINTCLOUD") == "1":
         ev.test_pointcloud()
+    if os.environ.get("PD_EVAL_DEPTH") == "1":
+        ev.test_depth(median_scaling=os.environ.get("PD_EVAL_MEDIAN_SCALING") or None)
 
 
 if __name__ == "__main__":

@@ -135,6 +135,10 @@ SIGNATURES = {
     "pd_cloud_nn": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _u, _i, _vp]),
     "pd_cloud_stats_workspace": (_sz, [_i, _i, _i, _i]),
     "pd_cloud_stats": (_i, [_vp, _vp, _vp, _ip, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pd_depth_medians_workspace": (_sz, [_i, _i]),
+    "pd_depth_medians": (_i, [_vp, _vp, _vp, _ip, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
+    "pd_depth_stats_workspace": (_sz, [_i, _i, _i, _i]),
+    "pd_depth_stats": (_i, [_vp, _vp, _vp, _ip, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
 }
 
 

@@ -552,7 +552,7 @@ int pd_loss_weights(const void* gvals, const int* scale_ids, int S, float w_norm
 
 /* SSIM map (mode 0, layers.py:468-499) or the photometric reprojection loss of trainer.py:1069-1081 (mode 1:
  * out [N,1,H,W] = 0.85 * mean_c SSIM + 0.15 * mean_c |y - x|, or the L1 part alone when no_ssim).  x, y planar
- * NCHW fp32.  Inactive under --depth_supervision_only; forward only. */
+ * NCHW fp32.  Inactive under --depth_supervision_only; the photometric mode (below) runs mode 1 with its gradient. */
 int pd_ssim_fwd(const void* x, const void* y, void* out, int N, int C, int H, int W, int mode, int no_ssim,
                 void* stream);
 /* Gradient of pd_ssim_fwd w.r.t. both images: gout [N,C,H,W] (mode 0) or [N,1,H,W] (mode 1), gx / gy [N,C,H,W] (gy may be
@@ -560,6 +560,71 @@ int pd_ssim_fwd(const void* x, const void* y, void* out, int N, int C, int H, in
  * the gather over the (reflected) 3x3 windows that contain each pixel. */
 int pd_ssim_bwd(const void* x, const void* y, const void* gout, void* coef_ws, void* gx, void* gy, int N, int C, int H, int W,
                 int mode, int no_ssim, void* stream);
+
+/* ------------------------------------------------------------------------- photometric multi-view term (csrc/reproj.hip)
+ * Training with --depth_supervision True --pose_input True (without --depth_supervision_only): the neighbouring frames
+ * are warped into the current view with the predicted depth and the ground-truth relative pose, and monodepth2's
+ * reprojection loss (pd_ssim_fwd mode 1), reduced over the frames by minimum with automasking, joins the supervised terms
+ * (trainer.py:479-530, 983-1067, 1069-1098, 1150-1236).
+ *
+ * pd_view_synth_fwd -- BackprojectDepth + Project3D + F.grid_sample(bilinear, padding_mode="border", align_corners=True)
+ * (layers.py:383-443, trainer.py:1021-1044) for one source frame.
+ *   depth  [N,1,H,W] fp32      src [N,C,H,W] planar fp32      K, inv_K, T [N,4,4] fp32 row-major
+ *   warped [N,C,H,W] fp32 out  coords [N,H,W,2] fp32 out (8-byte aligned): (u, v) of every pixel, UNCLAMPED
+ * Per pixel (x, y), evaluated in fp64 from the fp32 inputs, every sum left to right as written, no fused multiply-add:
+ *   P[i][j] = K[i][0] T[0][j] + K[i][1] T[1][j] + K[i][2] T[2][j] + K[i][3] T[3][j]      (i < 3; once per batch item)
+ *   r[i]    = inv_K[i][0] x + inv_K[i][1] y + inv_K[i][2]                                 (i < 3)
+ *   p       = depth * r
+ *   h[i]    = P[i][0] p[0] + P[i][1] p[1] + P[i][2] p[2] + P[i][3]
+ *   u = h[0] / (h[2] + 1e-7),  v = h[1] / (h[2] + 1e-7)
+ * rounded once to fp32 and stored in coords.  Under align_corners=True Project3D's division by W-1 / H-1, its (. - 0.5) * 2
+ * and grid_sample's un-normalisation cancel, so (u, v) are source pixel coordinates.  Sampling, in fp32 from the stored
+ * coordinate: uc = min(max(u, 0), W-1), vc likewise with H-1 (a non-finite coordinate becomes 0); x0 = floor(uc),
+ * x1 = min(x0 + 1, W-1), wx1 = uc - x0, wx0 = 1 - wx1 (y likewise);
+ *   warped = ((src[y0][x0] (wx0 wy0) + src[y0][x1] (wx1 wy0)) + src[y1][x0] (wx0 wy1)) + src[y1][x1] (wx1 wy1).
+ *
+ * pd_view_synth_bwd -- the gradient w.r.t. depth alone (the sources are data, and so is T under --pose_input): each output
+ * pixel depends on its own depth only, hence no scatter and no atomics.
+ *   gdepth [N,1,H,W] (=, or += when accumulate != 0) = sum_c gwarped_c (d warped_c / du * du/ddepth + d warped_c / dv * dv/ddepth)
+ * d warped / d(u, v) from the four taps with the weights of `coords`; it is exactly zero on an axis whose coordinate is
+ * <= 0, >= size-1 or not finite (PyTorch's border rule).  With h = depth * q + b, q = P[:, :3] r:
+ *   du/ddepth = (q[0] - u q[2]) / (h[2] + 1e-7), dv/ddepth = (q[1] - v q[2]) / (h[2] + 1e-7), in fp64 as above.
+ * Limits of both: 0 <= N <= 65535 (N = 0 does nothing), C, H, W > 0, H * W <= 2^30.
+ *
+ * pd_depth_to_updisp_bwd -- gup[i] = -gdepth[i] * depth[i]^2 * (1/min_depth - 1/max_depth): the gradient of
+ * depth = 1 / (min_disp + (max_disp - min_disp) * up) w.r.t. the upsampled disparity `up` (layers.py:62-71), n elements;
+ * pd_up_gather_bwd carries it on to the disparity map.  gup may alias gdepth. */
+#define PD_REPROJ_MAX_FRAMES 8
+int pd_view_synth_fwd(const void* depth, const void* src, const void* K, const void* inv_K, const void* T, void* warped,
+                      void* coords, int N, int C, int H, int W, void* stream);
+int pd_view_synth_bwd(const void* gwarped, const void* src, const void* coords, const void* depth, const void* K,
+                      const void* inv_K, const void* T, void* gdepth, int N, int C, int H, int W, int accumulate,
+                      void* stream);
+int pd_depth_to_updisp_bwd(const void* gdepth, const void* depth, void* gup, long n, float min_depth, float max_depth,
+                           void* stream);
+/* pd_reproj_combine_fwd -- trainer.py:1163-1215 over F <= PD_REPROJ_MAX_FRAMES neighbouring frames.
+ *   reproj    host array of F device pointers, each an [N,1,H,W] fp32 map of compute_reprojection_loss(warped_f, target)
+ *   identity  the same for the unwarped sources (automasking), or NULL: no automasking, the mask is all ones
+ *   noise     [N,1,H,W] fp32 added to the identity value (trainer.py:1193-1194), or NULL; needs identity
+ *   valid     [N,F] fp32, 0 = frame f of item n does not exist, or NULL: all valid
+ * Per pixel: m = the minimum of the valid frames' reproj values (the first valid frame, a later one only when strictly
+ * smaller), or with avg != 0 their mean (sum in frame order / number of valid frames); the same over the identity maps,
+ * plus noise; mask = m <= identity + noise (argmin index 0: a tie goes to the reprojection).  An invalid frame never wins
+ * a minimum, and a pixel of an item without a valid frame has mask 0.
+ *   sel   [N,H,W] uint8 out: the winning frame (0 with avg), 255 where the mask is 0 -- what the backward pass needs
+ *   sums  2 doubles out (8-byte aligned): sum(m * mask), sum(mask);   loss 1 float out = sums[0] / (sums[1] + 1e-7)
+ * Both sums are accumulated in fp64 in a fixed order: per thread over its grid-stride pixels, per wavefront by shuffles,
+ * per workgroup, one row of partial_ws (pd_reproj_combine_rows(N,H,W) * 2 doubles, 8-byte aligned) per workgroup, then
+ * one workgroup sums the rows (a second launch, like pd_loss_finalize).  Bit-reproducible, no host synchronisation.
+ * pd_reproj_combine_bwd -- greproj (F device pointers, [N,1,H,W] fp32 out): gloss[0] / (sums[1] + 1e-7) in the winning
+ * frame's map and 0 elsewhere; with avg that value / (number of valid frames) in every valid frame's map of an unmasked
+ * pixel.  gloss: 1 float on the device. */
+int pd_reproj_combine_rows(int N, int H, int W);
+int pd_reproj_combine_fwd(const void* const* reproj, const void* const* identity, int F, const void* noise,
+                          const void* valid, void* sel, void* partial_ws, void* sums, void* loss, int N, int H, int W,
+                          int avg, void* stream);
+int pd_reproj_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid, void* const* greproj,
+                          int F, int N, int H, int W, int avg, void* stream);
 /* compute_depth_errors (layers.py:539-557) per image on the device: metrics [N][8] = abs_rel, sq_rel, rmse,
  * rmse_log, a1, a2, a3, pixel count over min < gt < max (and mask == mask_value when mask != NULL, the
  * per-material selection of trainer.py:1385-1411); pred is clamped to [min, max] (trainer.py:1422-1423).

@@ -1,0 +1,374 @@
+// Photometric multi-view term: view synthesis from depth and a known relative pose, and the minimum / automask
+// reduction over the neighbouring frames.
+//
+// Reference restated:
+//   layers.py:383-413     BackprojectDepth   cam = depth * (inv_K[:3,:3] (x, y, 1))
+//   layers.py:416-443     Project3D          pix = (K T)[:3,:] (cam, 1);  (u, v) = pix.xy / (pix.z + 1e-7), normalised
+//   trainer.py:1041-1044  F.grid_sample(source, pix, padding_mode="border", align_corners=True)
+//   trainer.py:1084-1098  compute_loss_masks (argmin over [reprojection, identity])
+//   trainer.py:1163-1215  minimum (or mean) over the frames, identity + noise, masked mean
+// With align_corners=True the division by W-1 / H-1, the (. - 0.5) * 2 of Project3D and grid_sample's own
+// un-normalisation cancel: (u, v) ARE source pixel coordinates, and that is what `coords` holds.
+//
+// Gather / stream kernels.  blockIdx.y is the batch item, so K, inv_K and T are the same for a whole workgroup: the first
+// 12 + 9 threads form (K T)[:3,:] and inv_K[:3,:3] in fp64 into LDS once, every pixel reads them back as broadcasts.
+// Depth reads and warped / coords / gdepth writes are coalesced (thread = pixel, x fastest); the four taps of a pixel
+// are gathers whose locality is that of the warp itself.  No atomics: an output pixel depends on its own depth alone.
+#include "pd_common.h"
+
+namespace {
+
+constexpr int RT = 256;
+constexpr int RP_MAX_FRAMES = 8;   // = PD_REPROJ_MAX_FRAMES
+
+// ------------------------------------------------------------------ camera of one batch item, in LDS
+struct CamLds {
+    double P[12];   // (K T)[:3,:], row-major 3x4
+    double iK[9];   // inv_K[:3,:3]
+};
+
+__device__ __forceinline__ void load_cam(CamLds& cam, const float* __restrict__ K, const float* __restrict__ iK,
+                                         const float* __restrict__ T, long n) {
+    const int t = threadIdx.x;
+    if (t < 12) {
+        const int i = t >> 2, j = t & 3;
+        const float* k = K + n * 16 + i * 4;
+        const float* c = T + n * 16 + j;
+        // k ascending, plain multiply-adds (the file is built with -ffp-contract=off)
+        cam.P[t] = (((double)k[0] * (double)c[0] + (double)k[1] * (double)c[4]) + (double)k[2] * (double)c[8]) +
+                   (double)k[3] * (double)c[12];
+    } else if (t < 21) {
+        const int q = t - 12;
+        cam.iK[q] = (double)iK[n * 16 + (q / 3) * 4 + q % 3];
+    }
+    __syncthreads();
+}
+
+// steps 1-4 of the header in fp64; q = A r is returned for the backward pass (h = depth * q + b)
+__device__ __forceinline__ void project(const CamLds& cam, int x, int y, double d, double& u, double& v, double& hz,
+                                        double (&q)[3]) {
+    const double xd = (double)x, yd = (double)y;
+    double r[3], h[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] = (cam.iK[3 * i] * xd + cam.iK[3 * i + 1] * yd) + cam.iK[3 * i + 2];
+    const double p0 = d * r[0], p1 = d * r[1], p2 = d * r[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        h[i] = ((cam.P[4 * i] * p0 + cam.P[4 * i + 1] * p1) + cam.P[4 * i + 2] * p2) + cam.P[4 * i + 3];
+        q[i] = (cam.P[4 * i] * r[0] + cam.P[4 * i + 1] * r[1]) + cam.P[4 * i + 2] * r[2];
+    }
+    hz = h[2] + 1e-7;
+    u = h[0] / hz;
+    v = h[1] / hz;
+}
+
+// border padding of one axis: the clamped coordinate, its cell and the weight of the upper tap; `free_axis` is false where
+// the coordinate was clamped (PyTorch's rule: c <= 0 or c >= size-1) or is not finite -- the gradient is then exactly zero
+struct Axis {
+    int i0, i1;
+    float w1;
+    bool free_axis;
+};
+__device__ __forceinline__ Axis axis_of(float c, int size) {
+    Axis a;
+    const float hi = (float)(size - 1);
+    a.free_axis = (c > 0.f) && (c < hi);          // false for NaN and both infinities as well
+    float cc = c;
+    if (!(fabsf(c) <= 3.0e38f)) cc = 0.f;         // non-finite -> 0
+    cc = fminf(fmaxf(cc, 0.f), hi);
+    const float f = floorf(cc);
+    a.i0 = (int)f;
+    a.i1 = a.i0 + (a.i0 < size - 1);              // cc == size-1: the upper tap has weight 0, keep it in bounds
+    a.w1 = cc - f;
+    return a;
+}
+
+__global__ __launch_bounds__(RT) void view_synth_fwd_kernel(const float* __restrict__ depth, const float* __restrict__ src,
+                                                            const float* __restrict__ K, const float* __restrict__ iK,
+                                                            const float* __restrict__ T, float* __restrict__ warped,
+                                                            float2* __restrict__ coords, int C, int H, int W) {
+    __shared__ CamLds cam;
+    const long n = blockIdx.y;
+    load_cam(cam, K, iK, T, n);
+    const int HW = H * W;
+    const float* s = src + n * C * (long)HW;
+    for (int i = blockIdx.x * RT + threadIdx.x; i < HW; i += gridDim.x * RT) {
+        const int y = i / W, x = i - y * W;
+        double u, v, hz, q[3];
+        project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q);
+        const float uf = (float)u, vf = (float)v;
+        coords[n * HW + i] = make_float2(uf, vf);
+        const Axis ax = axis_of(uf, W), ay = axis_of(vf, H);
+        const float wx0 = 1.f - ax.w1, wy0 = 1.f - ay.w1;
+        const float w00 = wx0 * wy0, w10 = ax.w1 * wy0, w01 = wx0 * ay.w1, w11 = ax.w1 * ay.w1;
+        const int o00 = ay.i0 * W + ax.i0, o10 = ay.i0 * W + ax.i1, o01 = ay.i1 * W + ax.i0, o11 = ay.i1 * W + ax.i1;
+        for (int c = 0; c < C; ++c) {
+            const float* pc = s + (long)c * HW;
+            warped[(n * C + c) * (long)HW + i] = ((pc[o00] * w00 + pc[o10] * w10) + pc[o01] * w01) + pc[o11] * w11;
+        }
+    }
+}
+
+__global__ __launch_bounds__(RT) void view_synth_bwd_kernel(const float* __restrict__ gw, const float* __restrict__ src,
+                                                            const float2* __restrict__ coords, const float* __restrict__ depth,
+                                                            const float* __restrict__ K, const float* __restrict__ iK,
+                                                            const float* __restrict__ T, float* __restrict__ gdepth, int C,
+                                                            int H, int W, int accumulate) {
+    __shared__ CamLds cam;
+    const long n = blockIdx.y;
+    load_cam(cam, K, iK, T, n);
+    const int HW = H * W;
+    const float* s = src + n * C * (long)HW;
+    for (int i = blockIdx.x * RT + threadIdx.x; i < HW; i += gridDim.x * RT) {
+        const int y = i / W, x = i - y * W;
+        const float2 uv = coords[n * HW + i];
+        const Axis ax = axis_of(uv.x, W), ay = axis_of(uv.y, H);
+        float g = 0.f;
+        if (ax.free_axis || ay.free_axis) {
+            const float wx0 = 1.f - ax.w1, wy0 = 1.f - ay.w1;
+            const int o00 = ay.i0 * W + ax.i0, o10 = ay.i0 * W + ax.i1, o01 = ay.i1 * W + ax.i0, o11 = ay.i1 * W + ax.i1;
+            float gu = 0.f, gv = 0.f;             // sum_c gw_c * d warped_c / d(u, v)
+            for (int c = 0; c < C; ++c) {
+                const float* pc = s + (long)c * HW;
+                const float v00 = pc[o00], v10 = pc[o10], v01 = pc[o01], v11 = pc[o11];
+                const float gc = gw[(n * C + c) * (long)HW + i];
+                gu += gc * ((v10 - v00) * wy0 + (v11 - v01) * ay.w1);
+                gv += gc * ((v01 - v00) * wx0 + (v11 - v10) * ax.w1);
+            }
+            double u, v, hz, q[3];
+            project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q);
+            // h = depth * q + b:  d u / d depth = (q.x - u q.z) / (h.z + 1e-7), likewise v
+            const double du = ax.free_axis ? (q[0] - u * q[2]) / hz : 0.0;
+            const double dv = ay.free_axis ? (q[1] - v * q[2]) / hz : 0.0;
+            g = (float)((double)gu * du + (double)gv * dv);
+        }
+        gdepth[n * HW + i] = accumulate ? gdepth[n * HW + i] + g : g;
+    }
+}
+
+// gup = -gdepth * depth^2 * (1/min_depth - 1/max_depth): depth = 1 / (min_disp + (max_disp - min_disp) * up) backwards
+__global__ __launch_bounds__(RT) void depth_to_updisp_bwd_kernel(const float* __restrict__ gdepth, const float* __restrict__ depth,
+                                                                 float* __restrict__ gup, long total, float disp_range) {
+    for (long i = blockIdx.x * (long)RT + threadIdx.x; i < total; i += (long)gridDim.x * RT) {
+        const float d = depth[i];
+        gup[i] = gdepth[i] * (-disp_range * d * d);
+    }
+}
+
+// ------------------------------------------------------------------ minimum / mean over frames, automask, masked sums
+struct FrameArgs {
+    const float* reproj[RP_MAX_FRAMES];
+    const float* identity[RP_MAX_FRAMES];
+    float* greproj[RP_MAX_FRAMES];
+};
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// one value over the valid frames of a pixel: the minimum and its frame (the first valid frame is taken, a later one only
+// when it is strictly smaller: the earlier frame wins a tie), or the mean (sum in frame order / number of valid frames,
+// frame 0 reported)
+__device__ __forceinline__ float over_frames(const float* const* maps, const float* __restrict__ vrow, int F, long i, int avg,
+                                             int& nvalid, int& arg) {
+    float m = 0.f;
+    nvalid = 0;
+    arg = 255;
+    for (int f = 0; f < F; ++f) {
+        if (vrow && vrow[f] == 0.f) continue;
+        const float r = maps[f][i];
+        ++nvalid;
+        if (avg) m += r;
+        else if (arg == 255 || r < m) { m = r; arg = f; }
+    }
+    if (avg && nvalid) { m = m / (float)nvalid; arg = 0; }
+    return m;
+}
+
+__global__ __launch_bounds__(RT) void combine_fwd_kernel(const FrameArgs a, int F, int has_identity,
+                                                         const float* __restrict__ noise, const float* __restrict__ valid,
+                                                         unsigned char* __restrict__ sel, double* __restrict__ partial, int N,
+                                                         int HW, int avg) {
+    __shared__ double sm[4 * 2];
+    const long total = (long)N * HW;
+    double acc_s = 0.0, acc_c = 0.0;
+    for (long i = blockIdx.x * (long)RT + threadIdx.x; i < total; i += (long)gridDim.x * RT) {
+        const long n = i / HW;
+        const float* vrow = valid ? valid + n * F : nullptr;
+        int nv, arg, nvi, argi;
+        const float m = over_frames(a.reproj, vrow, F, i, avg, nv, arg);
+        bool keep = nv > 0;
+        if (keep && has_identity) {
+            float idm = over_frames(a.identity, vrow, F, i, avg, nvi, argi);
+            if (noise) idm += noise[i];
+            keep = m <= idm;                      // argmin index 0: a tie goes to the reprojection
+        }
+        sel[i] = keep ? (unsigned char)arg : (unsigned char)255;
+        if (keep) { acc_s += (double)m; acc_c += 1.0; }
+    }
+    acc_s = wave_sum_d(acc_s);
+    acc_c = wave_sum_d(acc_c);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sm[wave * 2] = acc_s; sm[wave * 2 + 1] = acc_c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x * 2] = ((sm[0] + sm[2]) + sm[4]) + sm[6];
+        partial[blockIdx.x * 2 + 1] = ((sm[1] + sm[3]) + sm[5]) + sm[7];
+    }
+}
+
+// one workgroup: thread t sums rows t, t + 256, ... then a tree over LDS (the order of loss_finalize_kernel)
+__global__ __launch_bounds__(256) void combine_finalize_kernel(const double* __restrict__ partial, int rows,
+                                                               double* __restrict__ sums, float* __restrict__ loss) {
+    __shared__ double s0[256], s1[256];
+    double a = 0.0, b = 0.0;
+    for (int r = threadIdx.x; r < rows; r += 256) { a += partial[2 * r]; b += partial[2 * r + 1]; }
+    s0[threadIdx.x] = a; s1[threadIdx.x] = b;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) { s0[threadIdx.x] += s0[threadIdx.x + k]; s1[threadIdx.x] += s1[threadIdx.x + k]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        sums[0] = s0[0];
+        sums[1] = s1[0];
+        loss[0] = (float)(s0[0] / (s1[0] + 1e-7));
+    }
+}
+
+__global__ __launch_bounds__(RT) void combine_bwd_kernel(const FrameArgs a, int F, const float* __restrict__ gloss,
+                                                         const unsigned char* __restrict__ sel, const double* __restrict__ sums,
+                                                         const float* __restrict__ valid, int N, int HW, int avg) {
+    const long total = (long)N * HW;
+    const float g = (float)((double)gloss[0] / (sums[1] + 1e-7));
+    for (long i = blockIdx.x * (long)RT + threadIdx.x; i < total; i += (long)gridDim.x * RT) {
+        const int s = sel[i];
+        if (!avg) {
+            for (int f = 0; f < F; ++f) a.greproj[f][i] = (s == f) ? g : 0.f;
+            continue;
+        }
+        const float* vrow = valid ? valid + (i / HW) * F : nullptr;
+        int nv = 0;
+        for (int f = 0; f < F; ++f) nv += !(vrow && vrow[f] == 0.f);
+        const float ga = (s != 255 && nv) ? g / (float)nv : 0.f;
+        for (int f = 0; f < F; ++f) a.greproj[f][i] = (vrow && vrow[f] == 0.f) ? 0.f : ga;
+    }
+}
+
+inline unsigned rgrid(long n) {
+    long b = (n + RT - 1) / RT;
+    if (b > 2048) b = 2048;
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
+
+// blocks along x for a per-item grid (blockIdx.y = item): about 4096 workgroups in all, the rest by grid stride
+inline unsigned item_grid(int N, long HW) {
+    long b = (HW + RT - 1) / RT;
+    const long cap = N >= 4096 ? 1 : 4096 / N;
+    if (b > cap) b = cap;
+    return (unsigned)(b < 1 ? 1 : b);
+}
+
+}  // namespace
+
+// ============================================================================ C ABI
+static int view_synth_args(const char* who, const void* depth, const void* src, const void* K, const void* inv_K, const void* T,
+                           int N, int C, int H, int W) {
+    PD_REQUIRE(depth && src && K && inv_K && T, "%s: depth, src, K, inv_K and T must not be null", who);
+    PD_REQUIRE(N >= 0 && N <= 65535 && C > 0 && H > 0 && W > 0, "%s: bad shape N=%d C=%d H=%d W=%d (0 <= N <= 65535)", who, N, C, H, W);
+    PD_REQUIRE((long)H * W <= (1L << 30), "%s: image too large (%d x %d): offsets inside a plane are 32-bit", who, H, W);
+    return PD_OK;
+}
+
+extern "C" int pd_view_synth_fwd(const void* depth, const void* src, const void* K, const void* inv_K, const void* T,
+                                 void* warped, void* coords, int N, int C, int H, int W, void* stream) {
+    if (int rc = view_synth_args("pd_view_synth_fwd", depth, src, K, inv_K, T, N, C, H, W)) return rc;
+    PD_REQUIRE(warped && coords, "pd_view_synth_fwd: warped and coords must not be null");
+    PD_REQUIRE((reinterpret_cast<uintptr_t>(coords) & 7u) == 0, "pd_view_synth_fwd: coords must be 8-byte aligned");
+    if (N == 0) return PD_OK;
+    hipLaunchKernelGGL(view_synth_fwd_kernel, dim3(item_grid(N, (long)H * W), N), dim3(RT), 0, (hipStream_t)stream,
+                       (const float*)depth, (const float*)src, (const float*)K, (const float*)inv_K, (const float*)T,
+                       (float*)warped, (float2*)coords, C, H, W);
+    return pd::check_launch("pd_view_synth_fwd");
+}
+
+extern "C" int pd_view_synth_bwd(const void* gwarped, const void* src, const void* coords, const void* depth, const void* K,
+                                 const void* inv_K, const void* T, void* gdepth, int N, int C, int H, int W, int accumulate,
+                                 void* stream) {
+    if (int rc = view_synth_args("pd_view_synth_bwd", depth, src, K, inv_K, T, N, C, H, W)) return rc;
+    PD_REQUIRE(gwarped && coords && gdepth, "pd_view_synth_bwd: gwarped, coords and gdepth must not be null");
+    PD_REQUIRE((reinterpret_cast<uintptr_t>(coords) & 7u) == 0, "pd_view_synth_bwd: coords must be 8-byte aligned");
+    if (N == 0) return PD_OK;
+    hipLaunchKernelGGL(view_synth_bwd_kernel, dim3(item_grid(N, (long)H * W), N), dim3(RT), 0, (hipStream_t)stream,
+                       (const float*)gwarped, (const float*)src, (const float2*)coords, (const float*)depth, (const float*)K,
+                       (const float*)inv_K, (const float*)T, (float*)gdepth, C, H, W, accumulate);
+    return pd::check_launch("pd_view_synth_bwd");
+}
+
+extern "C" int pd_depth_to_updisp_bwd(const void* gdepth, const void* depth, void* gup, long n, float min_depth, float max_depth,
+                                      void* stream) {
+    PD_REQUIRE(gdepth && depth && gup, "pd_depth_to_updisp_bwd: gdepth, depth and gup must not be null");
+    PD_REQUIRE(n >= 0, "pd_depth_to_updisp_bwd: bad element count %ld", n);
+    PD_REQUIRE(min_depth > 0 && max_depth > min_depth, "pd_depth_to_updisp_bwd: bad depth range");
+    if (n == 0) return PD_OK;
+    hipLaunchKernelGGL(depth_to_updisp_bwd_kernel, dim3(rgrid(n)), dim3(RT), 0, (hipStream_t)stream, (const float*)gdepth,
+                       (const float*)depth, (float*)gup, n, 1.f / min_depth - 1.f / max_depth);
+    return pd::check_launch("pd_depth_to_updisp_bwd");
+}
+
+extern "C" int pd_reproj_combine_rows(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 1;
+    return (int)rgrid((long)N * H * W);
+}
+
+static int combine_args(const char* who, int F, int N, int H, int W, int avg) {
+    PD_REQUIRE(F >= 1 && F <= RP_MAX_FRAMES, "%s: 1 <= F <= %d frames, got %d", who, RP_MAX_FRAMES, F);
+    PD_REQUIRE(N >= 0 && H > 0 && W > 0, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    PD_REQUIRE((long)H * W <= (1L << 30), "%s: image too large (%d x %d)", who, H, W);
+    PD_REQUIRE(avg == 0 || avg == 1, "%s: avg must be 0 or 1, got %d", who, avg);
+    return PD_OK;
+}
+
+extern "C" int pd_reproj_combine_fwd(const void* const* reproj, const void* const* identity, int F, const void* noise,
+                                     const void* valid, void* sel, void* partial_ws, void* sums, void* loss, int N, int H,
+                                     int W, int avg, void* stream) {
+    if (int rc = combine_args("pd_reproj_combine_fwd", F, N, H, W, avg)) return rc;
+    PD_REQUIRE(reproj && sel && partial_ws && sums && loss,
+               "pd_reproj_combine_fwd: reproj, sel, partial_ws, sums and loss must not be null");
+    PD_REQUIRE(identity || !noise, "pd_reproj_combine_fwd: noise is added to the identity maps, which are null");
+    PD_REQUIRE((reinterpret_cast<uintptr_t>(partial_ws) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7u) == 0,
+               "pd_reproj_combine_fwd: partial_ws and sums must be 8-byte aligned");
+    FrameArgs a = {};
+    for (int f = 0; f < F; ++f) {
+        PD_REQUIRE(reproj[f] && (!identity || identity[f]), "pd_reproj_combine_fwd: map %d is null", f);
+        a.reproj[f] = (const float*)reproj[f];
+        a.identity[f] = identity ? (const float*)identity[f] : nullptr;
+    }
+    const int rows = pd_reproj_combine_rows(N, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    // N == 0: one workgroup writes a zero partial row, the loss is 0 / 1e-7 = 0
+    hipLaunchKernelGGL(combine_fwd_kernel, dim3(rows), dim3(RT), 0, st, a, F, identity ? 1 : 0, (const float*)noise,
+                       (const float*)valid, (unsigned char*)sel, (double*)partial_ws, N, H * W, avg);
+    hipLaunchKernelGGL(combine_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)partial_ws, rows, (double*)sums,
+                       (float*)loss);
+    return pd::check_launch("pd_reproj_combine_fwd");
+}
+
+extern "C" int pd_reproj_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid,
+                                     void* const* greproj, int F, int N, int H, int W, int avg, void* stream) {
+    if (int rc = combine_args("pd_reproj_combine_bwd", F, N, H, W, avg)) return rc;
+    PD_REQUIRE(gloss && sel && sums && greproj, "pd_reproj_combine_bwd: gloss, sel, sums and greproj must not be null");
+    PD_REQUIRE((reinterpret_cast<uintptr_t>(sums) & 7u) == 0, "pd_reproj_combine_bwd: sums must be 8-byte aligned");
+    FrameArgs a = {};
+    for (int f = 0; f < F; ++f) {
+        PD_REQUIRE(greproj[f], "pd_reproj_combine_bwd: map %d is null", f);
+        a.greproj[f] = (float*)greproj[f];
+    }
+    if (N == 0) return PD_OK;
+    hipLaunchKernelGGL(combine_bwd_kernel, dim3(rgrid((long)N * H * W)), dim3(RT), 0, (hipStream_t)stream, a, F,
+                       (const float*)gloss, (const unsigned char*)sel, (const double*)sums, (const float*)valid, N, H * W, avg);
+    return pd::check_launch("pd_reproj_combine_bwd");
+}

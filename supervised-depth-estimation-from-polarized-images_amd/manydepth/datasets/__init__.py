@@ -41,6 +41,14 @@ modality, and neither ``rgb/`` nor ``pol00`` .. ``pol11`` is needed.  The frame 
 ``("pol_cdofp", 0, 0)`` [1,H4,W4] with the augmentation draw ``"color_jitter"`` (the draw of ``raw_color``); the item carries
 no colour pyramid and no ``("pol", 0, 0)``: Trainer.process_batch / Evaluation.predict make both on the device
 (polardepth/cdofp.py).  The intrinsics are scaled by the frame's own size.
+
+Neighbouring frames (``frame_idxs`` other than ``[0]``, the photometric mode ``--depth_supervision True --pose_input True``):
+for every index ``i != 0`` an item also carries ``("color", i, 0)`` float32 [3,H,W], the frame ``idx + i * offset`` resized
+with LANCZOS like frame 0; ``("poses", i)`` float32 [4,4] = ``inv(inv(T_c) @ T_s)`` in fp64 from ``_pose/%06d.txt`` of frame 0
+and of the neighbour (hammer_dataset.py:104-132); and ``("frame_valid", i)`` float32 scalar, 1 -- or 0 with a zero picture and
+the identity pose where the neighbour or one of the pose files does not exist (the reference substitutes a dummy picture,
+indoor_dataset.py:361-366).  With ``frame_idxs == [0]`` an item is, key for key and bit for bit, what it was without this.
+``raw_color`` applies to frame 0 only; ``pol_cdofp`` has no ``rgb/`` folder and refuses neighbours.
 """
 import glob
 import os
@@ -103,6 +111,14 @@ class HAMMER_Dataset(Dataset):
         self.pol_cdofp = (os.environ.get("PD_POL_CDOFP") == "1") if pol_cdofp is None else bool(pol_cdofp)
         if self.pol_cdofp and self.pol_dofp:
             raise ValueError("HAMMER_Dataset: pol_dofp and pol_cdofp name two different sensors; choose one")
+        # frame_idxs: 0 and the neighbours of the trajectory the photometric term warps into frame 0 (trainer.py:1006-1044);
+        # neighbour i is frame idx + i * offset (indoor_dataset.py:319-320).  [0] = the single-frame items of the supervised mode
+        self.frame_idxs = [int(i) for i in (frame_idxs if frame_idxs is not None else [0])]
+        self.neighbours = [i for i in self.frame_idxs if i != 0]
+        self.offset = int(offset)
+        if self.neighbours and self.pol_cdofp:
+            raise ValueError("HAMMER_Dataset: pol_cdofp frames have no rgb/ folder to take neighbouring colour frames from; "
+                             "frame_idxs must be [0]")
         self.data_path, self.modality, self.depth_modality, self.img_ext = data_path, modality, depth_modality, img_ext
         self.height, self.width, self.num_scales = height, width, num_scales
         self.is_train = is_train
@@ -208,7 +224,37 @@ class HAMMER_Dataset(Dataset):
             inputs[("inv_K", s)] = torch.from_numpy(np.linalg.pinv(K))
         inputs["stereo_T"] = torch.eye(4)
         inputs["stereo_T"][0, 3] = -0.0498921
+        for i in self.neighbours:                 # indoor_dataset.py:311-366: a missing neighbour is a dummy, not an error
+            inputs.update(self._neighbour(folder, idx, i))
         return inputs
+
+    @staticmethod
+    def relative_pose(pose_center, pose_side):
+        """hammer_dataset.py:104-132: inv(inv(T_c) T_s) in fp64 from two ``_pose/%06d.txt`` files (16 numbers, cam-to-world):
+        the motion that takes frame 0's camera coordinates to the neighbour's."""
+        with open(pose_center) as f:
+            T_c = np.array(f.read().split(), dtype="float").reshape(4, 4)
+        with open(pose_side) as f:
+            T_s = np.array(f.read().split(), dtype="float").reshape(4, 4)
+        return np.linalg.inv(np.linalg.inv(T_c) @ T_s)
+
+    def _neighbour(self, folder, idx, i):
+        """("color", i, 0), ("poses", i), ("frame_valid", i) of the frame idx + i * offset: the colour frame resized like
+        frame 0's first scale, the relative pose as float32, 1.0; zeros, the identity and 0.0 when the frame or one of the two
+        pose files does not exist."""
+        from PIL import Image
+        H, W = self.height, self.width
+        other = idx + i * self.offset
+        rgb = os.path.join(folder, "rgb", "{:06d}{}".format(other, self.img_ext))
+        pc, ps = (os.path.join(folder, "_pose", "{:06d}.txt".format(k)) for k in (idx, other))
+        if other >= 0 and all(os.path.isfile(p) for p in (rgb, pc, ps)):
+            im = Image.open(rgb).convert("RGB").resize((W, H), Image.LANCZOS)
+            color = torch.from_numpy(np.asarray(im, dtype=np.float32).transpose(2, 0, 1) / 255.0)
+            pose = torch.from_numpy(self.relative_pose(pc, ps).astype(np.float32))
+            ok = 1.0
+        else:
+            color, pose, ok = torch.zeros((3, H, W), dtype=torch.float32), torch.eye(4), 0.0
+        return {("color", i, 0): color, ("poses", i): pose, ("frame_valid", i): torch.tensor(ok, dtype=torch.float32)}
 
     @staticmethod
     def _dofp_frame(path, option="pol_dofp"):
@@ -274,6 +320,21 @@ class HAMMER_Dataset(Dataset):
         pol = np.clip(np.rint(pol + rng.normal(0, 1.5, pol.shape)), 0, 255).astype(np.uint8)
         inputs[("pol", 0, 0)] = torch.from_numpy(pol)
         inputs["stereo_T"] = torch.eye(4)
+        # neighbouring frames (drawn after every draw above, so frame 0 is what it is without them): a small rigid motion and a
+        # smooth colour picture -- frame 0's colour is white noise, so the term measures nothing here; it has to run and be finite
+        for i in self.neighbours:
+            rot, t = rng.uniform(-0.01, 0.01, 3), np.array([0.03 * i, 0.0, 0.0]) + rng.uniform(-0.01, 0.01, 3)
+            cx, sx = np.cos(rot[0]), np.sin(rot[0]); cy, sy = np.cos(rot[1]), np.sin(rot[1]); cz, sz = np.cos(rot[2]), np.sin(rot[2])
+            T = np.eye(4)
+            T[:3, :3] = (np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+                         @ np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]))
+            T[:3, 3] = t
+            ph = rng.uniform(0, 2 * np.pi, 3)
+            col = np.stack([0.5 + 0.3 * np.sin(xx / 11.0 + ph[c]) * np.cos(yy / 9.0 - ph[c]) + 0.15 * np.sin((xx + yy) / 17.0 + c)
+                            for c in range(3)])
+            inputs[("color", i, 0)] = torch.from_numpy(col.astype(np.float32))
+            inputs[("poses", i)] = torch.from_numpy(T.astype(np.float32))
+            inputs[("frame_valid", i)] = torch.tensor(1.0, dtype=torch.float32)
         return inputs
 
 

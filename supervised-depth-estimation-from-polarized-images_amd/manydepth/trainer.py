@@ -9,7 +9,14 @@ per-model ``<name>.pth`` + ``adam.pth`` checkpoint layout and the loss dictionar
 
 Implemented scope: the supervised single-frame branch (``--depth_supervision_only``,
 ``--depth_supervision``) -- trainer.py:192-216, 469-477, 497-513, 531-545, 567, 1126-1150, 1241-1265,
-1298-1309.  Pose / matching / reprojection / DPT / stereo branches raise NotImplementedError.
+1298-1309 -- and the supervised mode with photometric multi-view consistency from known poses (``--depth_supervision True
+--pose_input True`` without ``--depth_supervision_only``; trainer.py:479-530, 983-1098, 1150-1236): the same five networks and
+supervised terms, plus the neighbouring frames of ``--frame_ids`` warped into the current view through the predicted depth and
+the ground-truth relative poses of ``_pose/%06d.txt``, compared by monodepth2's reprojection loss (minimum over the frames,
+automasking; ``--no_ssim``, ``--disable_automasking``, ``--avg_reprojection`` are honoured).  It adds ``reproj_loss/{s}`` to
+``loss/{s}`` and their mean over the scales to ``loss``; under data parallelism the term is normalised per rank; it is not
+captured yet (``PD_STEP_GRAPH=1`` is refused with it).  The pose network, the cost-volume student (``--train_student``),
+``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
 
 What runs where: every tensor operation of a training step is a hand-written HIP kernel from
 libpolardepth.so (polar preprocessing K1, implicit-GEMM convolutions K2, fused BN/ReLU/pool chains
@@ -106,9 +113,20 @@ class Trainer:
         for flag in ("train_stereo_only", "train_dpt", "train_student", "use_stereo", "res_pose", "supervise_pose"):
             if getattr(self.opt, flag, False):
                 raise NotImplementedError(f"--{flag}: outside the supervised hot path of this build")
-        if not (self.opt.depth_supervision_only and self.opt.depth_supervision):
+        # the one further configuration: the supervised terms plus the photometric reprojection term from the neighbouring
+        # frames, warped with the ground-truth relative poses (no pose network, no cost volume)
+        self.photometric = bool(self.opt.depth_supervision and self.opt.pose_input and not self.opt.depth_supervision_only
+                                and not getattr(self.opt, "v1_multiscale", False))
+        if not (self.opt.depth_supervision_only and self.opt.depth_supervision) and not self.photometric:
             raise NotImplementedError("only --depth_supervision_only True --depth_supervision True is implemented "
                                       "(the path of train_supervised_GT.sh)")
+        if self.photometric and (os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False))):
+            raise NotImplementedError("PD_STEP_GRAPH=1 with --pose_input: the photometric term is not captured yet; "
+                                      "run this mode without the step graph")
+        self.frame_ids = [int(i) for i in self.opt.frame_ids] if self.photometric else [0]
+        if self.photometric and (self.frame_ids[0] != 0 or len(self.frame_ids) < 2 or 0 in self.frame_ids[1:]
+                                 or len(self.frame_ids) - 1 > ops.REPROJ_MAX_FRAMES):
+            raise ValueError(f"--frame_ids {self.frame_ids}: 0 first, then 1 .. {ops.REPROJ_MAX_FRAMES} neighbouring frames")
         local_rank = int(os.environ.get("LOCAL_RANK", 0))
         self.device = torch.device("cuda", local_rank)
         torch.cuda.set_device(self.device)
@@ -212,9 +230,9 @@ class Trainer:
         train_files = [self.opt.overfit_scene] if self.opt.overfit else _split(self.opt.split, "train", self.data_path)
         val_files = [self.opt.overfit_scene] if self.opt.overfit else _split(self.opt.split, "val", self.data_path)
         test_files = _split(self.opt.eval_split, "test", self.data_path_val)
-        mk = lambda path, files, tr: self.dataset(path, files, self.opt.height, self.opt.width, [0], 4, is_train=tr,
+        mk = lambda path, files, tr: self.dataset(path, files, self.opt.height, self.opt.width, self.frame_ids, 4, is_train=tr,
                                                   img_ext='.png', offset=self.opt.offset, modality=self.opt.modality,
-                                                  supervised_depth=True, supervised_depth_only=True,
+                                                  supervised_depth=True, supervised_depth_only=not self.photometric,
                                                   depth_modality=self.opt.depth_modality)
         train_dataset, val_dataset, test_dataset = mk(self.data_path, train_files, True), \
             mk(self.data_path, val_files, False), mk(self.data_path_val, test_files, False)
@@ -435,6 +453,23 @@ class Trainer:
             losses[f"supervised_normals_loss/{s}"] = vals[3 + 3 * i]
             outputs[("depth", 0, s)] = depths[i]
             outputs[("mono_depth", 0, s)] = depths[i]
+        if self.photometric:
+            # trainer.py:983-1067, 1150-1236 with --pose_input: the neighbours warped into frame 0 through each scale's depth
+            # map and the ground-truth relative poses, minimum over the frames with automasking (polardepth/functional.py)
+            ids = self.frame_ids[1:]
+            automask = not self.opt.disable_automasking
+            noise = None
+            if automask:                          # the tie-breaker of trainer.py:1193-1194, one draw per scale, on the device
+                noise = [torch.randn(depths[0].shape, device=depths[0].device).mul_(1e-5) for _ in scales]
+            reproj = PF.photometric_loss(self.loss_cfg, disps, depths, inputs[("color", 0, 0)],
+                                         [inputs[("color", i, 0)] for i in ids], inputs[("K", 0)], inputs[("inv_K", 0)],
+                                         [inputs[("poses", i)] for i in ids],
+                                         torch.stack([inputs[("frame_valid", i)] for i in ids], 1).float(), noise=noise,
+                                         no_ssim=self.opt.no_ssim, automask=automask, avg=self.opt.avg_reprojection)
+            for i, s in enumerate(scales):        # trainer.py:1234-1236, 1262-1265
+                losses[f"reproj_loss/{s}"] = reproj[i]
+                losses[f"loss/{s}"] = losses[f"loss/{s}"] + reproj[i]
+            losses["loss"] = losses["loss"] + sum(reproj[1:], reproj[0]) / len(reproj)
         if ("normals_pred", 0) in outputs:
             # `arch1++_separate_normals_dec`: the predicted normals against the normals of the ground truth, weighted like
             # the normals term of the depth loss (README.md:54,67: normals_loss_weight)

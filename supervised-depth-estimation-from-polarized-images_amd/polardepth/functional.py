@@ -1142,6 +1142,73 @@ def multiscale_loss(cfg, gt, K, disps, colors):
     return out[0], list(out[1:])
 
 
+# ------------------------------------------------------------------ photometric multi-view term (csrc/reproj.hip)
+class DispDepthFn(torch.autograd.Function):
+    """The tape link between a disparity map [N,1,hs,ws] and the full-resolution depth map [N,1,H,W] K5 made from it
+    (``multiscale_loss`` returns those maps as non-differentiable by-products): forward hands the depth map on as it is,
+    backward is depth = 1 / (min_disp + (max_disp - min_disp) * up(disp)) reversed -- pd_depth_to_updisp_bwd, then
+    pd_up_gather_bwd (trainer.py:997-1001, layers.py:62-71)."""
+
+    @staticmethod
+    def forward(ctx, disp, depth, min_depth, max_depth):
+        ctx.geom = (tuple(disp.shape), float(min_depth), float(max_depth))
+        ctx.save_for_backward(depth)
+        return depth.view_as(depth)
+
+    @staticmethod
+    def backward(ctx, gdepth):
+        (depth,) = ctx.saved_tensors
+        (N, _, hs, ws), min_depth, max_depth = ctx.geom
+        H, W = depth.shape[2], depth.shape[3]
+        st = stream_ptr()
+        gdepth = gdepth.float().contiguous()
+        gup = torch.empty_like(depth)
+        check(lib.pd_depth_to_updisp_bwd(ptr(gdepth), ptr(depth), ptr(gup), depth.numel(), min_depth, max_depth, st),
+              "pd_depth_to_updisp_bwd")
+        gdisp = _f32(depth.device, N, 1, hs, ws)
+        check(lib.pd_up_gather_bwd(ptr(gup), ptr(gdisp), N, hs, ws, H, W, 0, 0, st), "pd_up_gather_bwd")
+        return gdisp, None, None, None
+
+
+def photometric_loss(cfg, disps, depths, target, sources, K, inv_K, poses, valid, noise=None, no_ssim=False, automask=True,
+                     avg=False, details=False):
+    """monodepth2's photometric reprojection term with known poses (trainer.py:983-1098, 1150-1236 for ``--pose_input``):
+    per scale, every source frame is warped into the current view through that scale's full-resolution depth map
+    (``ops.view_synthesis``), compared with the target (``ops.reprojection_loss``) and reduced over the frames by minimum
+    (``avg``: mean) with automasking (``ops.reproj_combine``).  Returns one loss per scale.
+
+    disps    the disparity maps [N,1,hs,ws] the term is differentiable in (an entry, or the list, may be None: that depth
+             map is data); depths: the full-resolution depth maps [N,1,H,W] ``multiscale_loss`` returned for them
+    target   [N,3,H,W] ("color", 0, 0); sources: F frames [N,3,H,W]; poses: F matrices [N,4,4] current -> source camera
+    K, inv_K [N,4,4] of scale 0; valid [N,F], 0 = the frame does not exist (None: all do)
+    noise    the automask tie-breaker added to the identity value: one [N,1,H,W] map for every scale or a list of one per
+             scale (trainer.py:1193-1194 draws one per scale); ignored without automasking
+    The identity maps do not depend on the scale: they are evaluated once.  ``details``: also the per-scale ``sel`` maps."""
+    sources, poses = list(sources), list(poses)
+    if len(sources) != len(poses) or not sources:
+        raise ValueError("photometric_loss: one pose per source frame, at least one frame")
+    target = target.float().contiguous()
+    sources = [s.float().contiguous() for s in sources]
+    identity = None
+    if automask:
+        with torch.no_grad():
+            identity = [ops.reprojection_loss(s, target, no_ssim) for s in sources]
+    losses, sels = [], []
+    for i, depth in enumerate(depths):
+        d = depth
+        if disps is not None and disps[i] is not None:
+            d = DispDepthFn.apply(disps[i], depth, cfg.min_depth, cfg.max_depth)
+        maps = [ops.reprojection_loss(ops.view_synthesis(d, s, K, inv_K, T)[0], target, no_ssim)
+                for s, T in zip(sources, poses)]
+        nz = None
+        if automask and noise is not None:
+            nz = noise[i] if isinstance(noise, (list, tuple)) else noise
+        loss, sel, _ = ops.reproj_combine(maps, identity, nz, valid, avg, details=True)
+        losses.append(loss)
+        sels.append(sel)
+    return (losses, sels) if details else losses
+
+
 # ------------------------------------------------------------------ layers.get_smooth_loss as a function of its own
 class SmoothLossFn(torch.autograd.Function):
     """layers.py:452-465 on the K5 kernels: mean |dx disp| e^{-|dx I|} + mean |dy disp| e^{-|dy I|} of the disparity AS GIVEN

@@ -368,6 +368,117 @@ def reprojection_loss(pred, target, no_ssim=False):
     return _SSIMFn.apply(pred, target, 1, bool(no_ssim))
 
 
+# ------------------------------------------------------------------ photometric multi-view term (csrc/reproj.hip)
+REPROJ_MAX_FRAMES = 8         # PD_REPROJ_MAX_FRAMES
+
+
+def _dev_ptrs(tensors):
+    import ctypes
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _ViewSynthFn(torch.autograd.Function):
+    """BackprojectDepth + Project3D + grid_sample(border, align_corners=True) for one source frame (pd_view_synth_fwd /
+    _bwd): differentiable in depth only -- the source, the intrinsics and the pose are data."""
+
+    @staticmethod
+    def forward(ctx, depth, src, K, inv_K, T):
+        N, C, H, W = src.shape
+        warped = torch.empty_like(src)
+        coords = torch.empty((N, H, W, 2), dtype=torch.float32, device=src.device)
+        check(lib.pd_view_synth_fwd(ptr(depth), ptr(src), ptr(K), ptr(inv_K), ptr(T), ptr(warped), ptr(coords), N, C, H, W,
+                                    stream_ptr()), "pd_view_synth_fwd")
+        ctx.save_for_backward(depth, src, K, inv_K, T, coords)
+        ctx.mark_non_differentiable(coords)
+        return warped, coords
+
+    @staticmethod
+    def backward(ctx, gwarped, _gcoords):
+        depth, src, K, inv_K, T, coords = ctx.saved_tensors
+        N, C, H, W = src.shape
+        gdepth = torch.empty_like(depth)
+        check(lib.pd_view_synth_bwd(ptr(gwarped.float().contiguous()), ptr(src), ptr(coords), ptr(depth), ptr(K), ptr(inv_K),
+                                    ptr(T), ptr(gdepth), N, C, H, W, 0, stream_ptr()), "pd_view_synth_bwd")
+        return gdepth, None, None, None, None
+
+
+def view_synthesis(depth, src, K, inv_K, T):
+    """trainer.py:1021-1044 for one neighbouring frame: ``src`` [N,C,H,W] warped into the current view through ``depth``
+    [N,1,H,W], the intrinsics ``K`` / ``inv_K`` [N,4,4] and the relative pose ``T`` [N,4,4] (current camera -> source camera).
+    Returns (warped [N,C,H,W], coords [N,H,W,2]): coords are the unclamped source PIXEL coordinates (u, v) of every pixel
+    (include/polardepth.h states the arithmetic).  Differentiable in depth."""
+    _require_cuda(depth, src, K, inv_K, T)
+    if src.dim() != 4 or depth.dim() != 4 or depth.shape[1] != 1 or depth.shape[0] != src.shape[0] or \
+            depth.shape[2:] != src.shape[2:]:
+        raise ValueError(f"view_synthesis: depth [N,1,H,W] and src [N,C,H,W] expected, got {tuple(depth.shape)} / {tuple(src.shape)}")
+    N = src.shape[0]
+    for name, m in (("K", K), ("inv_K", inv_K), ("T", T)):
+        if tuple(m.shape) != (N, 4, 4):
+            raise ValueError(f"view_synthesis: {name} must be [{N},4,4], got {tuple(m.shape)}")
+    f = lambda t: t.float().contiguous()
+    return _ViewSynthFn.apply(f(depth), f(src), f(K), f(inv_K), f(T))
+
+
+class _ReprojCombineFn(torch.autograd.Function):
+    """trainer.py:1163-1215 (pd_reproj_combine_fwd / _bwd): returns (loss, sel, sums); differentiable in the F reproj maps."""
+
+    @staticmethod
+    def forward(ctx, identity, noise, valid, avg, *reproj):
+        F = len(reproj)
+        N, _, H, W = reproj[0].shape
+        dev = reproj[0].device
+        sel = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+        part = torch.empty((lib.pd_reproj_combine_rows(N, H, W), 2), dtype=torch.float64, device=dev)
+        sums = torch.empty(2, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib.pd_reproj_combine_fwd(_dev_ptrs(reproj), None if identity is None else _dev_ptrs(identity), F, ptr(noise),
+                                        ptr(valid), ptr(sel), ptr(part), ptr(sums), ptr(loss), N, H, W, int(avg),
+                                        stream_ptr()), "pd_reproj_combine_fwd")
+        ctx.geom = (F, N, H, W, int(avg))
+        ctx.save_for_backward(sel, sums, valid)
+        ctx.mark_non_differentiable(sel, sums)
+        return loss.reshape(()), sel, sums
+
+    @staticmethod
+    def backward(ctx, gloss, _gsel, _gsums):
+        sel, sums, valid = ctx.saved_tensors
+        F, N, H, W, avg = ctx.geom
+        grads = [torch.empty((N, 1, H, W), dtype=torch.float32, device=sel.device) for _ in range(F)]
+        check(lib.pd_reproj_combine_bwd(ptr(gloss.float().reshape(1).contiguous()), ptr(sel), ptr(sums), ptr(valid),
+                                        _dev_ptrs(grads), F, N, H, W, avg, stream_ptr()), "pd_reproj_combine_bwd")
+        return (None, None, None, None, *grads)
+
+
+def reproj_combine(reproj, identity=None, noise=None, valid=None, avg=False, details=False):
+    """The reduction of trainer.py:1163-1215 over the neighbouring frames: ``reproj`` (and, for automasking, ``identity``) are
+    lists of F [N,1,H,W] maps of ``reprojection_loss``; ``noise`` [N,1,H,W] is added to the identity value; ``valid`` [N,F]
+    marks with 0 the frames that do not exist.  Per pixel the minimum over the valid frames (``avg``: their mean), masked
+    where the identity value + noise is smaller; returns sum(min * mask) / (sum(mask) + 1e-7), summed in fp64 in a fixed
+    order.  ``details``: also ``sel`` [N,H,W] uint8 (winning frame, 255 = masked) and ``sums`` (2 doubles: sum, count).
+    Differentiable in the reproj maps."""
+    reproj = list(reproj)
+    if not 1 <= len(reproj) <= REPROJ_MAX_FRAMES:
+        raise ValueError(f"reproj_combine: 1 .. {REPROJ_MAX_FRAMES} frames, got {len(reproj)}")
+    if identity is not None and len(identity) != len(reproj):
+        raise ValueError("reproj_combine: as many identity maps as reproj maps")
+    if noise is not None and identity is None:
+        raise ValueError("reproj_combine: noise is added to the identity maps; there are none")
+    _require_cuda(*reproj, *(identity or ()), noise, valid)
+    shape = tuple(reproj[0].shape)
+    if len(shape) != 4 or shape[1] != 1:
+        raise ValueError(f"reproj_combine: maps must be [N,1,H,W], got {shape}")
+    for t in (*reproj, *(identity or ()), *((noise,) if noise is not None else ())):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"reproj_combine: every map must be {shape}, got {tuple(t.shape)}")
+    if valid is not None and tuple(valid.shape) != (shape[0], len(reproj)):
+        raise ValueError(f"reproj_combine: valid must be [{shape[0]},{len(reproj)}], got {tuple(valid.shape)}")
+    f = lambda t: t.float().contiguous()
+    loss, sel, sums = _ReprojCombineFn.apply(None if identity is None else [f(t).detach() for t in identity],
+                                             None if noise is None else f(noise).detach(),
+                                             None if valid is None else f(valid).detach(), bool(avg), *[f(t) for t in reproj])
+    return (loss, sel, sums) if details else loss
+
+
 def depth_metrics(gt, pred, min_depth, max_depth, mask=None, mask_value=0):
     """Per-image depth metrics on the device: [N,8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count."""
     _require_cuda(gt, pred, mask)

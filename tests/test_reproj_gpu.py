@@ -1,0 +1,299 @@
+"""csrc/reproj.hip on the device against tests/reproj_ref.py (fp64 NumPy) and fixture G12 (the reference's own pieces run on
+the CPU in float32 and float64, tests/golden/make_golden_reproj.py).
+
+Bounds.  coords: the kernel evaluates the projection in fp64 and rounds once, the reference value is an fp64 evaluation in
+another summation order rounded once -- both fp64 errors are far below half an fp32 ulp, so the two roundings differ by at
+most one ulp (double rounding).  warped, fed the kernel's own coords (identical cells): two weight roundings (1 - w), a weight
+product, a value product and three additions on values and weights in [0, 1]: at most 7 * 2^-24 ~ 4.2e-7 plus the weight
+roundings, bound 1e-6 * max(1, max|src|).  Against the fixture: multiples of the reference's own float32 deviation from its
+float64 run, as recorded in the fixture (1x in the mean; 2x in the maximum, a noisy statistic over ~2000 pixels)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+
+import reproj_ref as R
+
+pytestmark = pytest.mark.gpu
+H, W = 19, 37
+
+
+@pytest.fixture(scope="module")
+def g12():
+    return dict(np.load(os.path.join(GOLDEN, "g12_reproj.npz")))
+
+
+@pytest.fixture(scope="module")
+def synth(g12):
+    """pd_view_synth_fwd on both source frames of the fixture, once: (warped, coords) as NumPy, and the device inputs."""
+    from polardepth import ops
+    dev = {k: torch.from_numpy(g12[k]).cuda() for k in ("depth", "target", "src0", "src1", "K", "inv_K", "T0", "T1", "noise",
+                                                       "gw0", "gw1")}
+    out = {}
+    for f in range(2):
+        warped, coords = ops.view_synthesis(dev["depth"], dev[f"src{f}"], dev["K"], dev["inv_K"], dev[f"T{f}"])
+        out[f] = (warped.cpu().numpy(), coords.cpu().numpy())
+    return out, dev
+
+
+def _ulp_diff(got, want32):
+    return np.abs(got.astype(np.float64) - want32.astype(np.float64)) / np.spacing(np.abs(want32)).astype(np.float64)
+
+
+@pytest.mark.parametrize("f", [0, 1])
+def test_coords_are_the_fp32_rounding_of_the_fp64_projection(g12, synth, f):
+    _, coords = synth[0][f]
+    assert coords.dtype == np.float32 and coords.shape == (2, H, W, 2)
+    want = R.view_synth(g12["depth"], g12[f"src{f}"], g12["K"], g12["inv_K"], g12[f"T{f}"])["coords"].astype(np.float32)
+    d = _ulp_diff(coords, want)
+    print(f"coords frame {f}: max ulp {d.max()}, share exact {(d == 0).mean():.4f}")
+    assert d.max() <= 1.0
+    if f == 1:                                           # stored unclamped: the large pose leaves the image on every side
+        assert coords[..., 0].min() < -1 and coords[..., 0].max() > W and coords[..., 1].min() < -1 and coords[..., 1].max() > H
+
+
+@pytest.mark.parametrize("f", [0, 1])
+def test_warped_matches_the_definition_at_the_kernels_own_coords(g12, synth, f):
+    warped, coords = synth[0][f]
+    want = R.sample(g12[f"src{f}"], coords)["warped"]
+    err = np.abs(warped - want).max()
+    bound = 1e-6 * max(1.0, np.abs(g12[f"src{f}"]).max())
+    print(f"warped frame {f}: max |err| {err:.3e} (bound {bound:.3e})")
+    assert err <= bound
+
+
+def test_warped_against_the_reference_run(g12, synth):
+    dev = np.concatenate([np.abs(synth[0][f][0] - g12[f"warped{f}_f64"]).ravel() for f in range(2)])
+    print(f"warped vs reference fp64: mean {dev.mean():.3e} (reference fp32 {g12['dev_warped_mean']:.3e}), "
+          f"max {dev.max():.3e} (reference fp32 {g12['dev_warped_max']:.3e})")
+    assert dev.mean() <= 1.0 * g12["dev_warped_mean"]
+    assert dev.max() <= 2.0 * g12["dev_warped_max"]
+
+
+@pytest.mark.parametrize("f", [0, 1])
+def test_depth_gradient_against_the_reference_autograd(g12, synth, f):
+    from polardepth import ops
+    dev = synth[1]
+    depth = dev["depth"].clone().requires_grad_(True)
+    warped, coords = ops.view_synthesis(depth, dev[f"src{f}"], dev["K"], dev["inv_K"], dev[f"T{f}"])
+    assert not coords.requires_grad
+    warped.backward(dev[f"gw{f}"])
+    g = depth.grad.cpu().numpy().astype(np.float64)
+    c = coords.cpu().numpy()
+    near = R.near_boundary(c, H, W)[:, None]
+    assert near.mean() <= 0.03, near.mean()
+    want = g12[f"gdepth{f}_f64"]
+    rel = np.abs(g - want)[~near].max() / np.abs(want).max()
+    print(f"gdepth frame {f}: rel dev {rel:.3e} (reference fp32 {g12['dev_gdepth_rel']:.3e}), excluded {near.mean():.4f}")
+    assert rel <= 2.0 * g12["dev_gdepth_rel"]
+    s = R.sample(g12[f"src{f}"], c)
+    both = ~s["free_x"] & ~s["free_y"]
+    assert (g[:, 0][both] == 0).all()
+    # one clamped axis contributes exactly nothing: the gradient is the other axis' alone
+    one = R.view_synth_grad(g12[f"gw{f}"], g12[f"src{f}"], c, g12["depth"], g12["K"], g12["inv_K"], g12[f"T{f}"])
+    only_y = (~s["free_x"] & s["free_y"] & ~near[:, 0])
+    if f == 1:
+        assert only_y.sum() > 50
+    assert np.abs(g[:, 0][only_y] - one[:, 0][only_y]).max(initial=0.0) <= 2.0 * g12["dev_gdepth_rel"] * np.abs(want).max()
+
+
+def test_backward_accumulate_flag_adds_to_what_is_there(g12, synth):
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    dev = synth[1]
+    coords = torch.from_numpy(synth[0][1][1]).cuda()
+    args = lambda out, acc: (ptr(dev["gw1"]), ptr(dev["src1"]), ptr(coords), ptr(dev["depth"]), ptr(dev["K"]), ptr(dev["inv_K"]),
+                             ptr(dev["T1"]), ptr(out), 2, 3, H, W, acc, stream_ptr())
+    g = torch.empty_like(dev["depth"])
+    check(lib.pd_view_synth_bwd(*args(g, 0)), "pd_view_synth_bwd")
+    base = torch.full_like(g, 0.25)
+    acc = base.clone()
+    check(lib.pd_view_synth_bwd(*args(acc, 1)), "pd_view_synth_bwd")
+    assert torch.equal(acc, base + g) and g.abs().max().item() > 0
+
+
+def test_view_synthesis_grid_stride_and_non_finite_coordinates():
+    """4 x 1 x 512 x 520: more pixels per item than one sweep of the per-item grid, so every workgroup strides; two columns
+    of non-finite depth give non-finite coordinates, which sample source pixel 0 of both axes."""
+    from polardepth import ops
+    N, C, h, w = 4, 1, 512, 520
+    rng = np.random.default_rng(3)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    depth = np.stack([1.0 + 0.3 * np.sin(xx / 50.0 + n) * np.cos(yy / 40.0) for n in range(N)])[:, None].astype(np.float32)
+    src = rng.random((N, C, h, w), dtype=np.float32)
+    K = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
+    K[:, 0, 0] = K[:, 1, 1] = 0.6 * w
+    K[:, 0, 2], K[:, 1, 2] = w / 2, h / 2
+    inv_K = np.linalg.inv(K).astype(np.float32)
+    T = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
+    T[:, 0, 3], T[:, 2, 3] = 0.03, -0.02
+    depth[0, 0, :, 7] = np.nan                           # NaN and infinite depths: (u, v) = NaN (inf / inf)
+    depth[0, 0, :, 9] = np.inf
+    t = lambda a: torch.from_numpy(a).cuda()
+    warped, coords = ops.view_synthesis(t(depth), t(src), t(K), t(inv_K), t(T))
+    warped, coords = warped.cpu().numpy(), coords.cpu().numpy()
+    assert not np.isfinite(coords[0, :, [7, 9]]).any() and np.isfinite(coords[1:]).all()
+    assert np.array_equal(warped[0, 0, :, 7], np.full(h, src[0, 0, 0, 0])) and np.array_equal(warped[0, 0, :, 9], warped[0, 0, :, 7])
+    fin = np.isfinite(coords)
+    with np.errstate(all="ignore"):
+        want = R.view_synth(depth, src, K, inv_K, T)["coords"]
+    assert _ulp_diff(coords[fin], want[fin].astype(np.float32)).max() <= 1.0
+    assert np.abs(warped - R.sample(src, coords)["warped"]).max() <= 1e-6
+
+
+# ------------------------------------------------------------------ the reduction over the frames
+def _run_combine(reproj, identity=None, noise=None, valid=None, avg=False):
+    from polardepth import ops
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    maps = [t(r).requires_grad_(True) for r in reproj]
+    loss, sel, sums = ops.reproj_combine(maps, None if identity is None else [t(i) for i in identity], t(noise), t(valid), avg,
+                                         details=True)
+    loss.backward(torch.tensor(1.5, device="cuda"))
+    return loss.detach().cpu().numpy(), sel.cpu().numpy(), sums.cpu().numpy(), [m.grad.cpu().numpy() for m in maps]
+
+
+def _combine_cases(g12):
+    r = [g12["reproj0_f32"].copy(), g12["reproj1_f32"].copy()]
+    i = [g12["ident0_f32"], g12["ident1_f32"]]
+    tie = [r[0].copy(), r[1].copy()]
+    tie[1][:, :, 3:9] = tie[0][:, :, 3:9]                                           # equal maps: frame 0 must win
+    tie_id = [i[0].copy(), i[1].copy()]
+    tie_id[0][0, 0, :5] = tie_id[1][0, 0, :5] = np.minimum(r[0], r[1])[0, 0, :5]    # reprojection == identity: kept
+    return {
+        "fixture": dict(reproj=r, identity=i, noise=g12["noise"]),
+        "no_noise": dict(reproj=r, identity=i),
+        "no_automask": dict(reproj=r),
+        "avg": dict(reproj=r, identity=i, noise=g12["noise"], avg=True),
+        "avg_invalid": dict(reproj=r, identity=i, valid=np.array([[1, 0], [1, 1]], np.float32), avg=True),
+        "item_without_frames": dict(reproj=r, identity=i, noise=g12["noise"], valid=np.array([[0, 0], [1, 1]], np.float32)),
+        "first_frame_invalid": dict(reproj=r, identity=i, valid=np.array([[0, 1], [1, 0]], np.float32)),
+        "tie_between_frames": dict(reproj=tie),
+        "tie_with_identity": dict(reproj=r, identity=tie_id),
+    }
+
+
+@pytest.mark.parametrize("case", ["fixture", "no_noise", "no_automask", "avg", "avg_invalid", "item_without_frames",
+                                  "first_frame_invalid", "tie_between_frames", "tie_with_identity"])
+def test_combine_selection_count_and_sums(g12, case):
+    kw = _combine_cases(g12)[case]
+    want = R.combine(**kw)
+    loss, sel, sums, grads = _run_combine(**kw)
+    loss2, sel2, sums2, grads2 = _run_combine(**kw)
+    assert np.array_equal(sel, want["sel"]), (sel != want["sel"]).sum()
+    assert sums[1] == want["count"]
+    n = sel.size
+    print(f"{case}: sum {sums[0]!r} vs {want['sum']!r}, count {sums[1]}, loss {loss}")
+    assert abs(sums[0] - want["sum"]) <= n * 2.0 ** -52 * want["abs_sum"]
+    assert loss == np.float32(sums[0] / (sums[1] + 1e-7))
+    assert loss.tobytes() == loss2.tobytes() and sums.tobytes() == sums2.tobytes() and np.array_equal(sel, sel2)
+    assert all(np.array_equal(a, b) for a, b in zip(grads, grads2))
+    # backward: gloss / (count + 1e-7) rounded once (avg: one more division by the number of valid frames), 3 ulp
+    for g, w in zip(grads, R.combine_grad(1.5, want["sel"], want["count"], kw.get("valid"), 2, kw.get("avg", False))):
+        assert np.array_equal(g != 0, w != 0)
+        assert np.abs(g - w).max() <= 3 * 2.0 ** -24 * np.abs(w).max() + 0.0
+    if case == "item_without_frames":
+        assert (sel[0] == 255).all() and (sel[1] != 255).any() and all((g[0] == 0).all() for g in grads)
+    if case == "tie_between_frames":
+        assert (sel[:, 3:9] == 0).all() and (sel == 1).any()
+    if case == "tie_with_identity":
+        assert (sel[0, :5] != 255).all()
+    if case == "no_automask":
+        assert sums[1] == n and (sel != 255).all()
+    if case == "first_frame_invalid":
+        assert set(np.unique(sel[0])) <= {1, 255} and set(np.unique(sel[1])) <= {0, 255}
+
+
+def test_combine_grid_stride_is_reproducible_and_exact_in_count():
+    """3 x 512 x 384 pixels: more than the 2048 workgroups of 256 threads cover in one sweep."""
+    from polardepth import ops
+    gen = torch.Generator(device="cuda").manual_seed(4)
+    shape = (3, 1, 512, 384)
+    r = [torch.rand(shape, generator=gen, device="cuda") for _ in range(3)]
+    i = [torch.rand(shape, generator=gen, device="cuda") for _ in range(3)]
+    out = [ops.reproj_combine(r, i, details=True) for _ in range(2)]
+    m = torch.minimum(torch.minimum(r[0], r[1]), r[2])
+    keep = m <= torch.minimum(torch.minimum(i[0], i[1]), i[2])
+    total = (m.double() * keep).sum().item()
+    loss, sel, sums = out[0]
+    assert sums[1].item() == keep.sum().item() and torch.equal((sel != 255)[:, None], keep)
+    assert abs(sums[0].item() - total) <= keep.numel() * 2.0 ** -52 * total
+    assert torch.equal(sel, out[1][1]) and torch.equal(sums, out[1][2]) and torch.equal(loss, out[1][0])
+    assert torch.equal(sel[keep[:, 0]].long(), torch.stack(r, 0).argmin(0)[keep])
+
+
+# ------------------------------------------------------------------ the whole term
+def _cfg():
+    from polardepth import functional as PF
+    return PF.LossCfg([0], 0.1, 2.0, 0.35, 1e-3, H, W)
+
+
+def test_photometric_loss_end_to_end_with_the_stored_noise(g12, synth):
+    from polardepth import functional as PF
+    dev = synth[1]
+    valid = torch.ones(2, 2, device="cuda")
+    losses, sels = PF.photometric_loss(_cfg(), None, [dev["depth"]], dev["target"], [dev["src0"], dev["src1"]], dev["K"],
+                                       dev["inv_K"], [dev["T0"], dev["T1"]], valid, noise=dev["noise"], details=True)
+    assert len(losses) == 1 and losses[0].shape == ()
+    near = g12["near_tie"][:, 0]
+    assert near.mean() <= 0.01
+    want_sel = np.where(g12["mask_f64"][:, 0] != 0, g12["argmin_f64"][:, 0], 255).astype(np.uint8)
+    sel = sels[0].cpu().numpy()
+    print(f"selection: {(sel != want_sel)[~near].sum()} of {sel.size} differ; near ties {near.mean():.4f}")
+    assert np.array_equal(sel[~near], want_sel[~near])
+    err = abs(losses[0].item() - float(g12["loss_f64"]))
+    bound = max(2.0 * float(g12["dev_loss"]), 1e-6)
+    print(f"loss {losses[0].item()!r} vs {float(g12['loss_f64'])!r}: |err| {err:.3e} (bound {bound:.3e})")
+    assert err <= bound
+
+
+def test_photometric_loss_options_and_the_link_to_the_disparities():
+    """--no_ssim, --disable_automasking and --avg_reprojection change the term; through DispDepthFn every scale's disparity
+    receives a gradient, and that link equals torch's autograd of 1 / (min_disp + (max_disp - min_disp) * up(disp))."""
+    from polardepth import functional as PF, synthetic
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    b = synthetic.multiview_plane(2, 32, 48, seed=1)
+    cfg = PF.LossCfg([0, 1], 0.1, 2.0, 0.35, 1e-3, 32, 48)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    disps = [(0.3 + 0.4 * torch.rand((2, 1, 32 >> s, 48 >> s), generator=gen, device="cuda")).requires_grad_(True) for s in (0, 1)]
+    depths = []
+    for d in disps:
+        out = torch.empty((2, 1, 32, 48), device="cuda")
+        check(lib.pd_disp_to_depth(ptr(d.detach()), ptr(out), None, 2, d.shape[2], d.shape[3], 32, 48, 0.1, 2.0, stream_ptr()),
+              "pd_disp_to_depth")
+        depths.append(out)
+    args = (b[("color", 0, 0)], [b[("color", -1, 0)], b[("color", 1, 0)]], b[("K", 0)], b[("inv_K", 0)],
+            [b[("poses", -1)], b[("poses", 1)]], torch.ones(2, 2, device="cuda"))
+    base = PF.photometric_loss(cfg, disps, depths, *args)
+    assert len(base) == 2 and all(torch.isfinite(l) for l in base)
+    (base[0] + base[1]).backward()
+    assert all(d.grad is not None and torch.isfinite(d.grad).all() and d.grad.abs().max().item() > 0 for d in disps)
+    with torch.no_grad():
+        variants = {k: float(PF.photometric_loss(cfg, None, depths, *args, **kw)[0]) for k, kw in
+                    (("base", {}), ("no_ssim", {"no_ssim": True}), ("no_automask", {"automask": False}), ("avg", {"avg": True}))}
+    assert base[0].item() == variants["base"] and len(set(variants.values())) == 4, variants
+    # the link alone, against torch (fp32 on both sides: a few ulp of the largest entry)
+    d1 = disps[1].detach().clone().requires_grad_(True)
+    g = torch.randn((2, 1, 32, 48), generator=gen, device="cuda")
+    PF.DispDepthFn.apply(d1, depths[1], 0.1, 2.0).backward(g)
+    d2 = disps[1].detach().clone().requires_grad_(True)
+    up = torch.nn.functional.interpolate(d2, [32, 48], mode="bilinear", align_corners=False)
+    ref = 1.0 / (1 / 2.0 + (1 / 0.1 - 1 / 2.0) * up)
+    assert (ref - depths[1]).abs().max().item() <= 1e-5
+    ref.backward(g)
+    assert (d1.grad - d2.grad).abs().max().item() <= 1e-5 * d2.grad.abs().max().item()
+
+
+def test_conventions_true_depth_beats_scaled_depths_on_the_plane():
+    from polardepth import functional as PF, synthetic
+    b = synthetic.multiview_plane(2, 32, 48, frame_ids=(0, -1, 1), seed=0)
+    cfg = PF.LossCfg([0], 0.1, 2.0, 0.35, 1e-3, 32, 48)
+    vals = {}
+    for s in (0.9, 1.0, 1.1):
+        vals[s] = float(PF.photometric_loss(cfg, None, [b["depth"] * s], b[("color", 0, 0)],
+                                            [b[("color", -1, 0)], b[("color", 1, 0)]], b[("K", 0)], b[("inv_K", 0)],
+                                            [b[("poses", -1)], b[("poses", 1)]],
+                                            torch.stack([b[("frame_valid", -1)], b[("frame_valid", 1)]], 1))[0])
+    print("plane:", vals)
+    assert vals[1.0] < vals[0.9] and vals[1.0] < vals[1.1]

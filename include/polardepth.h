@@ -552,7 +552,8 @@ int pd_loss_weights(const void* gvals, const int* scale_ids, int S, float w_norm
 
 /* SSIM map (mode 0, layers.py:468-499) or the photometric reprojection loss of trainer.py:1069-1081 (mode 1:
  * out [N,1,H,W] = 0.85 * mean_c SSIM + 0.15 * mean_c |y - x|, or the L1 part alone when no_ssim).  x, y planar
- * NCHW fp32.  Inactive under --depth_supervision_only; the photometric mode (below) runs mode 1 with its gradient. */
+ * NCHW fp32.  Inactive under --depth_supervision_only; the photometric mode (below) runs mode 1 with its gradient.
+ * A NaN or infinite pixel gives NaN on the windows that hold it (torch.clamp propagates NaN; so does the clamp here). */
 int pd_ssim_fwd(const void* x, const void* y, void* out, int N, int C, int H, int W, int mode, int no_ssim,
                 void* stream);
 /* Gradient of pd_ssim_fwd w.r.t. both images: gout [N,C,H,W] (mode 0) or [N,1,H,W] (mode 1), gx / gy [N,C,H,W] (gy may be

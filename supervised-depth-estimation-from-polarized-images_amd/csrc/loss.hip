@@ -1162,8 +1162,9 @@ extern "C" int pd_loss_weights(const void* gvals, const int* scale_ids, int S, f
 // ============================================================================ SSIM + depth metrics
 // SSIM (layers.py:468-499: ReflectionPad2d(1), 3x3 average pools, C1 = 1e-4, C2 = 9e-4, clamp((1-n/d)/2, 0, 1))
 // and the photometric mix of trainer.py:1069-1081 (0.85 * mean_c SSIM + 0.15 * mean_c |target - pred|).
-// Constructed by the reference trainer but inactive under --depth_supervision_only; exposed because
-// north_star names it.  Planar NCHW fp32, one thread per pixel, all channels.
+// Inactive under --depth_supervision_only; on the training path with the photometric multi-view term
+// (functional.photometric_loss), 2 F launches per scale and step.  Planar NCHW fp32, one thread per pixel, all
+// channels.  A NaN or infinity in an image gives NaN on the windows that hold it, as in the reference.
 namespace {
 
 __device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
@@ -1197,7 +1198,10 @@ __global__ __launch_bounds__(LT) void ssim_kernel(const float* __restrict__ x, c
             const float sig_x = sxx * k - mu_x * mu_x, sig_y = syy * k - mu_y * mu_y, sig_xy = sxy * k - mu_x * mu_y;
             const float nn = (2.f * mu_x * mu_y + 1e-4f) * (2.f * sig_xy + 9e-4f);
             const float dd = (mu_x * mu_x + mu_y * mu_y + 1e-4f) * (sig_x + sig_y + 9e-4f);
-            const float v = fminf(fmaxf((1.f - nn / dd) * 0.5f, 0.f), 1.f);
+            // fminf / fmaxf return the other operand for a NaN: a non-finite pixel would read as SSIM loss 0 on every window
+            // that holds it.  torch.clamp propagates NaN, so does this (both outputs: v feeds the map and the mix).
+            const float f = (1.f - nn / dd) * 0.5f;
+            const float v = f != f ? f : fminf(fmaxf(f, 0.f), 1.f);
             if (mode == 0) out[(n * C + c) * P + (long)py * W + px] = v;
             s_ssim += v;
             s_l1 += fabsf(yp[(long)py * W + px] - xp[(long)py * W + px]);

@@ -60,18 +60,21 @@ def view_synth(depth, src, K, inv_K, T, coords=None):
     return out
 
 
-def view_synth_grad(gwarped, src, coords, depth, K, inv_K, T):
-    """pd_view_synth_bwd: d sum(gwarped * warped) / d depth [N,1,H,W] fp64, cells and weights from ``coords``."""
+def view_synth_grad(gwarped, src, coords, depth, K, inv_K, T, magnitude=False):
+    """pd_view_synth_bwd: d sum(gwarped * warped) / d depth [N,1,H,W] fp64, cells and weights from ``coords``.
+    magnitude: the same expression with the absolute value of every term that is added (tap differences, channel terms,
+    the two axes) -- what relative rounding errors of the summands are relative to."""
     s = sample(src, coords)
     v00, v10, v01, v11 = s["taps"]
     wx0, wx1, wy0, wy1 = s["w"]
     gw = np.asarray(gwarped, F64)
-    gu = (gw * ((v10 - v00) * wy0 + (v11 - v01) * wy1)).sum(1)
-    gv = (gw * ((v01 - v00) * wx0 + (v11 - v10) * wx1)).sum(1)
+    m = np.abs if magnitude else (lambda a: a)
+    gu = (m(gw) * (m(v10 - v00) * wy0 + m(v11 - v01) * wy1)).sum(1)
+    gv = (m(gw) * (m(v01 - v00) * wx0 + m(v11 - v10) * wx1)).sum(1)
     uv, hz, q = project(depth, K, inv_K, T)
     with np.errstate(divide="ignore", invalid="ignore"):
-        du = np.where(s["free_x"], (q[..., 0] - uv[..., 0] * q[..., 2]) / hz, 0.0)
-        dv = np.where(s["free_y"], (q[..., 1] - uv[..., 1] * q[..., 2]) / hz, 0.0)
+        du = np.where(s["free_x"], m((q[..., 0] - uv[..., 0] * q[..., 2]) / hz), 0.0)
+        dv = np.where(s["free_y"], m((q[..., 1] - uv[..., 1] * q[..., 2]) / hz), 0.0)
     g = np.where(s["free_x"], gu * du, 0.0) + np.where(s["free_y"], gv * dv, 0.0)
     return g[:, None]
 

@@ -6,7 +6,13 @@ another summation order rounded once -- both fp64 errors are far below half an f
 most one ulp (double rounding).  warped, fed the kernel's own coords (identical cells): two weight roundings (1 - w), a weight
 product, a value product and three additions on values and weights in [0, 1]: at most 7 * 2^-24 ~ 4.2e-7 plus the weight
 roundings, bound 1e-6 * max(1, max|src|).  Against the fixture: multiples of the reference's own float32 deviation from its
-float64 run, as recorded in the fixture (1x in the mean; 2x in the maximum, a noisy statistic over ~2000 pixels)."""
+float64 run, as recorded in the fixture (1x in the mean; 2x in the maximum, a noisy statistic over ~2000 pixels).
+
+The backward kernels on their own, nothing excluded.  pd_view_synth_bwd at the kernel's own coords: per pixel
+(4 + C) * 2^-24 * A + 2^-24 |ref|, roundings counted in _assert_depth_gradient, A the reference with |.| on every summand.
+pd_depth_to_updisp_bwd: 4 * 2^-24 |ref| (four roundings).  The whole term's disparity gradient: the rule of
+tests/loss_cases.py (4 x the deviation of the same chain with its SSIM stage in fp32) at the device's own sel, count,
+coords and warped images."""
 import os
 
 import numpy as np
@@ -297,3 +303,181 @@ def test_conventions_true_depth_beats_scaled_depths_on_the_plane():
                                             torch.stack([b[("frame_valid", -1)], b[("frame_valid", 1)]], 1))[0])
     print("plane:", vals)
     assert vals[1.0] < vals[0.9] and vals[1.0] < vals[1.1]
+
+
+# ------------------------------------------------------------------ the backward kernels, pixel by pixel
+def _view_synth_bwd(gw, src, coords, depth, K, inv_K, T):
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    N, C, h, w = src.shape
+    g = torch.full((N, 1, h, w), float("nan"), device="cuda")
+    check(lib.pd_view_synth_bwd(ptr(gw), ptr(src), ptr(coords), ptr(depth), ptr(K), ptr(inv_K), ptr(T), ptr(g), N, C, h, w, 0,
+                                stream_ptr()), "pd_view_synth_bwd")
+    torch.cuda.synchronize()
+    return g.cpu().numpy().astype(np.float64)
+
+
+def _assert_depth_gradient(g, gw, src, coords, depth, K, inv_K, T, what):
+    """|g - ref| <= k 2^-24 A + 2^-24 |ref| on EVERY pixel, A = the reference expression with the absolute value of every
+    summand (reproj_ref.view_synth_grad(magnitude=True)).  k = 4 + C, the fp32 roundings on the longest path to gu (or gv):
+    the lower weight 1 - w1 (1), a tap difference (1), its product with the weight (1), the sum of the two products (1),
+    the product with gw_c (1) -- 5 for a channel term -- and C - 1 additions of channel terms (the first lands on 0).  The
+    rest (projection, du, dv, gu du + gv dv) is fp64 and rounded once: 2^-24 |ref|."""
+    C = src.shape[1]
+    a = (gw, src, coords, depth, K, inv_K, T)
+    ref = R.view_synth_grad(*a)
+    mag = R.view_synth_grad(*a, magnitude=True)
+    bound = (4 + C) * 2.0 ** -24 * mag + 2.0 ** -24 * np.abs(ref)
+    err = np.abs(g - ref)
+    worst = np.argmax(err - bound)
+    print(f"{what}: max err {err.max():.3e}, largest err / bound {(err / np.maximum(bound, 1e-300)).max():.3f}, "
+          f"k = {4 + C}, every one of {err.size} pixels compared")
+    assert (err <= bound).all(), (what, err.ravel()[worst], bound.ravel()[worst])
+    s = R.sample(src, coords)
+    both = ~s["free_x"] & ~s["free_y"]
+    one = s["free_x"] ^ s["free_y"]
+    assert (g[:, 0][both] == 0).all()
+    return one, both, s
+
+
+@pytest.mark.parametrize("f", [0, 1])
+def test_depth_gradient_at_the_kernels_own_coords_on_every_pixel(g12, synth, f):
+    dev = synth[1]
+    coords = synth[0][f][1]
+    g = _view_synth_bwd(dev[f"gw{f}"], dev[f"src{f}"], torch.from_numpy(coords).cuda(), dev["depth"], dev["K"], dev["inv_K"],
+                        dev[f"T{f}"])
+    one, both, s = _assert_depth_gradient(g, g12[f"gw{f}"], g12[f"src{f}"], coords, g12["depth"], g12["K"], g12["inv_K"],
+                                          g12[f"T{f}"], f"gdepth frame {f}")
+    print(f"frame {f}: {one.sum()} pixels with one clamped axis, {both.sum()} with both")
+    if f == 1:                                           # leaves the image on every side
+        assert one.sum() >= 50 and both.sum() >= 50
+        assert (~s["free_x"] & s["free_y"]).any() and (s["free_x"] & ~s["free_y"]).any()
+        assert (g[:, 0][one] != 0).mean() > 0.9          # the single-axis value (inside the bound above), not a zero
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 2, 2), (1, 2, 3, 5)])
+def test_depth_gradient_on_tiny_images_where_the_upper_tap_clamps_at_the_last_cell(shape):
+    """Identity plus a small translation: the last column's coordinate passes W - 1, its cell is i0 = i1 = W - 1."""
+    from polardepth import ops
+    N, C, h, w = shape
+    rng = np.random.default_rng(h * w)
+    depth = (1.0 + 0.2 * rng.random((N, 1, h, w))).astype(np.float32)
+    src = rng.random(shape, dtype=np.float32)
+    gw = rng.standard_normal(shape).astype(np.float32)
+    K = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
+    K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2] = 0.9 * w, 1.1 * h, (w - 1) / 2 + 0.1, (h - 1) / 2 - 0.1
+    inv_K = np.linalg.inv(K).astype(np.float32)
+    T = np.tile(np.eye(4, dtype=np.float32), (N, 1, 1))
+    T[:, 0, 3], T[:, 1, 3], T[:, 2, 3] = 0.08, -0.03, 0.02
+    t = lambda a: torch.from_numpy(a).cuda()
+    warped, coords = ops.view_synthesis(t(depth), t(src), t(K), t(inv_K), t(T))
+    c = coords.cpu().numpy()
+    assert (c[..., 0] >= w - 1).any() and ((c[..., 0] > 0) & (c[..., 0] < w - 1)).any()
+    assert np.abs(warped.cpu().numpy() - R.sample(src, c)["warped"]).max() <= 1e-6
+    g = _view_synth_bwd(t(gw), t(src), coords, t(depth), t(K), t(inv_K), t(T))
+    one, both, _ = _assert_depth_gradient(g, gw, src, c, depth, K, inv_K, T, f"gdepth {shape}")
+    assert one.any() or both.any()
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 2048 * 256 + 3])
+def test_depth_to_updisp_backward_elementwise(n):
+    """gup = -g d^2 (1 / min - 1 / max) in fp64, per element within 4 * 2^-24 |ref|: the range, d d, its product with the range
+    and the product with g.  (With min = 0.1, max = 2 the range 1.f / 0.1f - 1.f / 2.f is 9.5 exactly.)  The last size
+    takes the grid-stride loop past its first trip; zero and mirrored gradients give exact zeros and exact symmetry."""
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    gen = torch.Generator().manual_seed(n)
+    d = (0.1 + 1.9 * torch.rand(n, generator=gen)).float()
+    d[0], d[-1] = 0.1, 2.0                                # spans [min_depth, max_depth] (n == 1: max_depth)
+    g = torch.randn(n, generator=gen)
+    g[::5] = 0.0
+    run = lambda gg: _updisp_bwd(lib, check, ptr, stream_ptr, gg, d)
+    got, neg = run(g), run(-g)
+    ref = -g.double() * d.double() ** 2 * (1 / 0.1 - 1 / 2.0)
+    err = (got.double() - ref).abs()
+    print(f"updisp bwd n = {n}: max err / |ref| {(err / ref.abs().clamp_min(1e-300)).max().item() / 2.0 ** -24:.3f} x 2^-24")
+    assert (err <= 4 * 2.0 ** -24 * ref.abs()).all()
+    assert (got[::5] == 0).all() and torch.equal(neg, -got)
+    assert n == 1 or (got[1::5] != 0).all()
+
+
+def _updisp_bwd(lib, check, ptr, stream_ptr, g, d):
+    n = g.numel()
+    out = torch.full((n + 64,), -7.25, device="cuda")
+    gd, dd = g.cuda(), d.cuda()                           # named: a temporary's block would be handed to the next one
+    check(lib.pd_depth_to_updisp_bwd(ptr(gd), ptr(dd), ptr(out), n, 0.1, 2.0, stream_ptr()), "pd_depth_to_updisp_bwd")
+    torch.cuda.synchronize()
+    assert (out[n:] == -7.25).all()
+    return out[:n].cpu()
+
+
+# ------------------------------------------------------------------ the whole term's disparity gradient
+def test_photometric_term_disparity_gradient_against_the_fp64_chain(g12, synth):
+    """d (loss_0 + loss_1) / d disparity of PF.photometric_loss at two scales against the chain of the
+    pieces in fp64, evaluated at the device's own discrete intermediates (sel, count, coords, warped):
+        reproj_ref.combine_grad -> autograd of the fp64 photometric mix at (warped, target) -> reproj_ref.view_synth_grad,
+        summed over the frames -> -g d^2 range -> loss_cases.ref_gather.
+    The yardstick is the same chain with the mix in fp32; the rule of loss_cases elementwise.  Excluded: disparity pixels
+    whose footprint touches an SSIM gate-undecided pixel of the winning frame -- none on the fixture's images (asserted,
+    cap 5 %; tests/test_reproj_ref.py shows the same on the fp64 images), so no blending toward the target (factor 0).
+    The scales are 19 x 37 and 1 x 37: pd_up_gather_bwd takes integer zoom factors only and 19 and 37 are prime, so the
+    coarser map of this fixture can only drop a whole axis (zoom 19 x 1, the any-ratio gather kernel)."""
+    import loss_cases as lc
+    import ssim_cases as sc
+    from polardepth import functional as PF, ops
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    dev = synth[1]
+    N = 2
+    sizes = [(H, W), (1, W)]
+    rng_d = 1 / 0.1 - 1 / 2.0
+    fix = dev["depth"]
+    disps, depths = [], []
+    for hs, ws in sizes:
+        dsmall = fix if (hs, ws) == (H, W) else torch.nn.functional.interpolate(fix, size=(hs, ws), mode="bilinear", align_corners=False)
+        disp = ((1.0 / dsmall - 1 / 2.0) / rng_d).contiguous()
+        out = torch.empty((N, 1, H, W), device="cuda")
+        check(lib.pd_disp_to_depth(ptr(disp), ptr(out), None, N, hs, ws, H, W, 0.1, 2.0, stream_ptr()), "pd_disp_to_depth")
+        assert out.min().item() >= g12["depth"].min() - 1e-3 and out.max().item() <= g12["depth"].max() + 1e-3
+        disps.append(disp.requires_grad_(True))
+        depths.append(out)
+    cfg = PF.LossCfg([0, 1], 0.1, 2.0, 0.35, 1e-3, H, W)
+    srcs, poses = [dev["src0"], dev["src1"]], [dev["T0"], dev["T1"]]
+    valid = torch.ones(N, 2, device="cuda")
+    losses, sels = PF.photometric_loss(cfg, disps, depths, dev["target"], srcs, dev["K"], dev["inv_K"], poses, valid,
+                                       noise=dev["noise"], details=True)
+    (losses[0] + losses[1]).backward()
+    with torch.no_grad():
+        identity = [ops.reprojection_loss(s, dev["target"]) for s in srcs]
+    tgt = torch.from_numpy(g12["target"])
+    for i, (hs, ws) in enumerate(sizes):
+        synth_i = [ops.view_synthesis(depths[i], s, dev["K"], dev["inv_K"], T) for s, T in zip(srcs, poses)]
+        again = [ops.view_synthesis(depths[i], s, dev["K"], dev["inv_K"], T) for s, T in zip(srcs, poses)]
+        assert all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(synth_i, again))
+        maps = [ops.reprojection_loss(w, dev["target"]) for w, _ in synth_i]
+        loss, sel, sums = ops.reproj_combine(maps, identity, dev["noise"], valid, False, details=True)
+        # the separate calls reproduce what the term computed inside, bit for bit
+        assert torch.equal(loss, losses[i].detach()) and torch.equal(sel, sels[i])
+        sel_np, count = sel.cpu().numpy(), float(sums[1].item())
+        assert 0 < count < sel_np.size and (sel_np == 0).any() and (sel_np == 1).any()
+        gmaps = R.combine_grad(1.0, sel_np, count, None, 2)
+        depth_np = depths[i].cpu().numpy()
+        und = torch.zeros(N, 1, H, W, dtype=torch.bool)
+        chain = {}
+        for dt in (sc.F32, sc.F64):
+            gdepth = np.zeros((N, 1, H, W))
+            for f in range(2):
+                warped = synth_i[f][0].cpu()
+                gw = sc.ref_grads(warped, tgt, torch.from_numpy(gmaps[f]), dt, 1)[0].double().numpy()
+                gdepth += R.view_synth_grad(gw, g12[f"src{f}"], synth_i[f][1].cpu().numpy(), depth_np, g12["K"], g12["inv_K"],
+                                            g12[f"T{f}"])
+                if dt == sc.F64:
+                    u = sc.gate_undecided(warped, tgt).any(1, keepdim=True) & torch.from_numpy(sel_np == f)[:, None]
+                    und |= torch.nn.functional.max_pool2d(u.double(), 5, 1, 2) > 0
+            gup = torch.from_numpy(-gdepth * depth_np.astype(np.float64) ** 2 * rng_d)
+            chain[dt] = lc.ref_gather(gup, hs, ws, torch.float64)
+        keep = lc.ref_gather(und.double(), hs, ws, torch.float64) == 0
+        excluded = 1.0 - keep.double().mean().item()
+        assert excluded <= 0.05
+        got = disps[i].grad.cpu()
+        assert got.abs().max().item() > 0
+        err, tol = lc.assert_elem(got[keep], chain[sc.F32][keep], chain[sc.F64][keep], f"disparity gradient scale {i}")
+        print(f"REPROJFIG | disparity gradient {hs} x {ws} | err {err:.2e} | tol {tol:.2e} | excluded {excluded:.4f} | "
+              f"scale of the gradient {chain[sc.F64].abs().max().item():.2e}")

@@ -88,3 +88,34 @@ def test_combine_rules_for_invalid_frames_ties_and_avg():
     sel = R.combine([a, b])["sel"]
     g = R.combine_grad(1.0, sel, 40.0, None, 2)
     assert np.array_equal(g[0][:, 0] != 0, sel == 0) and np.array_equal(g[1][:, 0] != 0, sel == 1)
+
+
+@pytest.mark.parametrize("f", [0, 1])
+def test_gradient_magnitude_bounds_the_gradient_and_frame_1_holds_the_clamped_populations(g12, f):
+    """view_synth_grad(magnitude=True) is the same expression with |.| on every summand: never below |gradient|, equal to it
+    where one channel term and one axis are all there is; frame 1 has at least 50 pixels with exactly one clamped axis and 50
+    with both (tests/test_reproj_gpu.py compares those with the single-axis value and with exactly 0)."""
+    a = (g12[f"gw{f}"], g12[f"src{f}"], g12[f"coords{f}_f32"], g12["depth"], g12["K"], g12["inv_K"], g12[f"T{f}"])
+    g, mag = R.view_synth_grad(*a), R.view_synth_grad(*a, magnitude=True)
+    assert (mag >= np.abs(g) * (1 - 1e-14)).all() and (mag[g != 0] > 0).all()
+    s = R.sample(g12[f"src{f}"], g12[f"coords{f}_f32"])
+    one, both = s["free_x"] ^ s["free_y"], ~s["free_x"] & ~s["free_y"]
+    assert (mag[:, 0][both] == 0).all()
+    if f == 1:
+        assert one.sum() >= 50 and both.sum() >= 50
+    one_channel = (a[0][:, :1], a[1][:, :1]) + a[2:]
+    g1, m1 = R.view_synth_grad(*one_channel), R.view_synth_grad(*one_channel, magnitude=True)
+    only_x = s["free_x"] & ~s["free_y"]                   # gu alone: a sum of two tap terms times du
+    assert (m1[:, 0][only_x] >= np.abs(g1[:, 0][only_x]) * (1 - 1e-14)).all() and only_x.any()
+
+
+def test_no_gate_undecided_ssim_pixel_on_the_fixture_images(g12):
+    """The whole-term disparity-gradient test excludes disparity pixels that hear of an SSIM gate-undecided pixel, capped at
+    5 %: on the fixture's images (fp64 warped frames against the target) there is none, so nothing is blended."""
+    import torch
+    import ssim_cases as sc
+    tgt = torch.from_numpy(g12["target"])
+    for f in range(2):
+        und = sc.gate_undecided(torch.from_numpy(g12[f"warped{f}_f64"]).float(), tgt, dilate=True)
+        print(f"frame {f}: undecided (dilated) {und.double().mean().item():.4f}")
+        assert und.double().mean().item() <= 0.05

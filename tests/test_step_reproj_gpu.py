@@ -1,6 +1,8 @@
 """The Trainer in the photometric mode (--depth_supervision True --pose_input True, without --depth_supervision_only) on
 synthetic items, at the size of tests/test_step_gpu.py: two training steps, the new loss entries, the gradient the term sends
-to every disparity scale, its place in ``loss``, and the configurations the constructor still refuses."""
+to every disparity scale, its place in ``loss``, and the configurations the constructor still refuses.  The synthetic loader's
+frame 0 is white noise, so nothing here says the numbers are right: that the term, its gradient and the weight gradients of the
+step equal a reference's is checked in tests/test_step_reproj_oracle_gpu.py, against the CPU oracle on a consistent batch."""
 import pytest
 import torch
 

@@ -324,7 +324,9 @@ int pd_conv2d_add(const void* x, const void* w, const void* addend, long ld_add,
 /* Weight gradient dW[Cout][KH][KW][Cin] (+ optional dbias[Cout]) of the convolution above
  * (modes 0 and 1).  dy is NHWC on the output grid with row stride ldd.  Partial tiles go to
  * `workspace` (pd_conv2d_wgrad_workspace bytes) and are summed deterministically; accumulate != 0
- * adds to dw/dbias instead of overwriting.  Replaces autograd's conv weight/bias gradient. */
+ * adds to dw/dbias instead of overwriting.  Replaces autograd's conv weight/bias gradient.
+ * The slice count of every kernel depends on the shape and `flags` only, never on ws_bytes:
+ * pd_conv2d_wgrad_workspace(M, Cout, K, flags) bytes hold it, and a larger workspace gives the same bits. */
 size_t pd_conv2d_wgrad_workspace(long M, int Cout, int K, unsigned flags);
 int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* dbias, void* workspace, size_t ws_bytes,
                     int N, int H, int W, int C, long sN, long sH, long sW, long sC,
@@ -340,16 +342,22 @@ int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* dbias, void* 
  * fp32 products on the bf16 matrix cores, every element split once (conv_wgrad_x3c_kernel; PD_CONV_FP32_MFMA: fp32 MFMA) --
  * the profiler label of a launch and bench.py's roofline object use it.  Reflection padding other than ReflectionPad2d(1) in
  * front of a same-size 3x3 runs the general kernel (0).  Who decides: route_wgrad (csrc/conv.hip) routes every launch, and this
- * query and pd_conv2d_wgrad_uses_bf16 read the same function's answer for dense, 16-byte aligned NHWC x and dy (ldd = Cout) with
- * a workspace of pd_conv2d_wgrad_workspace(M, Cout, K, flags) bytes; an empty output grid: 0. */
+ * query, pd_conv2d_wgrad_uses_bf16 and pd_conv2d_wgrad_route read the same function's answer for dense, 16-byte aligned NHWC x and
+ * dy (ldd = Cout); an empty output grid: 0. */
 int pd_conv2d_wgrad_uses_x3(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho, int Wo,
                             unsigned flags);
 /* 3 (conv_wgrad_roll_bf16_kernel) or 2 (conv_wgrad_halo_bf16_kernel): pd_conv2d_wgrad runs this shape on the single-bf16 form
  * of the kernel pd_conv2d_wgrad_uses_x3 names with the same code (PD_CONV_BF16 in `flags`); 0: the layer keeps the arithmetic it
- * has without the flag.  The slice count of these kernels depends on the shape and `flags` only, never on ws_bytes:
- * pd_conv2d_wgrad_workspace(M, Cout, K, flags) bytes hold it, and a larger workspace gives the same bits.  Pure host logic. */
+ * has without the flag.  Pure host logic. */
 int pd_conv2d_wgrad_uses_bf16(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho, int Wo,
                               unsigned flags);
+/* The launch pd_conv2d_wgrad plans for this shape (the arguments and the tensors of pd_conv2d_wgrad_uses_x3), as
+ * code | one << 2 | rows << 4: code = pd_conv2d_wgrad_uses_x3's answer, one = 1 for the single-bf16 form (pd_conv2d_wgrad_uses_bf16
+ * non-zero), rows >= 1 the partial rows ([Cout][K] weights + [Cout] bias each) the kernel writes and the ordered reduction sums --
+ * never more than pd_conv2d_wgrad_workspace(M, Cout, K, flags) pays for.  A flags word pd_conv2d_wgrad refuses is read without
+ * PD_CONV_BF16.  Pure host logic; the profiler label of a launch (ops.conv2d_wgrad) is made of this answer alone. */
+int pd_conv2d_wgrad_route(long M, int Cout, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho, int Wo,
+                          unsigned flags);
 
 /* 7x7 / stride-2 / pad-3 stems (pre_encoders.py:54 ShallowEncoder.Conv1, torchvision resnet conv1) executed as a
  * 4x4 / stride-1 / pad-2 convolution over the space-to-depth input [N][H/2][W/2][4C] (4C is a multiple of 4 ->

@@ -2545,35 +2545,53 @@ void wgrad_plan(long M, int Co, int K, unsigned flags, int* S, long* mper) {
     *S = (int)s; *mper = per;
 }
 
-// ---- routing: which kernel one weight gradient gets, and everything its launch needs.  route_wgrad is the ONLY place that
-// decides; pd_conv2d_wgrad launches from the route, and pd_conv2d_wgrad_uses_x3 / _uses_bf16 read the route of the dense tensors
-// they document with the workspace pd_conv2d_wgrad_workspace asks for.
+// halo-tile / rolling-row kernels: where the bf16 split is the arithmetic and no flag asks for a gather kernel
+inline bool wgrad_halo_enabled(unsigned flags) { return wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL)); }
+
+// Partial rows pd_conv2d_wgrad_workspace reserves = the most a plan may write: wgrad_plan's S, raised where the halo-tile /
+// rolling-row kernels may run (they cut their own slices; Cout and K bound their number) to that bound or one row per 64 pixels
+static int wgrad_rows_cap(long M, int Co, int K, unsigned flags) {
+    int S; long mper;
+    wgrad_plan(M, Co, K, flags, &S, &mper);
+    if (!wgrad_halo_enabled(flags)) return S;
+    const long own = std::min<long>(std::max(wgrad_halo_slices_bound(Co, K), wgrad_roll_slices_bound(Co, K)), (M + 63) / 64);
+    return S > own ? S : (int)own;
+}
+
+// ---- routing: which kernel one weight gradient gets, and everything its launch needs, the slice plan included.  route_wgrad
+// is the ONLY place that decides, from the shape and `flags` alone: its slice counts are capped by wgrad_rows_cap, the rows the
+// workspace query reserves, never by the ws_bytes a caller happens to own -- a larger workspace gives the same summation order,
+// the same bits.  pd_conv2d_wgrad launches from the route; pd_conv2d_wgrad_route (and its decoders _uses_x3 / _uses_bf16) read
+// the route of the dense tensors they document.
 enum WgradFamily { WGRAD_GENERAL = 0, WGRAD_UNI, WGRAD_UNI_X3, WGRAD_X3C, WGRAD_HALO, WGRAD_ROLL };
 struct WgradRoute {
     int family;             // general | scalar-pixel fp32 | scalar-pixel split in registers | x3c | halo-tile | rolling-row
+    int rows;               // partial rows the launch writes (the bias partials sit behind them): S; halo-tile: S x rows per slice
     int tco, S; long mper;  // the first four: output channels per workgroup, slices and pixels per slice (wgrad_plan)
     bool vec, row8;         // general kernel: 16-byte gather; x3c: the lean walker
     int nb, nbw;            // scalar-pixel kernels (x3c included): border rows / column pairs
-    int s_cap; bool bf16;   // halo-tile / rolling-row: partial rows the workspace may take; the one-term form (PD_CONV_BF16)
+    bool bf16;              // halo-tile / rolling-row: the one-term form (PD_CONV_BF16)
+    WgradHaloPlan halo;     // halo-tile
     WgradRollPlan roll;     // rolling-row
 };
 
-static WgradRoute route_wgrad(const WgradArgs& a, bool vec, unsigned flags, size_t ws_bytes) {
+static WgradRoute route_wgrad(const WgradArgs& a, bool vec, unsigned flags) {
     WgradRoute r{};
     r.vec = vec; r.tco = wgrad_tco(a.Co);
     wgrad_plan(a.M, a.Co, a.K, flags, &r.S, &r.mper);
+    r.rows = r.S;
     // every kernel but the general one: zero padding, or ReflectionPad2d(1) in front of a same-size 3x3
     const bool refl_ok = a.mode == MODE_REFLECT && a.pad == 1 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.Ho == a.H && a.Wo == a.W && a.H >= 3;
     if (!(a.mode == MODE_ZERO || refl_ok)) return r;
-    if (wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL)) && wgrad_halo_eligible(a, vec)) {
-        // halo-tile kernel (both operands split once per tile, transposed LDS reads): its slice count never exceeds what the
-        // workspace holds.  PD_CONV_BF16, the one-term forms: the slice count of the workspace the FLAGS ask for, whatever ws_bytes
-        // says -- a larger workspace must not change the summation order.
+    if (wgrad_halo_enabled(flags) && wgrad_halo_eligible(a, vec)) {
         r.bf16 = (flags & PD_CONV_BF16) != 0;
-        const size_t per_slice = ((size_t)a.Co * a.K + a.Co) * sizeof(float);
-        r.s_cap = (int)std::min<size_t>((r.bf16 ? pd_conv2d_wgrad_workspace(a.M, a.Co, a.K, flags) : ws_bytes) / per_slice, 1 << 20);
+        const int cap = wgrad_rows_cap(a.M, a.Co, a.K, flags);
         // 3x3 with long tile columns: all three filter rows per workgroup, input rows rolling through LDS
-        r.family = !(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, vec, r.s_cap, r.roll) ? WGRAD_ROLL : WGRAD_HALO;
+        if (!(flags & PD_CONV_WGRAD_ROW_WORKGROUPS) && wgrad_roll_eligible(a, vec, cap, r.roll)) {
+            r.family = WGRAD_ROLL; r.rows = r.roll.S;
+        } else {
+            r.family = WGRAD_HALO; wgrad_halo_plan(a, cap, r.halo); r.rows = r.halo.S * r.halo.rps;
+        }
         return r;
     }
     // scalar-pixel variant: 16-byte path, 64- or 32-wide co tile, even output rows (pixel pairs stay inside a row), border
@@ -2648,37 +2666,35 @@ static void fill_wgrad_args(WgradArgs& a, int N, int H, int W, int C, long sN, l
 }  // namespace
 
 extern "C" size_t pd_conv2d_wgrad_workspace(long M, int Co, int K, unsigned flags) {
-    int S; long mper;
-    wgrad_plan(M, Co, K, flags, &S, &mper);
-    // (the halo-tile kernel cuts its own slices; Cout and K bound their number)
-    if (wgrad_x3c_enabled(flags) && !(flags & (PD_CONV_GENERAL_KERNELS | PD_CONV_X3_IM2COL))) {
-        const int sh = std::max(wgrad_halo_slices_bound(Co, K), wgrad_roll_slices_bound(Co, K));
-        const long cap = (M + 63) / 64;
-        S = S > (sh < cap ? sh : (int)cap) ? S : (sh < cap ? sh : (int)cap);
-    }
-    return ((size_t)S * Co * K + (size_t)S * Co) * sizeof(float);
+    const size_t rows = (size_t)wgrad_rows_cap(M, Co, K, flags);
+    return (rows * Co * K + rows * Co) * sizeof(float);
 }
 
-// The route of the tensors the queries document: dense, 16-byte aligned NHWC x and dy (ldd = Cout), the workspace of
-// pd_conv2d_wgrad_workspace -- M is the caller's, also where it is no whole number of images; an empty grid: the general kernel
+// The route of the tensors the queries document: dense, 16-byte aligned NHWC x and dy (ldd = Cout) -- M is the caller's, also
+// where it is no whole number of images (the slice plan: of at least one); an empty grid: the general kernel, one row
+extern "C" int pd_conv2d_wgrad_route(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho,
+                                     int Wo, unsigned flags) {
+    if (Ho <= 0 || Wo <= 0) return 1 << 4;
+    if (!pd::conv_flags_ok(flags)) flags &= ~PD_CONV_BF16;       // (no one-term form under a word pd_conv2d_wgrad refuses)
+    WgradArgs a{};
+    fill_wgrad_args(a, std::max(1, (int)(M / ((long)Ho * Wo))), H, W, C, (long)H * W * C, (long)W * C, C, 1, Ho, Wo, Co, KH, KW, stride,
+                    pad, mode, 0, 0.f, 1.f, Co);
+    a.M = M;
+    const WgradRoute r = route_wgrad(a, vec16_ok(a.x, C, a.sN, a.sH, a.sW, a.sC, a.affine), flags);
+    const int code = r.family == WGRAD_ROLL ? 3 : r.family == WGRAD_HALO ? 2 : r.family == WGRAD_X3C ? 1 : 0;
+    return code | (r.bf16 ? 4 : 0) | r.rows << 4;
+}
+
 extern "C" int pd_conv2d_wgrad_uses_x3(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho,
                                        int Wo, unsigned flags) {
-    if (Ho <= 0 || Wo <= 0) return 0;
-    WgradArgs a{};
-    fill_wgrad_args(a, (int)(M / ((long)Ho * Wo)), H, W, C, (long)H * W * C, (long)W * C, C, 1, Ho, Wo, Co, KH, KW, stride, pad, mode,
-                    0, 0.f, 1.f, Co);
-    a.M = M;
-    const int family = route_wgrad(a, vec16_ok(a.x, C, a.sN, a.sH, a.sW, a.sC, a.affine), flags, pd_conv2d_wgrad_workspace(M, Co, a.K, flags)).family;
-    return family == WGRAD_ROLL ? 3 : family == WGRAD_HALO ? 2 : family == WGRAD_X3C ? 1 : 0;
+    return pd_conv2d_wgrad_route(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags) & 3;
 }
 
-// PD_CONV_BF16: the one-term forms of the halo-tile / rolling-row kernels, with the slice count of the workspace the flags ask
-// for (never of the caller's ws_bytes: a larger workspace must not change the summation order)
+// PD_CONV_BF16 changes the arithmetic of the halo-tile / rolling-row kernels only: their layers run the one-term forms
 extern "C" int pd_conv2d_wgrad_uses_bf16(long M, int Co, int C, int KH, int KW, int stride, int pad, int mode, int H, int W, int Ho,
                                          int Wo, unsigned flags) {
-    if (!(flags & PD_CONV_BF16) || !pd::conv_flags_ok(flags)) return 0;
-    const int r = pd_conv2d_wgrad_uses_x3(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags);
-    return r >= 2 ? r : 0;
+    const int r = pd_conv2d_wgrad_route(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags);
+    return r & 4 ? r & 3 : 0;
 }
 
 extern "C" int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* dbias, void* workspace, size_t ws_bytes,
@@ -2698,24 +2714,24 @@ extern "C" int pd_conv2d_wgrad(const void* x, const void* dy, void* dw, void* db
     const size_t need = pd_conv2d_wgrad_workspace(a.M, Co, a.K, flags);
     PD_REQUIRE(ws_bytes >= need, "pd_conv2d_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
     PD_REQUIRE(pd::aligned16(dy) && (ldd % 4 == 0 || Co < 4), "pd_conv2d_wgrad: dy must be 16-byte aligned rows");
-    const WgradRoute r = route_wgrad(a, vec16_ok(x, C, sN, sH, sW, sC, affine), flags, ws_bytes);
+    const WgradRoute r = route_wgrad(a, vec16_ok(x, C, sN, sH, sW, sC, affine), flags);
+    const int cap = wgrad_rows_cap(a.M, Co, a.K, flags);        // the rows `need` pays for
+    PD_REQUIRE(r.rows <= cap, "pd_conv2d_wgrad: %d partial rows planned, the workspace holds %d", r.rows, cap);
     a.S = r.S; a.mper = r.mper;
     PD_REQUIRE(a.mper * ldd * 4 < 0x7fffffffL, "pd_conv2d_wgrad: slice too large for 32-bit offsets");
     PD_REQUIRE((a.mper / ((long)Ho * Wo) + 2) * sN * 4 < 0x7fffffffL, "pd_conv2d_wgrad: image too large for 32-bit offsets");
     a.part = (float*)workspace;
-    a.bpart = dbias ? a.part + (size_t)a.S * Co * a.K : nullptr;
+    a.bpart = dbias ? a.part + (size_t)r.rows * Co * a.K : nullptr;       // bias partials behind the weight tiles
     a.ktiles = (a.K + WG_K - 1) / WG_K; a.ctiles = (Co + r.tco - 1) / r.tco;
     hipStream_t st = (hipStream_t)stream;
-    int S = a.S;       // partial rows written: the halo-tile / rolling-row kernels cut their own slices
-    if (r.family == WGRAD_ROLL) S = launch_wgrad_roll(a, r.roll, st, dbias != nullptr, r.bf16);
-    else if (r.family == WGRAD_HALO) S = launch_wgrad_halo(a, r.s_cap, st, dbias != nullptr, r.bf16);
+    if (r.family == WGRAD_ROLL) launch_wgrad_roll(a, r.roll, st, dbias != nullptr, r.bf16);
+    else if (r.family == WGRAD_HALO) launch_wgrad_halo(a, r.halo, st, dbias != nullptr, r.bf16);
     else if (int rc = launch_wgrad_slices(a, r, dbias != nullptr, st)) return rc;
-    a.bpart = dbias ? a.part + (size_t)S * Co * a.K : nullptr;
     if (int rc = pd::check_launch("pd_conv2d_wgrad")) return rc;
     const long nw = (long)Co * a.K;
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(256), 0, st, a.part, (float*)dw, S, nw, accumulate);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(256), 0, st, a.part, (float*)dw, r.rows, nw, accumulate);
     if (dbias)
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(256), 0, st, a.bpart, (float*)dbias, S, (long)Co, accumulate);
+        hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((Co + 63) / 64)), dim3(256), 0, st, a.bpart, (float*)dbias, r.rows, (long)Co, accumulate);
     return pd::check_launch("pd_conv2d_wgrad/reduce");
 }
 

@@ -303,7 +303,6 @@ __global__ __launch_bounds__(NT, KS == 3 ? 3 : 2) void conv_wgrad_halo_x3_kernel
 static int wgrad_halo_tw(int Ho, int Wo) {
     return Wo % 32 == 0 ? 32 : (Wo % 16 == 0 && Ho % 2 == 0) ? 16 : (Wo % 8 == 0 && Ho % 4 == 0) ? 8 : (Wo % 4 == 0 && Ho % 8 == 0) ? 4 : 0;
 }
-static bool wgrad_halo_co32(const WgradArgs& a) { return a.Co % 64 != 0; }
 static bool wgrad_halo_eligible(const WgradArgs& a, bool vec) {
     if (!(vec && (a.mode == MODE_ZERO || (a.mode == MODE_REFLECT && a.pad < a.H && a.pad < a.W)) && a.stride == 1 && a.KH == a.KW &&
           (a.KH == 3 || a.KH == 5) && a.pad < a.KH && wgrad_halo_tw(a.Ho, a.Wo) != 0 && a.ldd % 4 == 0 &&
@@ -330,28 +329,34 @@ static int wgrad_halo_slices_bound(int Co, int K) {
     return best;
 }
 
-// s_cap: partial rows the caller's workspace holds; returns the partial rows written
-static int launch_wgrad_halo(WgradArgs a, int s_cap, hipStream_t st, bool bias, bool bf16 = false) {
-    WgradHaloArgs ha;
-    const bool co32 = wgrad_halo_co32(a);
-    ha.ncb = (a.C + 63) / 64;
-    a.ctiles = co32 ? a.Co / 32 : a.Co / 64;
-    const int tw = wgrad_halo_tw(a.Ho, a.Wo);
-    ha.tiles_w = a.Wo / tw;
-    ha.tiles_h = a.Ho / (wgh::NPX / tw);
-    ha.ntiles_total = a.N * ha.tiles_h * ha.tiles_w;
-    const int per_slice_wgs = a.KH * ha.ncb * a.ctiles;
-    const int rows_per_slice = co32 ? 2 : 1;
+// Plan: slices = runs of consecutive tiles (wgrad_halo_eligible holds, N >= 1).  rows_cap: partial rows the workspace holds
+// (wgrad_rows_cap); a slice writes rps of them (a 32-channel workgroup: two), the bias partials sit behind S * rps rows.
+struct WgradHaloPlan { int tw, tiles_w, tiles_h, ntiles, tps, S, rps; bool co32; };
+static void wgrad_halo_plan(const WgradArgs& a, int rows_cap, WgradHaloPlan& p) {
+    p.co32 = a.Co % 64 != 0;
+    p.rps = p.co32 ? 2 : 1;
+    p.tw = wgrad_halo_tw(a.Ho, a.Wo);
+    p.tiles_w = a.Wo / p.tw;
+    p.tiles_h = a.Ho / (wgh::NPX / p.tw);
+    p.ntiles = a.N * p.tiles_h * p.tiles_w;
     int S = wgrad_halo_slices(a.KH, a.C, a.Co);
-    if (S > s_cap / rows_per_slice) S = s_cap / rows_per_slice;
+    if (S > rows_cap / p.rps) S = rows_cap / p.rps;
     if (S < 1) S = 1;
-    if (S > ha.ntiles_total) S = ha.ntiles_total;
-    ha.tiles_per_slice = (ha.ntiles_total + S - 1) / S;
-    S = (ha.ntiles_total + ha.tiles_per_slice - 1) / ha.tiles_per_slice;
-    a.S = S;
-    if (a.bpart) a.bpart = a.part + (size_t)S * rows_per_slice * a.Co * a.K;          // bias partials behind the weight tiles
+    if (S > p.ntiles) S = p.ntiles;
+    p.tps = (p.ntiles + S - 1) / S;
+    p.S = (p.ntiles + p.tps - 1) / p.tps;
+}
+
+static void launch_wgrad_halo(WgradArgs a, const WgradHaloPlan& p, hipStream_t st, bool bias, bool bf16) {
+    WgradHaloArgs ha;
+    const bool co32 = p.co32;
+    const int tw = p.tw;
+    ha.ncb = (a.C + 63) / 64;
+    ha.tiles_w = p.tiles_w; ha.tiles_h = p.tiles_h; ha.ntiles_total = p.ntiles; ha.tiles_per_slice = p.tps;
+    a.ctiles = co32 ? a.Co / 32 : a.Co / 64;
+    a.S = p.S;
     ha.g = a;
-    const long nwg = (long)per_slice_wgs * S;
+    const long nwg = (long)a.KH * ha.ncb * a.ctiles * p.S;
     const dim3 grid((unsigned)((nwg + 7) / 8 * 8)), block(NT);
 #define PD_WGH(KSV, TWV, C32) with_bool(bias, [&](auto b) { \
         if (bf16) hipLaunchKernelGGL((conv_wgrad_halo_x3_kernel<KSV, TWV, decltype(b)::value, C32, 1>), grid, block, 0, st, ha); \
@@ -360,5 +365,4 @@ static int launch_wgrad_halo(WgradArgs a, int s_cap, hipStream_t st, bool bias, 
     else if (a.KH == 3) { if (tw == 32) PD_WGH(3, 32, false); else if (tw == 16) PD_WGH(3, 16, false); else if (tw == 8) PD_WGH(3, 8, false); else PD_WGH(3, 4, false); }
     else { if (tw == 32) PD_WGH(5, 32, false); else if (tw == 16) PD_WGH(5, 16, false); else PD_WGH(5, 8, false); }
 #undef PD_WGH
-    return S * rows_per_slice;
 }

@@ -248,6 +248,7 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_roll_x3_kernel(const WgradRo
 }
 
 // Plan: slices = (tile column) x (row range).  As many slices per column as fill the 512 resident workgroup slots once.
+// s_cap: partial rows the workspace holds (wgrad_rows_cap); one per slice.
 struct WgradRollPlan { int tw, tiles_w, tiles_h, spc, rps, S; };
 static bool wgrad_roll_plan(const WgradArgs& a, int s_cap, WgradRollPlan& p) {
     p.tw = a.Wo % 32 == 0 ? 32 : (a.Wo % 16 == 0 && a.Ho % 2 == 0) ? 16 : 0;
@@ -279,13 +280,12 @@ static int wgrad_roll_slices_bound(int Co, int K) {
     return 512 / (per > 0 ? per : 1);
 }
 
-static int launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st, bool bias, bool bf16 = false) {
+static void launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st, bool bias, bool bf16) {
     WgradRollArgs ra;
     ra.ncb = a.C / 64;
-    a.ctiles = a.Co / 64;
     ra.tiles_w = p.tiles_w; ra.tiles_h = p.tiles_h; ra.spc = p.spc; ra.rps = p.rps;
+    a.ctiles = a.Co / 64;
     a.S = p.S;
-    if (a.bpart) a.bpart = a.part + (size_t)p.S * a.Co * a.K;          // bias partials behind the weight tiles
     ra.g = a;
     const long nwg = (long)ra.ncb * a.ctiles * p.S;
     const dim3 grid((unsigned)((nwg + 7) / 8 * 8)), block(NT);
@@ -294,5 +294,4 @@ static int launch_wgrad_roll(WgradArgs a, const WgradRollPlan& p, hipStream_t st
         else hipLaunchKernelGGL((conv_wgrad_roll_x3_kernel<TWV, decltype(b)::value>), grid, block, 0, st, ra); })
     if (p.tw == 32) PD_WGR(32); else PD_WGR(16);
 #undef PD_WGR
-    return p.S;
 }

@@ -46,6 +46,7 @@ SIGNATURES = {
     "pd_conv2d_uses_bf16": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u]),
     "pd_conv2d_route": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u]),
     "pd_conv2d_wgrad_uses_bf16": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u]),
+    "pd_conv2d_wgrad_route": (_i, [_l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _u]),
     "pd_conv2d": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                        _i, _f, _f, _l, _u, _vp]),
     "pd_conv16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _l, _i, _i, _i, _l, _i, _i, _vp]),

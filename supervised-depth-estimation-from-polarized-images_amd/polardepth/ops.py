@@ -279,6 +279,11 @@ def _workspace(nbytes, device):
     return buf
 
 
+# pd_conv2d_wgrad_route's code | one-term bit -> profiler label (the one-term forms exist for the halo-tile / rolling-row kernels only)
+_WGRAD_LABELS = ("conv_wgrad_kernel", "conv_wgrad_x3c_kernel", "conv_wgrad_halo_x3_kernel", "conv_wgrad_roll_x3_kernel",
+                 None, None, "conv_wgrad_halo_bf16_kernel", "conv_wgrad_roll_bf16_kernel")
+
+
 def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, mode=MODE_ZERO, affine=None, dw=None, dbias=None,
                  want_bias=False, accumulate=False, alg_k=None, bf16=None):
     """dW (channels_last [Co,Ci,kh,kw]) and optionally dbias of conv(x, w) given dy (NHWC).
@@ -313,12 +318,8 @@ def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, mode=MODE_ZERO, affine=None, d
     sub, div = (affine if affine is not None else (0.0, 1.0))
     sN, sC, sH, sW = x.stride()
     fits = affine is None and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0 and dy.stride(3) % 4 == 0
-    x3c = lib.pd_conv2d_wgrad_uses_x3(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags & ~CONV_BF16) if fits else 0
-    one = lib.pd_conv2d_wgrad_uses_bf16(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags) if fits else 0
-    label = ("conv_wgrad_roll_bf16_kernel" if one == 3 else "conv_wgrad_halo_bf16_kernel" if one == 2 else
-             "conv_wgrad_roll_x3_kernel" if x3c == 3 else "conv_wgrad_halo_x3_kernel" if x3c == 2 else "conv_wgrad_x3c_kernel" if x3c else
-             "conv_wgrad_kernel")
-    _profiled(label,
+    route = lib.pd_conv2d_wgrad_route(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags) if fits else 0
+    _profiled(_WGRAD_LABELS[route & 7],
               2.0 * M * Co * (alg_k if alg_k is not None else K),
               lambda: check(lib.pd_conv2d_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), N, H, W, C,
                                                 sN, sH, sW, sC, Ho, Wo, Co, KH, KW, stride, pad, mode,

@@ -613,3 +613,22 @@ def check_fp32_cpu(row):
     if d["bias"] is not None:
         z = z + d["bias"].float().view(1, -1, 1, 1)
     return torch.equal(z, d["z"].float())
+
+
+# ====================================================================================================== raw C ABI
+def wgrad_raw(xd, dyd, w_shape, p, mode, ws_bytes, flags, dbias=None):
+    """pd_conv2d_wgrad through the C ABI with a workspace of exactly `ws_bytes` bytes (ops.conv2d_wgrad passes a cached buffer
+    of whatever size it has grown to): channels_last device tensors x and dy on the same grid, stride 1; dbias, where given, is
+    overwritten like dW.  Returns dW on the CPU."""
+    from polardepth._lib import lib, stream_ptr
+    N, C, H, W = xd.shape
+    Co, k = w_shape[0], w_shape[2]
+    dw = torch.empty(tuple(w_shape), device="cuda", memory_format=torch.channels_last)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    sN, sC, sH, sW = xd.stride()
+    rc = lib.pd_conv2d_wgrad(xd.data_ptr(), dyd.data_ptr(), dw.data_ptr(), None if dbias is None else dbias.data_ptr(),
+                             ws.data_ptr(), ws_bytes, N, H, W, C, sN, sH, sW, sC, H, W, Co, k, k, 1, p, mode, 0, 0.0, 1.0,
+                             dyd.stride(3), 0, flags, stream_ptr())
+    assert rc == 0, lib.pd_last_error()
+    torch.cuda.synchronize()
+    return dw.cpu()

@@ -424,3 +424,19 @@ def test_routing_queries_over_a_shape_sweep():
             if b == 3:      # rolling rows: 3x3, whole 64-channel blocks, at least 384 workgroups' worth of slices in the workspace
                 assert k == 3 and C % 64 == 0 and Co % 64 == 0 and not (fl & 32)
                 assert (ws // per) * (C // 64) * (Co // 64) >= 384
+
+
+def test_wgrad_route_decodes_to_the_other_queries_and_fits_its_workspace():
+    """pd_conv2d_wgrad_route = code | one << 2 | rows << 4 over the recorded sweep (tests/conv_routes.py): the plan writes at least
+    one partial row and never more than pd_conv2d_wgrad_workspace pays for, and pd_conv2d_wgrad_uses_x3 / _uses_bf16 are its
+    decoders."""
+    import conv_routes
+    lib = _lib.lib
+    for (M, Co, C, k, s, pad, mode, H, W, Ho, Wo, fl) in conv_routes.wgrad_points():
+        args = (M, Co, C, k, k, s, pad, mode, H, W, Ho, Wo, fl)
+        r = lib.pd_conv2d_wgrad_route(*args)
+        K = k * k * C
+        assert r >> 4 >= 1, (args, r)
+        assert (r >> 4) * 4 * (Co * K + Co) <= lib.pd_conv2d_wgrad_workspace(M, Co, K, fl), (args, r)
+        assert r & 3 == lib.pd_conv2d_wgrad_uses_x3(*args), (args, r)
+        assert lib.pd_conv2d_wgrad_uses_bf16(*args) == (r & 3 if r & 4 else 0), (args, r)

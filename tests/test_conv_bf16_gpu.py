@@ -13,8 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import wgrad_raw
 from polardepth import ops
-from polardepth._lib import stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -192,22 +192,6 @@ def test_bf16_denormal_operands():
     assert measured == ("flushed" if DENORMALS_FLUSHED else "kept"), measured
 
 
-def _wgrad_raw(xd, dyd, w_shape, p, mode, ws_bytes):
-    lib = ops.lib
-    N, C, H, W = xd.shape
-    Co = w_shape[0]
-    k = w_shape[2]
-    dw = torch.empty(tuple(w_shape), device="cuda", memory_format=torch.channels_last)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-    sN, sC, sH, sW = xd.stride()
-    rc = lib.pd_conv2d_wgrad(xd.data_ptr(), dyd.data_ptr(), dw.data_ptr(), None, ws.data_ptr(), ws_bytes, N, H, W, C,
-                             sN, sH, sW, sC, H, W, Co, k, k, 1, p, mode, 0, 0.0, 1.0, dyd.stride(3), 0, BF16,
-                             stream_ptr())
-    assert rc == 0, lib.pd_last_error()
-    torch.cuda.synchronize()
-    return dw.cpu()
-
-
 @pytest.mark.parametrize("case", [CASES[1], CASES[0], CASES[5]])
 def test_bf16_determinism_and_workspace_independence(case):
     """The same launch twice: bit-identical (forward, data gradient, weight gradient); the weight gradient also with a
@@ -221,9 +205,9 @@ def test_bf16_determinism_and_workspace_independence(case):
     for fn in (lambda: ops.conv2d_fwd(xd, wd, None, 1, p, mode=mode), lambda: ops.conv2d_dgrad(dyd, wd, (H, W), 1, p)):
         assert torch.equal(_run(fn, BF16), _run(fn, BF16))
     need = ops.lib.pd_conv2d_wgrad_workspace(N * H * W, Co, k * k * C, BF16)
-    a = _wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, need)
-    b = _wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, need)
-    c = _wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, 8 * need)
+    a = wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, need, BF16)
+    b = wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, need, BF16)
+    c = wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, 8 * need, BF16)
     assert torch.equal(a, b) and torch.equal(a, c)
     assert not torch.equal(a, _run(lambda: ops.conv2d_wgrad(xd, dyd, (Co, C, k, k), 1, p, mode=mode), ops.CONV_AUTO).float())
 

@@ -2,10 +2,13 @@
 
 Tolerance: fp32 MFMA accumulates like an fmaf chain in a fixed k order (exact fp32), the CPU
 reference in another order; |err| <= ~1e-6 * sum|a*b|.  Checked as rtol 2e-5 on the output scale."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import wgrad_raw
 from polardepth import ops
 
 pytestmark = pytest.mark.gpu
@@ -785,3 +788,84 @@ def test_bf16x3_kernel_cancellation_heavy_contraction():
     split, fp32 = _three(lambda: ops.conv2d_dgrad(xd, wd, (H, W), stride=1, pad=2))
     e_s, e_f = (split.double() - ref).abs().max().item() / sc, (fp32.double() - ref).abs().max().item() / sc
     assert e_s <= 1e-6 and e_f <= 1e-6 and e_s <= 1.5 * e_f + 1e-9, ("dgrad", e_s, e_f)
+
+
+# ------------------------------------------------------------------ the weight gradient's bits do not depend on the workspace size
+# (N, C, H, W, Co, k, mode), bias, binding: on the first three planes one partial row per 64 pixels is fewer than the halo-tile
+# kernel's own slice count, so the rows the workspace query reserves cap the plan -- and a caller's larger buffer must not lift it
+WS_CASES = [
+    ((2, 64, 32, 48, 64, 3, 0), False, True),       # 2 x 16 tiles
+    ((1, 64, 16, 32, 64, 5, 0), False, True),       # 5x5
+    ((1, 32, 16, 32, 32, 3, 1), True, True),        # 32-channel workgroups: two partial rows per slice, the bias partials behind them
+    ((1, 64, 16, 18, 64, 3, 0), False, False),      # no tile shape divides the plane: the gather kernel
+    ((1, 12, 9, 11, 24, 3, 0), True, False),        # general kernel
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _ws_case(case):
+    """Operands, fp64 references (of the values and of the absolute values) and the fp32-MFMA kernel's error: once per case."""
+    N, C, H, W, Co, k, mode = case
+    p = k // 2
+    g = torch.Generator().manual_seed(sum(case))
+    x = torch.randn(N, C, H, W, generator=g)
+    dy = torch.randn(N, Co, H, W, generator=g)
+
+    def wgrad64(a, b):
+        ap = F.pad(a.double(), (p, p, p, p), mode="reflect" if mode == ops.MODE_REFLECT else "constant")
+        return torch.nn.grad.conv2d_weight(ap, (Co, C, k, k), b.double(), padding=0)
+
+    ref_dw, abs_dw = wgrad64(x, dy), wgrad64(x.abs(), dy.abs())
+    xd = x.cuda().contiguous(memory_format=torch.channels_last)
+    dyd = dy.cuda().contiguous(memory_format=torch.channels_last)
+    need = ops.lib.pd_conv2d_wgrad_workspace(N * H * W, Co, k * k * C, ops.CONV_FP32_MFMA)
+    fp32 = wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, need, ops.CONV_FP32_MFMA)
+    e_fp32 = (fp32.double() - ref_dw).abs().max().item() / ref_dw.abs().max().item()
+    return xd, dyd, ref_dw, abs_dw, dy.double().sum((0, 2, 3)), dy.double().abs().sum((0, 2, 3)), e_fp32
+
+
+@pytest.mark.parametrize("flags", [ops.CONV_AUTO, ops.CONV_BF16], ids=["auto", "bf16"])
+@pytest.mark.parametrize("case,bias,binding", WS_CASES)
+def test_weight_gradient_bits_do_not_depend_on_the_workspace_size(case, bias, binding, flags):
+    """pd_conv2d_wgrad with exactly the bytes pd_conv2d_wgrad_workspace asks for, with one partial row more and with eight times
+    as many: the same bits of dW (and dbias), for the kernels that cut their own slices and for the others.  The exact-size
+    result against the fp64 weight gradient: the yardstick of the split-kernel weight gradients above (<= 2e-5 of the scale,
+    <= 1.5 x the fp32-MFMA kernel + 2e-7; dbias <= 2e-5); where PD_CONV_BF16 selects a one-term form, the a-priori bound of two
+    operands rounded to 8 significant bits, per element (tests/test_conv_bf16_gpu.py)."""
+    N, C, H, W, Co, k, mode = case
+    p, M, K = k // 2, N * H * W, k * k * C
+    xd, dyd, ref_dw, abs_dw, ref_db, abs_db, e_fp32 = _ws_case(case)
+    route = ops.lib.pd_conv2d_wgrad_route(M, Co, C, k, k, 1, p, mode, H, W, H, W, flags)
+    if binding:
+        assert route & 3 == 2 and route >> 4 == (M + 63) // 64, (route & 7, route >> 4)
+    need = ops.lib.pd_conv2d_wgrad_workspace(M, Co, K, flags)
+    got = []
+    for ws_bytes in (need, need + 4 * (Co * K + Co), 8 * need):
+        db = torch.full((Co,), float("nan"), device="cuda") if bias else None
+        dw = wgrad_raw(xd, dyd, (Co, C, k, k), p, mode, ws_bytes, flags, db)
+        got.append((dw, db.cpu() if bias else None))
+    for dw, db in got[1:]:
+        assert torch.equal(dw, got[0][0])
+        assert not bias or torch.equal(db, got[0][1])
+    dw, db = got[0]
+    if route & 4:
+        rel = 2.0 ** -8 + M * 2.0 ** -23
+        assert ((dw.double() - ref_dw).abs() - rel * abs_dw).max().item() <= 0.0
+        assert not bias or ((db.double() - ref_db).abs() - rel * abs_db).max().item() <= 0.0
+    else:
+        err = (dw.double() - ref_dw).abs().max().item() / ref_dw.abs().max().item()
+        assert err <= 2e-5 and err <= 1.5 * e_fp32 + 2e-7, (err, e_fp32)
+        assert not bias or (db.double() - ref_db).abs().max().item() / ref_db.abs().max().item() <= 2e-5
+
+
+def test_weight_gradient_bits_do_not_depend_on_what_ran_before(monkeypatch):
+    """ops.conv2d_wgrad takes its workspace from a per-stream cache that only grows: the same call before and after a larger
+    layer has grown it returns the same bits."""
+    (N, C, H, W, Co, k, mode), _, _ = WS_CASES[0]
+    xd, dyd = _ws_case(WS_CASES[0][0])[:2]
+    monkeypatch.setattr(ops, "_ws_cache", {})          # (a fresh process: whatever ran before this test has grown the cache)
+    with ops.conv_flags(wgrad=ops.CONV_AUTO):
+        a = ops.conv2d_wgrad(xd, dyd, (Co, C, k, k), stride=1, pad=k // 2, mode=mode).clone()
+        assert ops._workspace(64 << 20, xd.device).numel() >= 64 << 20
+        b = ops.conv2d_wgrad(xd, dyd, (Co, C, k, k), stride=1, pad=k // 2, mode=mode)
+    assert torch.equal(a, b)

@@ -634,6 +634,56 @@ int pd_reproj_combine_fwd(const void* const* reproj, const void* const* identity
                           int avg, void* stream);
 int pd_reproj_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid, void* const* greproj,
                           int F, int N, int H, int W, int avg, void* stream);
+
+/* ------------------------------------------------------------------------- multi-frame cost volume (csrc/matching.hip)
+ * pd_cost_volume -- ManyDepth's plane sweep from known poses: ResnetEncoderMatching.match_features, compute_confidence_mask
+ * and the lowest-cost map (resnet_encoder.py:430-511, 534-541, 620-630), forward only (the reference runs it under no_grad).
+ *   cur     [B,h,w,C] fp32 NHWC, 16-byte aligned         features of the current frame (1/4 resolution)
+ *   lookup  [B,F,h,w,C] fp32 NHWC, 16-byte aligned       features of the F lookup frames
+ *   T       [B,F,4,4] fp32 row-major                     relative pose, current camera -> lookup camera
+ *   K, inv_K [B,4,4] fp32                                intrinsics of the feature resolution
+ *   bins    [D] fp32 ON THE DEVICE                       hypothesised depths, read by the kernel: new bins need no rebuild and
+ *                                                        no host synchronisation
+ *   valid   [B,F] fp32 or NULL                           0 = frame f of item b is skipped (NULL: none is)
+ *   cost    [B,h,w,D] fp32 out, pixel stride ldc >= D floats: ldc > D writes into channels of a wider NHWC buffer (the
+ *           input of reduce_conv, beside the 64 feature channels) and leaves its other channels alone
+ *   missing [B,h,w,D] uint8 out or NULL      confidence [B,h,w] fp32 out (0 / 1)
+ *   argmin  [B,h,w] int32 out                lowest [B,h,w] fp32 out = 1 / bins[argmin]
+ * 1. Per item and frame, in fp64 from the fp32 inputs, sums left to right, no fused multiply-add (as pd_view_synth_fwd):
+ *      P[i][j] = K[i][0] T[0][j] + K[i][1] T[1][j] + K[i][2] T[2][j] + K[i][3] T[3][j]      (i < 3)
+ *    A frame with valid[b][f] == 0 is skipped entirely.  (polardepth.ops.cost_volume also clears valid where the 16
+ *    elements of T[b][f] sum to 0, the reference's "missing frame" rule, :463.)
+ * 2. Per pixel (x, y) and bin d, in fp64 likewise:
+ *      r[i] = inv_K[i][0] x + inv_K[i][1] y + inv_K[i][2];   p = bins[d] * r;
+ *      hh[i] = P[i][0] p[0] + P[i][1] p[1] + P[i][2] p[2] + P[i][3];
+ *      u = hh[0] / (hh[2] + 1e-7),  v = hh[1] / (hh[2] + 1e-7), each rounded once to fp32.
+ *    Project3D's normalisation and grid_sample's align_corners=True un-normalisation cancel: (u, v) are pixel coordinates
+ *    of the lookup frame.  A point behind the lookup camera is NOT rejected (the reference does not reject it).
+ * 3. Edge mask, decided on the fp32 coordinates (a NaN gives 0):
+ *      m = (u >= 2) && (u <= w-2) && (v >= 2) && (v <= h-2) && (2 <= x < w-2) && (2 <= y < h-2).
+ *    Where m = 1 all four bilinear taps lie inside the image, so the reference's padding_mode='zeros' never shows in a
+ *    value that is used: the kernel samples ONLY where m = 1, needs no clamp, and reads nothing for the other entries.
+ * 4. Where m = 1, in fp32 without fused multiply-add: x0 = floor(u), wx1 = u - x0, wx0 = 1 - wx1 (y likewise),
+ *      warped_c = ((L[y0][x0][c] (wx0 wy0) + L[y0][x0+1][c] (wx1 wy0)) + L[y0+1][x0][c] (wx0 wy1)) + L[y0+1][x0+1][c] (wx1 wy1)
+ *      diff = (sum_c |warped_c - cur_c|) / (float)C
+ *    The order of the channel sum: 16 partial sums, partial l adding channels 4l, 4l+1, 4l+2, 4l+3, then 64 + 4l, ... in
+ *    ascending order from 0 (a partial without channels is 0); then a binary tree: partials (0,1), (2,3), ... are added,
+ *    then those pairs' sums pairwise, four levels in all.
+ * 5. Over the valid frames in frame order, where m = 1:  s += diff;  n += (diff > 0).
+ * 6. c = s / ((float)n + 1e-7f), in fp32 exactly as written (the reference's fp32 run: 1 + 1e-7 rounds up, 2 + 1e-7 not).
+ * 7. Per pixel over its D bins: missing = (c == 0); mx = max_d c (NaN if any c is NaN); filled = missing ? mx : c;
+ *    confidence = (number of bins with c > 0) == D; argmin = the FIRST index of the minimum of (filled == 0 ? 100 : filled),
+ *    where a NaN counts as below every number (the first NaN wins, as numpy.argmin); lowest = 1 / bins[argmin];
+ *    cost = filled, or filled * confidence when apply_confidence != 0 (resnet_encoder.py:630).
+ * 8. Non-finite features and poses propagate through these expressions and no further: a NaN coordinate masks its entry,
+ *    a NaN feature makes the sums it enters NaN; nothing of one batch item reaches another.
+ * A pixel outside the interior, an item without a valid frame and F = 0 give cost 0, missing 1, confidence 0, argmin 0.
+ * Limits: C % 4 == 0 (C >= 4), 1 <= D <= 128, 0 <= F <= PD_REPROJ_MAX_FRAMES, h, w >= 1, h * w <= 2^30, 0 <= B <= 65535
+ * (B = 0 does nothing), ldc >= D.  One launch, no atomics, no workspace, no host synchronisation; bit-reproducible. */
+int pd_cost_volume(const void* cur, const void* lookup, const void* T, const void* K, const void* inv_K, const void* bins,
+                   const void* valid, void* cost, long ldc, void* missing, void* confidence, void* argmin, void* lowest,
+                   int B, int F, int h, int w, int C, int D, int apply_confidence, void* stream);
+
 /* compute_depth_errors (layers.py:539-557) per image on the device: metrics [N][8] = abs_rel, sq_rel, rmse,
  * rmse_log, a1, a2, a3, pixel count over min < gt < max (and mask == mask_value when mask != NULL, the
  * per-material selection of trainer.py:1385-1411); pred is clamped to [min, max] (trainer.py:1422-1423).

@@ -15,8 +15,10 @@ supervised terms, plus the neighbouring frames of ``--frame_ids`` warped into th
 the ground-truth relative poses of ``_pose/%06d.txt``, compared by monodepth2's reprojection loss (minimum over the frames,
 automasking; ``--no_ssim``, ``--disable_automasking``, ``--avg_reprojection`` are honoured).  It adds ``reproj_loss/{s}`` to
 ``loss/{s}`` and their mean over the scales to ``loss``; under data parallelism the term is normalised per rank; it is not
-captured yet (``PD_STEP_GRAPH=1`` is refused with it).  The pose network, the cost-volume student (``--train_student``),
-``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
+captured yet (``PD_STEP_GRAPH=1`` is refused with it).  The cost-volume student's building blocks exist -- the plane sweep
+(``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training branch (``--train_student``: matching
+augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it, the pose network, ``--v1_multiscale``, DPT
+and stereo branches raise NotImplementedError.
 
 What runs where: every tensor operation of a training step is a hand-written HIP kernel from
 libpolardepth.so (polar preprocessing K1, implicit-GEMM convolutions K2, fused BN/ReLU/pool chains

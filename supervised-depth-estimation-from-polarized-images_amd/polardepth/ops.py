@@ -480,6 +480,71 @@ def reproj_combine(reproj, identity=None, noise=None, valid=None, avg=False, det
     return (loss, sel, sums) if details else loss
 
 
+# ------------------------------------------------------------------ multi-frame cost volume (csrc/matching.hip)
+COST_VOLUME_MAX_BINS = 128
+
+
+def cost_volume(cur, lookup, poses, K, inv_K, bins, valid=None, out=None, apply_confidence=False, want_missing=False):
+    """ManyDepth's plane sweep from known poses in one launch (pd_cost_volume; include/polardepth.h states the arithmetic).
+
+    cur [B,C,h,w] and lookup [B,F,C,h,w] features (channels-last storage is used as it is, anything else is copied),
+    poses [B,F,4,4] current -> lookup camera, K / inv_K [B,4,4] of the feature resolution, bins [D] fp32 on the device (read
+    by the kernel: overwriting them in place needs no new capture), valid [B,F] or None.  A frame is also skipped where its
+    pose sums to 0, the reference's "missing frame" rule.  No gradient: call it under no_grad or on detached features.
+
+    Returns (cost, confidence, argmin, lowest[, missing]): cost a logical [B,D,h,w] channels-last tensor -- ``out`` if given,
+    the sliced view [:, c0:c0+D] of a wider NHWC buffer as for conv2d_fwd(out=) -- confidence [B,h,w] fp32 0/1, argmin
+    [B,h,w] int32, lowest [B,h,w] fp32 = 1 / bins[argmin], missing [B,D,h,w] uint8 (channels-last) with want_missing."""
+    _require_cuda(cur, lookup, poses, K, inv_K, bins, valid, out)
+    if cur.dim() != 4 or lookup.dim() != 5 or lookup.shape[0] != cur.shape[0] or lookup.shape[2:] != cur.shape[1:]:
+        raise ValueError(f"cost_volume: cur [B,C,h,w] and lookup [B,F,C,h,w] expected, got {tuple(cur.shape)} / {tuple(lookup.shape)}")
+    B, C, h, w = cur.shape
+    F = lookup.shape[1]
+    D = bins.numel()
+    if C % 4 or C < 4:
+        raise ValueError(f"cost_volume: the channel count must be a multiple of 4, got {C}")
+    if not 1 <= D <= COST_VOLUME_MAX_BINS or bins.dim() != 1:
+        raise ValueError(f"cost_volume: 1 <= D <= {COST_VOLUME_MAX_BINS} depth bins in a 1-d tensor, got {tuple(bins.shape)}")
+    if F > REPROJ_MAX_FRAMES:
+        raise ValueError(f"cost_volume: at most {REPROJ_MAX_FRAMES} lookup frames, got {F}")
+    if tuple(poses.shape) != (B, F, 4, 4):
+        raise ValueError(f"cost_volume: poses must be [{B},{F},4,4], got {tuple(poses.shape)}")
+    for name, m in (("K", K), ("inv_K", inv_K)):
+        if tuple(m.shape) != (B, 4, 4):
+            raise ValueError(f"cost_volume: {name} must be [{B},4,4], got {tuple(m.shape)}")
+    if valid is not None and tuple(valid.shape) != (B, F):
+        raise ValueError(f"cost_volume: valid must be [{B},{F}], got {tuple(valid.shape)}")
+    f32 = lambda t: t.detach().float().contiguous()
+    cur = as_nhwc(cur.detach().float())
+    lookup = lookup.detach().float()
+    if lookup.stride() != (F * h * w * C, h * w * C, 1, w * C, C):
+        lookup = lookup.permute(0, 1, 3, 4, 2).contiguous().permute(0, 1, 4, 2, 3)
+    poses, K, inv_K, bins = f32(poses), f32(K), f32(inv_K), f32(bins)
+    dev = cur.device
+    v = None
+    if F:
+        v = (poses.reshape(B, F, 16).sum(-1) != 0)
+        if valid is not None:
+            v = v & (valid != 0)
+        v = v.float()
+    if out is None:
+        out = empty_nhwc(B, D, h, w, dev)
+    if tuple(out.shape) != (B, D, h, w) or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise ValueError(f"cost_volume: out must be a float32 [{B},{D},{h},{w}] view with channel stride 1")
+    ldc = out.stride(3)
+    if out.stride(2) != w * ldc or out.stride(0) != h * w * ldc or ldc < D:
+        raise ValueError(f"cost_volume: out is not a channel slice of an NHWC buffer (strides {out.stride()})")
+    confidence = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    argmin = torch.empty((B, h, w), dtype=torch.int32, device=dev)
+    lowest = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    missing = torch.empty((B, h, w, D), dtype=torch.uint8, device=dev) if want_missing else None
+    check(lib.pd_cost_volume(ptr(cur), ptr(lookup), ptr(poses), ptr(K), ptr(inv_K), ptr(bins), ptr(v), ptr(out), ldc,
+                             ptr(missing), ptr(confidence), ptr(argmin), ptr(lowest), B, F, h, w, C, D,
+                             int(bool(apply_confidence)), stream_ptr()), "pd_cost_volume")
+    res = (out, confidence, argmin, lowest)
+    return res + (missing.permute(0, 3, 1, 2),) if want_missing else res
+
+
 def depth_metrics(gt, pred, min_depth, max_depth, mask=None, mask_value=0):
     """Per-image depth metrics on the device: [N,8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count."""
     _require_cuda(gt, pred, mask)

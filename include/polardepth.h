@@ -684,6 +684,81 @@ int pd_cost_volume(const void* cur, const void* lookup, const void* T, const voi
                    const void* valid, void* cost, long ldc, void* missing, void* confidence, void* argmin, void* lowest,
                    int B, int F, int h, int w, int C, int D, int apply_confidence, void* stream);
 
+/* ------------------------------------------------------------------------- cost-volume student's step (csrc/student.hip)
+ * The reference's --train_student branch (trainer.py:567-664, 1112-1124, 1202-1236): the multi-frame network is trained
+ * with the reprojection loss where the cost volume can be trusted and pulled towards the teacher's depth where it cannot.
+ * Streaming kernels, four x-neighbouring pixels per thread (16-byte accesses); no atomics, no host synchronisation.
+ *
+ * pd_student_masks -- once per step, independent of the scale.
+ *   lowest, confidence [N,h,w] fp32       as pd_cost_volume writes them (confidence 0 / 1)
+ *   mono_depth [N,1,H,W] fp32             the teacher's scale-0 depth at full resolution, 16-byte aligned
+ *   aug [N] fp32 or NULL                  != 0: the item was augmented (static frame / zero pose), NULL: none was
+ *   motion_masking 0 / 1                  0 = --disable_motion_masking
+ * H == 4h and W == 4w are required.  F.interpolate(mode="nearest") reads source index floor(dst * (in / out)) with the
+ * scale in / out computed in fp32; for out = 4 * in that scale is exactly 0.25, dst * 0.25 is exact, and its floor is
+ * dst >> 2: the nearest source of pixel (y, x) is (y >> 2, x >> 2), bit for bit what the reference reads.
+ * Per pixel, all in fp32, every operation rounded once, a comparison with a NaN false:
+ *   l = lowest[n][y>>2][x>>2];  md = 1.0f / l;  t = mono_depth[n][0][y][x]
+ *   mm    = ((md - t) / t < 1) && ((t - md) / md < 1)                              compute_matching_mask
+ *   cmask = (confidence[n][y>>2][x>>2] != 0) && (!motion_masking || mm)
+ *   rmask = (!motion_masking || cmask) && !(aug && aug[n] != 0)
+ *   rmask     [N,H,W] uint8 out, 4-byte aligned: where the reprojection loss applies
+ *   cmask     [N,H,W] fp32 out (0 / 1) or NULL, 16-byte aligned: outputs["consistency_mask"]
+ *   lowest_up [N,H,W] fp32 out (= l) or NULL, 16-byte aligned: outputs["lowest_cost"]
+ *   minmax    [N,2] fp32 out: the minimum and the maximum of mono_depth over item n, both NaN if the item holds a NaN
+ *   partial_ws  N * pd_student_masks_rows(N, h, w) * 2 floats: one (min, max) pair per workgroup; a second launch with one
+ *               workgroup per item reduces them (minimum and maximum do not depend on the order).
+ * Limits: 0 <= N <= 65535 (N = 0 does nothing), h, w >= 1, h * w <= 2^26.
+ *
+ * pd_depth_bins_update -- update_adaptive_depth_bins (trainer.py:650-664) and compute_depth_bins (resnet_encoder.py:
+ * 406-420) in one workgroup, with no host round trip (the reference synchronises twice per step here).
+ *   minmax [N,2] fp32 (N >= 1)    tracker: 2 doubles on the device, 8-byte aligned, in and out: (min, max)
+ *   floor_depth = opt.min_depth   bins [D] fp32 out, 1 <= D <= 128   binning PD_BINS_LINEAR / PD_BINS_INVERSE
+ *   mn = (fp32 sum of minmax[n][0], n ascending) / (float)N;   mx likewise over minmax[n][1]
+ * then in fp64, every product and sum rounded on its own (no fused multiply-add):
+ *   lo = mn * 0.9;  mn64 = lo > floor_depth ? lo : floor_depth  (Python's max(floor, lo): a NaN gives floor);  mx64 = mx * 1.1
+ *   tracker[1] = tracker[1] * 0.99 + mx64 * 0.01;   tracker[0] = tracker[0] * 0.99 + mn64 * 0.01
+ * bins = polardepth.matching.depth_bins(tracker[0], tracker[1], D, binning), bit for bit.  numpy.linspace(start, stop, D) in
+ * fp64 is: delta = stop - start, step = delta / (D - 1), y[j] = j * step (or (j / (D - 1)) * delta when step == 0), then
+ * y[j] + start, and y[D-1] = stop; with D == 1, y[0] = 0 * delta + start.  linear: start, stop = tracker[0], tracker[1] and
+ * bins[i] = (float)y[i]; inverse: start, stop = 1 / tracker[1], 1 / tracker[0] and bins[i] = (float)(1 / y[D-1-i]).
+ * The step's own plane sweep has already read the old bins: the update is enqueued after the losses.
+ *
+ * pd_student_combine_fwd -- the is_multi branch of compute_losses (trainer.py:1202-1236) for one scale.
+ *   reproj    host array of F <= PD_REPROJ_MAX_FRAMES device pointers to [N,1,H,W] fp32 maps, valid [N,F] fp32 or NULL, avg:
+ *             as pd_reproj_combine_fwd; m = the minimum (first valid frame, a later one only when strictly smaller) or the
+ *             mean over the valid frames, 0 without one.  No identity maps: the reference overwrites its automask with ones.
+ *   rmask [N,H,W] uint8 (pd_student_masks)      multi_depth, mono_depth [N,1,H,W] fp32
+ *   r = (rmask != 0 && the item has a valid frame) ? 1.0f : 0.0f
+ *   sel  [N,H,W] uint8 out: the winning frame (0 with avg), 255 where r = 0
+ *   sums 3 doubles out: sum(m * r), sum(r), sum(|multi - mono| * (1 - r)); every term is formed in fp32 as written -- a
+ *        real product, so a NaN under the mask propagates as in the reference -- and added in fp64 in the fixed order of
+ *        pd_reproj_combine_fwd (the same two-stage reducer, csrc/frame_reduce.hpp; a thread adds its four pixels in x order)
+ *   loss 2 floats out: sums[0] / (sums[1] + 1e-7) and sums[2] / (N * H * W)        (reproj_loss, consistency_loss)
+ *   partial_ws pd_student_combine_rows(N,H,W) * 3 doubles, 8-byte aligned.
+ * pd_student_combine_bwd -- gloss: 2 floats on the device.
+ *   greproj (F device pointers, [N,1,H,W] fp32 out) as pd_reproj_combine_bwd defines it from sel, sums[1] and gloss[0]
+ *   gmulti [N,1,H,W] fp32 out = ((float)(gloss[1] / (N * H * W)) * sign(multi - mono)) * (1 - r)
+ *   sign(0) = 0 and sign(NaN) = 0: torch.sign returns 0 for a NaN on the CPU, and abs' backward is grad * sign.
+ *   No gradient reaches mono_depth or the masks.
+ * Both need H % 4 == 0 and W % 4 == 0 (what pd_student_masks produces), the fp32 maps 16-byte and the uint8 maps 4-byte
+ * aligned, H * W <= 2^30; N = 0 does nothing.  Bit-reproducible. */
+#define PD_BINS_LINEAR 0
+#define PD_BINS_INVERSE 1
+int pd_student_masks_rows(int N, int h, int w);
+int pd_student_masks(const void* lowest, const void* confidence, const void* mono_depth, const void* aug, int motion_masking,
+                     void* rmask, void* cmask, void* lowest_up, void* minmax, void* partial_ws, int N, int h, int w, int H,
+                     int W, void* stream);
+int pd_depth_bins_update(const void* minmax, int N, void* tracker, double floor_depth, int D, int binning, void* bins,
+                         void* stream);
+int pd_student_combine_rows(int N, int H, int W);
+int pd_student_combine_fwd(const void* const* reproj, int F, const void* valid, const void* rmask, const void* multi_depth,
+                           const void* mono_depth, void* sel, void* partial_ws, void* sums, void* loss, int N, int H, int W,
+                           int avg, void* stream);
+int pd_student_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid, const void* multi_depth,
+                           const void* mono_depth, void* const* greproj, void* gmulti, int F, int N, int H, int W, int avg,
+                           void* stream);
+
 /* compute_depth_errors (layers.py:539-557) per image on the device: metrics [N][8] = abs_rel, sq_rel, rmse,
  * rmse_log, a1, a2, a3, pixel count over min < gt < max (and mask == mask_value when mask != NULL, the
  * per-material selection of trainer.py:1385-1411); pred is clamped to [min, max] (trainer.py:1422-1423).

@@ -15,11 +15,12 @@
 // Depth reads and warped / coords / gdepth writes are coalesced (thread = pixel, x fastest); the four taps of a pixel
 // are gathers whose locality is that of the warp itself.  No atomics: an output pixel depends on its own depth alone.
 #include "pd_common.h"
+#include "frame_reduce.hpp"
 
 namespace {
 
-constexpr int RT = 256;
-constexpr int RP_MAX_FRAMES = 8;   // = PD_REPROJ_MAX_FRAMES
+constexpr int RT = pd_frames::RT;
+constexpr int RP_MAX_FRAMES = pd_frames::MAX_FRAMES;   // = PD_REPROJ_MAX_FRAMES
 
 // ------------------------------------------------------------------ camera of one batch item, in LDS
 struct CamLds {
@@ -156,36 +157,10 @@ __global__ __launch_bounds__(RT) void depth_to_updisp_bwd_kernel(const float* __
 }
 
 // ------------------------------------------------------------------ minimum / mean over frames, automask, masked sums
-struct FrameArgs {
-    const float* reproj[RP_MAX_FRAMES];
-    const float* identity[RP_MAX_FRAMES];
-    float* greproj[RP_MAX_FRAMES];
-};
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// one value over the valid frames of a pixel: the minimum and its frame (the first valid frame is taken, a later one only
-// when it is strictly smaller: the earlier frame wins a tie), or the mean (sum in frame order / number of valid frames,
-// frame 0 reported)
-__device__ __forceinline__ float over_frames(const float* const* maps, const float* __restrict__ vrow, int F, long i, int avg,
-                                             int& nvalid, int& arg) {
-    float m = 0.f;
-    nvalid = 0;
-    arg = 255;
-    for (int f = 0; f < F; ++f) {
-        if (vrow && vrow[f] == 0.f) continue;
-        const float r = maps[f][i];
-        ++nvalid;
-        if (avg) m += r;
-        else if (arg == 255 || r < m) { m = r; arg = f; }
-    }
-    if (avg && nvalid) { m = m / (float)nvalid; arg = 0; }
-    return m;
-}
+// FrameArgs, over_frames and the two-stage fp64 reducer live in frame_reduce.hpp (csrc/student.hip shares them)
+using pd_frames::FrameArgs;
+using pd_frames::over_frames;
+using pd_frames::rgrid;
 
 __global__ __launch_bounds__(RT) void combine_fwd_kernel(const FrameArgs a, int F, int has_identity,
                                                          const float* __restrict__ noise, const float* __restrict__ valid,
@@ -208,33 +183,20 @@ __global__ __launch_bounds__(RT) void combine_fwd_kernel(const FrameArgs a, int 
         sel[i] = keep ? (unsigned char)arg : (unsigned char)255;
         if (keep) { acc_s += (double)m; acc_c += 1.0; }
     }
-    acc_s = wave_sum_d(acc_s);
-    acc_c = wave_sum_d(acc_c);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sm[wave * 2] = acc_s; sm[wave * 2 + 1] = acc_c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x * 2] = ((sm[0] + sm[2]) + sm[4]) + sm[6];
-        partial[blockIdx.x * 2 + 1] = ((sm[1] + sm[3]) + sm[5]) + sm[7];
-    }
+    double acc[2] = {acc_s, acc_c};
+    pd_frames::block_rows<2>(acc, sm, partial);
 }
 
-// one workgroup: thread t sums rows t, t + 256, ... then a tree over LDS (the order of loss_finalize_kernel)
+// one workgroup sums the rows (the order of loss_finalize_kernel)
 __global__ __launch_bounds__(256) void combine_finalize_kernel(const double* __restrict__ partial, int rows,
                                                                double* __restrict__ sums, float* __restrict__ loss) {
-    __shared__ double s0[256], s1[256];
-    double a = 0.0, b = 0.0;
-    for (int r = threadIdx.x; r < rows; r += 256) { a += partial[2 * r]; b += partial[2 * r + 1]; }
-    s0[threadIdx.x] = a; s1[threadIdx.x] = b;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) { s0[threadIdx.x] += s0[threadIdx.x + k]; s1[threadIdx.x] += s1[threadIdx.x + k]; }
-        __syncthreads();
-    }
+    __shared__ double sm[2 * 256];
+    double s[2];
+    pd_frames::finalize_rows<2>(partial, rows, sm, s);
     if (threadIdx.x == 0) {
-        sums[0] = s0[0];
-        sums[1] = s1[0];
-        loss[0] = (float)(s0[0] / (s1[0] + 1e-7));
+        sums[0] = s[0];
+        sums[1] = s[1];
+        loss[0] = (float)(s[0] / (s[1] + 1e-7));
     }
 }
 
@@ -255,13 +217,6 @@ __global__ __launch_bounds__(RT) void combine_bwd_kernel(const FrameArgs a, int 
         const float ga = (s != 255 && nv) ? g / (float)nv : 0.f;
         for (int f = 0; f < F; ++f) a.greproj[f][i] = (vrow && vrow[f] == 0.f) ? 0.f : ga;
     }
-}
-
-inline unsigned rgrid(long n) {
-    long b = (n + RT - 1) / RT;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (unsigned)b;
 }
 
 // blocks along x for a per-item grid (blockIdx.y = item): about 4096 workgroups in all, the rest by grid stride

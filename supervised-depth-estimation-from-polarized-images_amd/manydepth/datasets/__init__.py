@@ -49,6 +49,9 @@ and of the neighbour (hammer_dataset.py:104-132); and ``("frame_valid", i)`` flo
 the identity pose where the neighbour or one of the pose files does not exist (the reference substitutes a dummy picture,
 indoor_dataset.py:361-366).  With ``frame_idxs == [0]`` an item is, key for key and bit for bit, what it was without this.
 ``raw_color`` applies to frame 0 only; ``pol_cdofp`` has no ``rgb/`` folder and refuses neighbours.
+``lookup_aug=True`` (opt-in; the cost-volume student's lookup frames, trainer.py:491): every neighbour also arrives as
+``("color_aug", i, 0)``, the resized frame under the item's own ColorJitter draw (the frame itself when the item is not
+jittered, when it is blank or when it is missing); synthetic items get the same keys.  Without the switch nothing changes.
 """
 import glob
 import os
@@ -92,8 +95,11 @@ class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
                  depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None,
-                 pol_dofp=None, pol_cdofp=None):
+                 pol_dofp=None, pol_cdofp=None, lookup_aug=False):
         super().__init__()
+        # lookup_aug: the neighbouring frames also arrive as ("color_aug", i, 0), jittered with the item's own ColorJitter
+        # draw -- the lookup frames of the cost-volume student (trainer.py:491).  Off: an item is what it was, bit for bit.
+        self.lookup_aug = bool(lookup_aug)
         # raw_pol: hand the four polarizer images over at their native size; the Trainer resizes them on the device
         # with the Pillow-exact LANCZOS kernels before K1.  Default: $PD_DEVICE_RESIZE == "1".
         self.raw_pol = (os.environ.get("PD_DEVICE_RESIZE") == "1") if raw_pol is None else bool(raw_pol)
@@ -225,7 +231,7 @@ class HAMMER_Dataset(Dataset):
         inputs["stereo_T"] = torch.eye(4)
         inputs["stereo_T"][0, 3] = -0.0498921
         for i in self.neighbours:                 # indoor_dataset.py:311-366: a missing neighbour is a dummy, not an error
-            inputs.update(self._neighbour(folder, idx, i))
+            inputs.update(self._neighbour(folder, idx, i, jitter))
         return inputs
 
     @staticmethod
@@ -238,10 +244,11 @@ class HAMMER_Dataset(Dataset):
             T_s = np.array(f.read().split(), dtype="float").reshape(4, 4)
         return np.linalg.inv(np.linalg.inv(T_c) @ T_s)
 
-    def _neighbour(self, folder, idx, i):
+    def _neighbour(self, folder, idx, i, jitter=None):
         """("color", i, 0), ("poses", i), ("frame_valid", i) of the frame idx + i * offset: the colour frame resized like
         frame 0's first scale, the relative pose as float32, 1.0; zeros, the identity and 0.0 when the frame or one of the two
-        pose files does not exist."""
+        pose files does not exist.  With ``lookup_aug`` also ("color_aug", i, 0): the resized frame under ``jitter``, the
+        item's ColorJitter draw (None, a blank or a missing frame: the colour frame itself), as frame 0's "color_aug"."""
         from PIL import Image
         H, W = self.height, self.width
         other = idx + i * self.offset
@@ -253,8 +260,14 @@ class HAMMER_Dataset(Dataset):
             pose = torch.from_numpy(self.relative_pose(pc, ps).astype(np.float32))
             ok = 1.0
         else:
-            color, pose, ok = torch.zeros((3, H, W), dtype=torch.float32), torch.eye(4), 0.0
-        return {("color", i, 0): color, ("poses", i): pose, ("frame_valid", i): torch.tensor(ok, dtype=torch.float32)}
+            color, pose, ok, im = torch.zeros((3, H, W), dtype=torch.float32), torch.eye(4), 0.0, None
+        out = {("color", i, 0): color, ("poses", i): pose, ("frame_valid", i): torch.tensor(ok, dtype=torch.float32)}
+        if self.lookup_aug:
+            out[("color_aug", i, 0)] = color
+            if jitter is not None and im is not None and color.sum() != 0:
+                aug = apply_color_jitter(im, jitter)
+                out[("color_aug", i, 0)] = torch.from_numpy(np.asarray(aug, dtype=np.float32).transpose(2, 0, 1) / 255.0)
+        return out
 
     @staticmethod
     def _dofp_frame(path, option="pol_dofp"):
@@ -335,6 +348,8 @@ class HAMMER_Dataset(Dataset):
             inputs[("color", i, 0)] = torch.from_numpy(col.astype(np.float32))
             inputs[("poses", i)] = torch.from_numpy(T.astype(np.float32))
             inputs[("frame_valid", i)] = torch.tensor(1.0, dtype=torch.float32)
+            if self.lookup_aug:                   # synthetic items are not jittered: frame 0's "color_aug" is its "color" too
+                inputs[("color_aug", i, 0)] = inputs[("color", i, 0)]
         return inputs
 
 

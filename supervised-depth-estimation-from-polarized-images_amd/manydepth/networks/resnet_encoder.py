@@ -230,7 +230,9 @@ class ResnetEncoderMatching(nn.Module):
         D = self.num_depth_bins
         buf = ops.empty_nhwc(B, C + D, h, w, current_feats.device)
         with torch.no_grad():
-            if self.adaptive_bins:
+            # a caller that keeps ``depth_bins`` current on the device itself (polardepth.student.DepthBinTracker) passes
+            # no range: the host-side recomputation is for callers that hold the range as Python numbers
+            if self.adaptive_bins and min_depth_bin is not None:
                 self.compute_depth_bins(min_depth_bin, max_depth_bin)
             batch_size, num_frames, chns, height, width = lookup_images.shape
             lookup_feats = self.feature_extraction(lookup_images.reshape(batch_size * num_frames, chns, height, width))

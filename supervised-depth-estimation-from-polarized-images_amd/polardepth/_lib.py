@@ -137,6 +137,12 @@ SIGNATURES = {
     "pd_reproj_combine_fwd": (_i, [_vpp, _vpp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pd_reproj_combine_bwd": (_i, [_vp, _vp, _vp, _vp, _vpp, _i, _i, _i, _i, _i, _vp]),
     "pd_cost_volume": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "pd_student_masks_rows": (_i, [_i, _i, _i]),
+    "pd_student_masks": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "pd_depth_bins_update": (_i, [_vp, _i, _vp, _dbl, _i, _i, _vp, _vp]),
+    "pd_student_combine_rows": (_i, [_i, _i, _i]),
+    "pd_student_combine_fwd": (_i, [_vpp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "pd_student_combine_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vpp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pd_normals_stats_workspace": (_sz, [_i, _i, _i, _i]),
     "pd_normals_stats": (_i, [_vp, _l, _vp, _vp, _vp, _ip, _i, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
     "pd_backproject": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),

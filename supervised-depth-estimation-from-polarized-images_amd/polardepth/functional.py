@@ -1209,6 +1209,41 @@ def photometric_loss(cfg, disps, depths, target, sources, K, inv_K, poses, valid
     return (losses, sels) if details else losses
 
 
+def student_loss(cfg, disps, depths, mono_depths, target, sources, K, inv_K, poses, valid, rmask, no_ssim=False, avg=False,
+                 details=False):
+    """The ``is_multi`` branch of the reference's compute_losses (trainer.py:1202-1236) for the cost-volume student, shaped
+    like ``photometric_loss``: per scale, every source frame is warped through the student's full-resolution depth map
+    (``DispDepthFn`` -> ``ops.view_synthesis``), compared with the target (``ops.reprojection_loss``) and reduced by
+    ``ops.student_combine``: the minimum (``avg``: mean) over the frames weighted by ``rmask`` [N,H,W] uint8 of
+    ``ops.student_masks``, and |student depth - teacher depth| where the mask is 0.  Returns one (reproj, consistency) pair
+    per scale; ``details``: also the per-scale ``sel`` maps and warped frames (the reference's ("color", frame, scale)).
+
+    mono_depths  the teacher's full-resolution depth maps [N,1,H,W], one per scale: data, no gradient reaches them
+    The other arguments are those of ``photometric_loss``.
+
+    No identity maps are evaluated and no tie-breaking noise is drawn: the reference computes both in this branch and then
+    overwrites the automask with ones (trainer.py:1203), so neither reaches a value or a gradient."""
+    sources, poses = list(sources), list(poses)
+    if len(sources) != len(poses) or not sources:
+        raise ValueError("student_loss: one pose per source frame, at least one frame")
+    if len(mono_depths) != len(depths):
+        raise ValueError("student_loss: one teacher depth map per scale")
+    target = target.float().contiguous()
+    sources = [s.float().contiguous() for s in sources]
+    losses, sels, warped = [], [], []
+    for i, depth in enumerate(depths):
+        d = depth
+        if disps is not None and disps[i] is not None:
+            d = DispDepthFn.apply(disps[i], depth, cfg.min_depth, cfg.max_depth)
+        views = [ops.view_synthesis(d, s, K, inv_K, T)[0] for s, T in zip(sources, poses)]
+        maps = [ops.reprojection_loss(v, target, no_ssim) for v in views]
+        reproj, consistency, sel, _ = ops.student_combine(maps, rmask, d, mono_depths[i], valid, avg, details=True)
+        losses.append((reproj, consistency))
+        sels.append(sel)
+        warped.append(views)
+    return (losses, sels, warped) if details else losses
+
+
 # ------------------------------------------------------------------ layers.get_smooth_loss as a function of its own
 class SmoothLossFn(torch.autograd.Function):
     """layers.py:452-465 on the K5 kernels: mean |dx disp| e^{-|dx I|} + mean |dy disp| e^{-|dy I|} of the disparity AS GIVEN

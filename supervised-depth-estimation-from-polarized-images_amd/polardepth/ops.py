@@ -545,6 +545,126 @@ def cost_volume(cur, lookup, poses, K, inv_K, bins, valid=None, out=None, apply_
     return res + (missing.permute(0, 3, 1, 2),) if want_missing else res
 
 
+# ------------------------------------------------------------------ cost-volume student's step (csrc/student.hip)
+BINS_LINEAR, BINS_INVERSE = 0, 1          # PD_BINS_LINEAR / PD_BINS_INVERSE
+_BINNING = {"linear": BINS_LINEAR, "inverse": BINS_INVERSE}
+
+
+def _f32c16(t):
+    """float32, contiguous and 16-byte aligned (a fresh allocation is; an odd view is copied)."""
+    t = t.float().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def student_masks(lowest, confidence, mono_depth, aug=None, motion_masking=True, want_maps=True):
+    """The consistency masks of the reference's --train_student branch in one pass (pd_student_masks; include/polardepth.h
+    states the arithmetic): ``lowest`` / ``confidence`` [N,h,w] as ops.cost_volume returns them, ``mono_depth`` [N,1,4h,4w]
+    the teacher's full-resolution depth, ``aug`` [N] (non-zero = augmented item) or None.  Returns (rmask [N,H,W] uint8,
+    cmask [N,H,W] fp32, lowest_up [N,H,W] fp32, minmax [N,2] fp32); cmask and lowest_up are None without ``want_maps``.
+    No gradient."""
+    _require_cuda(lowest, confidence, mono_depth, aug)
+    if lowest.dim() != 3 or confidence.shape != lowest.shape:
+        raise ValueError(f"student_masks: lowest and confidence must be [N,h,w], got {tuple(lowest.shape)} / {tuple(confidence.shape)}")
+    N, h, w = lowest.shape
+    if tuple(mono_depth.shape) != (N, 1, 4 * h, 4 * w):
+        raise ValueError(f"student_masks: mono_depth must be [{N},1,{4 * h},{4 * w}], got {tuple(mono_depth.shape)}")
+    if aug is not None and aug.numel() != N:
+        raise ValueError(f"student_masks: aug must hold {N} values, got {tuple(aug.shape)}")
+    f32 = lambda t: t.detach().float().contiguous()
+    lowest, confidence, mono = f32(lowest), f32(confidence), _f32c16(mono_depth.detach())
+    aug = None if aug is None else f32(aug).reshape(N)
+    dev = lowest.device
+    H, W = 4 * h, 4 * w
+    rmask = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    cmask = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_maps else None
+    lowest_up = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_maps else None
+    minmax = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    part = torch.empty((max(N, 1) * lib.pd_student_masks_rows(N, h, w), 2), dtype=torch.float32, device=dev)
+    check(lib.pd_student_masks(ptr(lowest), ptr(confidence), ptr(mono), ptr(aug), int(bool(motion_masking)), ptr(rmask),
+                               ptr(cmask), ptr(lowest_up), ptr(minmax), ptr(part), N, h, w, H, W, stream_ptr()),
+          "pd_student_masks")
+    return rmask, cmask, lowest_up, minmax
+
+
+def depth_bins_update(minmax, tracker, floor_depth, bins, binning="linear"):
+    """update_adaptive_depth_bins + compute_depth_bins on the device, in place (pd_depth_bins_update): ``minmax`` [N,2] fp32
+    from student_masks, ``tracker`` 2 doubles (min, max), ``bins`` [D] fp32 -- both are overwritten where they are, so a
+    cost volume that reads ``bins`` needs nothing else.  No host synchronisation."""
+    _require_cuda(minmax, tracker, bins)
+    if binning not in _BINNING:
+        raise NotImplementedError(f"depth_binning {binning!r}: linear or inverse")
+    if minmax.dim() != 2 or minmax.shape[1] != 2 or minmax.dtype != torch.float32 or not minmax.is_contiguous():
+        raise ValueError(f"depth_bins_update: minmax must be a contiguous float32 [N,2], got {tuple(minmax.shape)}")
+    if tracker.dtype != torch.float64 or tracker.numel() != 2 or not tracker.is_contiguous():
+        raise ValueError("depth_bins_update: tracker must be 2 contiguous doubles (min, max)")
+    if bins.dtype != torch.float32 or bins.dim() != 1 or not bins.is_contiguous():
+        raise ValueError("depth_bins_update: bins must be a contiguous 1-d float32 tensor")
+    check(lib.pd_depth_bins_update(ptr(minmax), minmax.shape[0], ptr(tracker), float(floor_depth), bins.numel(),
+                                   _BINNING[binning], ptr(bins), stream_ptr()), "pd_depth_bins_update")
+
+
+class _StudentCombineFn(torch.autograd.Function):
+    """trainer.py:1202-1236 for one scale (pd_student_combine_fwd / _bwd): returns (loss [2], sel, sums); differentiable in
+    the F reproj maps and in the multi-frame depth."""
+
+    @staticmethod
+    def forward(ctx, valid, rmask, mono, avg, multi, *reproj):
+        F = len(reproj)
+        N, _, H, W = reproj[0].shape
+        dev = reproj[0].device
+        sel = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+        part = torch.empty((lib.pd_student_combine_rows(N, H, W), 3), dtype=torch.float64, device=dev)
+        sums = torch.empty(3, dtype=torch.float64, device=dev)
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        check(lib.pd_student_combine_fwd(_dev_ptrs(reproj), F, ptr(valid), ptr(rmask), ptr(multi), ptr(mono), ptr(sel), ptr(part),
+                                         ptr(sums), ptr(loss), N, H, W, int(avg), stream_ptr()), "pd_student_combine_fwd")
+        ctx.geom = (F, N, H, W, int(avg))
+        ctx.save_for_backward(sel, sums, valid, multi, mono)
+        ctx.mark_non_differentiable(sel, sums)
+        return loss, sel, sums
+
+    @staticmethod
+    def backward(ctx, gloss, _gsel, _gsums):
+        sel, sums, valid, multi, mono = ctx.saved_tensors
+        F, N, H, W, avg = ctx.geom
+        grads = [torch.empty((N, 1, H, W), dtype=torch.float32, device=sel.device) for _ in range(F)]
+        gmulti = torch.empty((N, 1, H, W), dtype=torch.float32, device=sel.device)
+        check(lib.pd_student_combine_bwd(ptr(gloss.float().reshape(2).contiguous()), ptr(sel), ptr(sums), ptr(valid), ptr(multi),
+                                         ptr(mono), _dev_ptrs(grads), ptr(gmulti), F, N, H, W, avg, stream_ptr()),
+              "pd_student_combine_bwd")
+        return (None, None, None, None, gmulti, *grads)
+
+
+def student_combine(reproj, rmask, multi_depth, mono_depth, valid=None, avg=False, details=False):
+    """The is_multi branch of the reference's compute_losses for one scale: ``reproj`` a list of F [N,1,H,W] maps of
+    ``reprojection_loss``, ``rmask`` [N,H,W] uint8 from student_masks, ``multi_depth`` / ``mono_depth`` [N,1,H,W], ``valid``
+    [N,F] or None.  Returns (reproj_loss, consistency_loss): sum(min * rmask) / (sum(rmask) + 1e-7) and
+    mean(|multi - mono| * (1 - rmask)), summed in fp64 in a fixed order; ``details``: also ``sel`` [N,H,W] uint8 (winning
+    frame, 255 = masked) and ``sums`` (3 doubles).  Differentiable in the reproj maps and in multi_depth; mono_depth and the
+    mask are data."""
+    reproj = list(reproj)
+    if not 1 <= len(reproj) <= REPROJ_MAX_FRAMES:
+        raise ValueError(f"student_combine: 1 .. {REPROJ_MAX_FRAMES} frames, got {len(reproj)}")
+    _require_cuda(*reproj, rmask, multi_depth, mono_depth, valid)
+    shape = tuple(reproj[0].shape)
+    if len(shape) != 4 or shape[1] != 1 or shape[2] % 4 or shape[3] % 4:
+        raise ValueError(f"student_combine: maps must be [N,1,H,W] with H and W multiples of 4, got {shape}")
+    for t in (*reproj, multi_depth, mono_depth):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"student_combine: every map must be {shape}, got {tuple(t.shape)}")
+    if tuple(rmask.shape) != (shape[0], shape[2], shape[3]) or rmask.dtype != torch.uint8:
+        raise ValueError(f"student_combine: rmask must be uint8 [{shape[0]},{shape[2]},{shape[3]}], got {rmask.dtype} {tuple(rmask.shape)}")
+    if valid is not None and tuple(valid.shape) != (shape[0], len(reproj)):
+        raise ValueError(f"student_combine: valid must be [{shape[0]},{len(reproj)}], got {tuple(valid.shape)}")
+    rmask = rmask.contiguous()
+    if rmask.data_ptr() % 4:
+        rmask = rmask.clone()
+    loss, sel, sums = _StudentCombineFn.apply(None if valid is None else valid.detach().float().contiguous(), rmask,
+                                              _f32c16(mono_depth.detach()), bool(avg), _f32c16(multi_depth),
+                                              *[_f32c16(t) for t in reproj])
+    return (loss[0], loss[1], sel, sums) if details else (loss[0], loss[1])
+
+
 def depth_metrics(gt, pred, min_depth, max_depth, mask=None, mask_value=0):
     """Per-image depth metrics on the device: [N,8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count."""
     _require_cuda(gt, pred, mask)

@@ -592,13 +592,32 @@ int pd_ssim_bwd(const void* x, const void* y, const void* gout, void* coef_ws, v
  * x1 = min(x0 + 1, W-1), wx1 = uc - x0, wx0 = 1 - wx1 (y likewise);
  *   warped = ((src[y0][x0] (wx0 wy0) + src[y0][x1] (wx1 wy0)) + src[y1][x0] (wx0 wy1)) + src[y1][x1] (wx1 wy1).
  *
- * pd_view_synth_bwd -- the gradient w.r.t. depth alone (the sources are data, and so is T under --pose_input): each output
- * pixel depends on its own depth only, hence no scatter and no atomics.
+ * pd_view_synth_bwd -- the gradient w.r.t. depth alone (the sources are data, and so is T under --pose_input; a PREDICTED
+ * pose takes pd_view_synth_bwd_pose below): each output pixel depends on its own depth only, hence no scatter and no atomics.
  *   gdepth [N,1,H,W] (=, or += when accumulate != 0) = sum_c gwarped_c (d warped_c / du * du/ddepth + d warped_c / dv * dv/ddepth)
  * d warped / d(u, v) from the four taps with the weights of `coords`; it is exactly zero on an axis whose coordinate is
  * <= 0, >= size-1 or not finite (PyTorch's border rule).  With h = depth * q + b, q = P[:, :3] r:
  *   du/ddepth = (q[0] - u q[2]) / (h[2] + 1e-7), dv/ddepth = (q[1] - v q[2]) / (h[2] + 1e-7), in fp64 as above.
  * Limits of both: 0 <= N <= 65535 (N = 0 does nothing), C, H, W > 0, H * W <= 2^30.
+ *
+ * pd_view_synth_bwd_pose -- pd_view_synth_bwd and the gradient w.r.t. the pose T in one pass over the same taps (gwarped and
+ * src are read once).  gdepth may be NULL (skipped); where given it holds the bits pd_view_synth_bwd writes.
+ *   partial_ws  N * pd_view_synth_pose_rows(H, W) * 12 doubles, 8-byte aligned (pd_view_synth_pose_rows is a pure function
+ *               of H and W: min(ceil(H W / 256), 512))
+ *   gP          [N,12] doubles out, or NULL: the gradient w.r.t. P = (K T)[:3,:], row-major 3x4
+ *   gT          [N,4,4] fp32 out, written with "="
+ * Per pixel with gu = sum_c gwarped_c d warped_c / du, gv likewise (fp32, the expressions of pd_view_synth_bwd), and u, v,
+ * hz = h[2] + 1e-7, p = depth * r in fp64 as in pd_view_synth_fwd; free_x / free_y = the axis is neither clamped nor
+ * non-finite.  The rest in fp64, no fused multiply-add:
+ *   a0 = free_x ? gu / hz : 0        a1 = free_y ? gv / hz : 0
+ *   a2 = -((free_x ? a0 u : 0) + (free_y ? a1 v : 0))
+ *   gP[i][j] += a_i * (p[0], p[1], p[2], 1)[j]        a row whose axis is not free receives no term (never 0 * inf), and a
+ *                                                     pixel with neither axis free contributes nothing at all
+ * The 12 sums per item are accumulated in the order of pd_reproj_combine_fwd: per thread over its grid-stride pixels, per
+ * wavefront by shuffles, per workgroup, one row of partial_ws per workgroup; then one workgroup per item sums that item's
+ * rows and forms, in fp64 rounded once,
+ *   gT[k][j] = (K[0][k] gP[0][j] + K[1][k] gP[1][j]) + K[2][k] gP[2][j]        (k, j < 4).
+ * Bit-reproducible, no atomics, no host synchronisation.  Limits as pd_view_synth_bwd.
  *
  * pd_depth_to_updisp_bwd -- gup[i] = -gdepth[i] * depth[i]^2 * (1/min_depth - 1/max_depth): the gradient of
  * depth = 1 / (min_disp + (max_disp - min_disp) * up) w.r.t. the upsampled disparity `up` (layers.py:62-71), n elements;
@@ -609,6 +628,10 @@ int pd_view_synth_fwd(const void* depth, const void* src, const void* K, const v
 int pd_view_synth_bwd(const void* gwarped, const void* src, const void* coords, const void* depth, const void* K,
                       const void* inv_K, const void* T, void* gdepth, int N, int C, int H, int W, int accumulate,
                       void* stream);
+int pd_view_synth_pose_rows(int H, int W);
+int pd_view_synth_bwd_pose(const void* gwarped, const void* src, const void* coords, const void* depth, const void* K,
+                           const void* inv_K, const void* T, void* gdepth, void* partial_ws, void* gP, void* gT, int N, int C,
+                           int H, int W, int accumulate, void* stream);
 int pd_depth_to_updisp_bwd(const void* gdepth, const void* depth, void* gup, long n, float min_depth, float max_depth,
                            void* stream);
 /* pd_reproj_combine_fwd -- trainer.py:1163-1215 over F <= PD_REPROJ_MAX_FRAMES neighbouring frames.
@@ -634,6 +657,52 @@ int pd_reproj_combine_fwd(const void* const* reproj, const void* const* identity
                           int avg, void* stream);
 int pd_reproj_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid, void* const* greproj,
                           int F, int N, int H, int W, int avg, void* stream);
+
+/* ------------------------------------------------------------------------- pose network tail (csrc/pose.hip)
+ * The monodepth2 / ManyDepth setting: a pose network predicts the relative pose of two frames, and the photometric term
+ * trains depth and pose together (trainer.py:222-236, 669-707; networks/pose_decoder.py; layers.py:74-149).
+ *
+ * pd_pose_matrix_fwd -- transformation_from_parameters(axisangle [N,3], translation [N,3], invert) -> T [N,4,4], fp32 in
+ * and out.  Evaluated in fp64 from the fp32 inputs in the reference's order, each entry rounded once:
+ *   angle = sqrt((a0 a0 + a1 a1) + a2 a2);  (x, y, z) = a / (angle + 1e-7);  ca = cos angle, sa = sin angle, C = 1 - ca
+ *   xs = x sa, ys, zs;  xC = x C, yC, zC;  xyC = x yC, yzC = y zC, zxC = z xC
+ *   R = [x xC + ca, xyC - zs, zxC + ys;  xyC + zs, y yC + ca, yzC - xs;  zxC - ys, yzC + xs, z zC + ca]
+ *   invert == 0:  T = Trans(t) R = [R | t]
+ *   invert == 1:  T = R^T Trans(-t) = [R^T | c],  c[i] = (R[0][i] (-t0) + R[1][i] (-t1)) + R[2][i] (-t2)
+ *   last row (0, 0, 0, 1).
+ * pd_pose_matrix_bwd -- gaxisangle, gtranslation [N,3] fp32 out ("=") from gT [N,4,4] fp32 (its last row is ignored), in
+ * fp64, rounded once.  At angle == 0 the derivative of the norm is taken as 0 (PyTorch's rule), and the axisangle gradient
+ * is then exactly 0.  One thread per item; N >= 0 (N = 0 does nothing).
+ *
+ * pd_pose_head_fwd -- the tail of PoseDecoder.forward from the input of ("pose", 2) on, and the two matrices of slot 0.
+ *   x [N,h,w,Cin] NHWC fp32      w [Co,Cin], b [Co] fp32: the 1x1 convolution, Co = 6 nf
+ *   axisangle, translation [N,nf,1,3] fp32 out      T, T_inv [N,4,4] fp32 out      mean [N,Cin] doubles out (8-byte aligned)
+ * Per item, one workgroup of 256 threads:
+ *   mean[c] = (sum over the pixels, ascending, of x[p][c] in fp64) / (h w)        (the mean commutes with a 1x1 convolution)
+ *   o[k]    = fp32(0.01 * (b[k] + dot_k)),  dot_k = sum_c w[k][c] mean[c] in fp64: lane l of a wavefront sums
+ *             c = l, l + 64, ... ascending, the 64 lanes are added by xor shuffles (32, 16, ... 1)
+ *   axisangle[f] = o[6f .. 6f+2], translation[f] = o[6f+3 .. 6f+5]
+ *   T = pd_pose_matrix_fwd(axisangle[0], translation[0], invert), T_inv the same with invert flipped (cam_T_cam and
+ *   cam_T_cam_inv of trainer.py:694-707).
+ * pd_pose_head_bwd -- gT, gT_inv [N,4,4], gaxisangle, gtranslation [N,nf,1,3] fp32: any may be NULL (= zero).
+ *   gx [N,h,w,Cin] fp32 out ("=")      gw [Co,Cin], gb [Co] fp32, "=" or, with accumulate != 0, "+="
+ *   gpre_ws  N * Co doubles of workspace, 8-byte aligned
+ * In fp64: go = (gaxisangle | gtranslation) + for slot 0 the two pd_pose_matrix_bwd results; gpre = 0.01 go;
+ * gx[p][c] = (sum_k w[k][c] gpre[k], k ascending) / (h w); gw[k][c] = sum_n gpre[n][k] mean[n][c] and gb[k] = sum_n
+ * gpre[n][k], items ascending, one thread per element (a second launch).  Rows of gw / gb for slots >= 1 receive exactly 0
+ * unless gaxisangle / gtranslation are given.  No atomics, no host synchronisation.
+ * Limits of both: 0 <= N <= 65535 (N = 0 does nothing), h, w > 0, h w <= 2^20, Cin a multiple of 64 and <= 1024, Co a
+ * multiple of 6 and <= 384, invert 0 or 1.  Meant for the decoder's small plane (1/32 of the image: a few hundred pixels):
+ * one thread per channel walks the pixels of its item serially, forward for the mean (the stated ascending order) and
+ * backward for gx, so the time grows with h w on Cin threads per item; a large plane is legal but slow. */
+int pd_pose_matrix_fwd(const void* axisangle, const void* translation, void* T, int N, int invert, void* stream);
+int pd_pose_matrix_bwd(const void* gT, const void* axisangle, const void* translation, void* gaxisangle, void* gtranslation,
+                       int N, int invert, void* stream);
+int pd_pose_head_fwd(const void* x, const void* w, const void* b, void* axisangle, void* translation, void* T, void* T_inv,
+                     void* mean, int N, int h, int wd, int Cin, int Co, int invert, void* stream);
+int pd_pose_head_bwd(const void* gT, const void* gT_inv, const void* gaxisangle, const void* gtranslation,
+                     const void* axisangle, const void* translation, const void* w, const void* mean, void* gx, void* gw,
+                     void* gb, void* gpre_ws, int N, int h, int wd, int Cin, int Co, int invert, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------- multi-frame cost volume (csrc/matching.hip)
  * pd_cost_volume -- ManyDepth's plane sweep from known poses: ResnetEncoderMatching.match_features, compute_confidence_mask

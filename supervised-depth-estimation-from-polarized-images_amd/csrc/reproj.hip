@@ -14,6 +14,9 @@
 // 12 + 9 threads form (K T)[:3,:] and inv_K[:3,:3] in fp64 into LDS once, every pixel reads them back as broadcasts.
 // Depth reads and warped / coords / gdepth writes are coalesced (thread = pixel, x fastest); the four taps of a pixel
 // are gathers whose locality is that of the warp itself.  No atomics: an output pixel depends on its own depth alone.
+// The gradient w.r.t. a PREDICTED pose (view_synth_bwd_pose_kernel) is the one reduction here: every pixel of an item into
+// the 12 entries of d loss / d (K T)[:3,:], formed from the same taps in the same pass as the depth gradient and summed in
+// fp64 in the fixed order of frame_reduce.hpp (rows per item, then one finalising workgroup per item that applies K^T).
 #include "pd_common.h"
 #include "frame_reduce.hpp"
 
@@ -46,8 +49,9 @@ __device__ __forceinline__ void load_cam(CamLds& cam, const float* __restrict__ 
 }
 
 // steps 1-4 of the header in fp64; q = A r is returned for the backward pass (h = depth * q + b)
+// p = depth * r, the camera point, is returned as well: the pose gradient needs it
 __device__ __forceinline__ void project(const CamLds& cam, int x, int y, double d, double& u, double& v, double& hz,
-                                        double (&q)[3]) {
+                                        double (&q)[3], double (&p)[3]) {
     const double xd = (double)x, yd = (double)y;
     double r[3], h[3];
 #pragma unroll
@@ -61,6 +65,12 @@ __device__ __forceinline__ void project(const CamLds& cam, int x, int y, double 
     hz = h[2] + 1e-7;
     u = h[0] / hz;
     v = h[1] / hz;
+    p[0] = p0; p[1] = p1; p[2] = p2;
+}
+__device__ __forceinline__ void project(const CamLds& cam, int x, int y, double d, double& u, double& v, double& hz,
+                                        double (&q)[3]) {
+    double p[3];
+    project(cam, x, y, d, u, v, hz, q, p);
 }
 
 // border padding of one axis: the clamped coordinate, its cell and the weight of the upper tap; `free_axis` is false where
@@ -144,6 +154,87 @@ __global__ __launch_bounds__(RT) void view_synth_bwd_kernel(const float* __restr
             g = (float)((double)gu * du + (double)gv * dv);
         }
         gdepth[n * HW + i] = accumulate ? gdepth[n * HW + i] + g : g;
+    }
+}
+
+// view_synth_bwd_kernel's gdepth (same expressions, hence the same bits) and, from the same taps, the 12 sums of
+// d loss / d P per item: one row of 12 doubles per workgroup (frame_reduce.hpp), gridDim.x rows per item
+__global__ __launch_bounds__(RT) void view_synth_bwd_pose_kernel(const float* __restrict__ gw, const float* __restrict__ src,
+                                                                 const float2* __restrict__ coords,
+                                                                 const float* __restrict__ depth, const float* __restrict__ K,
+                                                                 const float* __restrict__ iK, const float* __restrict__ T,
+                                                                 float* __restrict__ gdepth, double* __restrict__ partial,
+                                                                 int C, int H, int W, int accumulate) {
+    __shared__ CamLds cam;
+    __shared__ double sm[4 * 12];
+    const long n = blockIdx.y;
+    load_cam(cam, K, iK, T, n);
+    const int HW = H * W;
+    const float* s = src + n * C * (long)HW;
+    double acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.0;
+    for (int i = blockIdx.x * RT + threadIdx.x; i < HW; i += gridDim.x * RT) {
+        const int y = i / W, x = i - y * W;
+        const float2 uv = coords[n * HW + i];
+        const Axis ax = axis_of(uv.x, W), ay = axis_of(uv.y, H);
+        float g = 0.f;
+        if (ax.free_axis || ay.free_axis) {
+            const float wx0 = 1.f - ax.w1, wy0 = 1.f - ay.w1;
+            const int o00 = ay.i0 * W + ax.i0, o10 = ay.i0 * W + ax.i1, o01 = ay.i1 * W + ax.i0, o11 = ay.i1 * W + ax.i1;
+            float gu = 0.f, gv = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const float* pc = s + (long)c * HW;
+                const float v00 = pc[o00], v10 = pc[o10], v01 = pc[o01], v11 = pc[o11];
+                const float gc = gw[(n * C + c) * (long)HW + i];
+                gu += gc * ((v10 - v00) * wy0 + (v11 - v01) * ay.w1);
+                gv += gc * ((v01 - v00) * wx0 + (v11 - v10) * ax.w1);
+            }
+            double u, v, hz, q[3], p[3];
+            project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q, p);
+            const double du = ax.free_axis ? (q[0] - u * q[2]) / hz : 0.0;
+            const double dv = ay.free_axis ? (q[1] - v * q[2]) / hz : 0.0;
+            g = (float)((double)gu * du + (double)gv * dv);
+            // d loss / d h = (a0, a1, a2); h = P (p, 1).  A clamped axis adds nothing (never 0 * inf)
+            double a2 = 0.0;
+            if (ax.free_axis) {
+                const double a0 = (double)gu / hz;
+                acc[0] += a0 * p[0]; acc[1] += a0 * p[1]; acc[2] += a0 * p[2]; acc[3] += a0;
+                a2 = a0 * u;
+            }
+            if (ay.free_axis) {
+                const double a1 = (double)gv / hz;
+                acc[4] += a1 * p[0]; acc[5] += a1 * p[1]; acc[6] += a1 * p[2]; acc[7] += a1;
+                a2 = a2 + a1 * v;
+            }
+            a2 = -a2;
+            acc[8] += a2 * p[0]; acc[9] += a2 * p[1]; acc[10] += a2 * p[2]; acc[11] += a2;
+        }
+        if (gdepth) gdepth[n * HW + i] = accumulate ? gdepth[n * HW + i] + g : g;
+    }
+    pd_frames::block_rows<12>(acc, sm, partial + n * (long)gridDim.x * 12);
+}
+
+// one workgroup per item: the rows of that item in the order of finalize_rows, then gT = K[:3,:]^T gP, rounded once
+__global__ __launch_bounds__(256) void view_synth_pose_finalize_kernel(const double* __restrict__ partial, int rows,
+                                                                       const float* __restrict__ K, double* __restrict__ gP,
+                                                                       float* __restrict__ gT) {
+    __shared__ double sm[12 * 256];
+    const long n = blockIdx.x;
+    double s[12];
+    pd_frames::finalize_rows<12>(partial + n * (long)rows * 12, rows, sm, s);
+    if (threadIdx.x == 0) {
+        if (gP) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) gP[n * 12 + k] = s[k];
+        }
+        const float* k = K + n * 16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                gT[n * 16 + r * 4 + j] =
+                    (float)(((double)k[r] * s[j] + (double)k[4 + r] * s[4 + j]) + (double)k[8 + r] * s[8 + j]);
     }
 }
 
@@ -261,6 +352,33 @@ extern "C" int pd_view_synth_bwd(const void* gwarped, const void* src, const voi
                        (const float*)gwarped, (const float*)src, (const float2*)coords, (const float*)depth, (const float*)K,
                        (const float*)inv_K, (const float*)T, (float*)gdepth, C, H, W, accumulate);
     return pd::check_launch("pd_view_synth_bwd");
+}
+
+// rows of partial_ws per item: one per workgroup, at most 512 (a thread then strides over its pixels)
+extern "C" int pd_view_synth_pose_rows(int H, int W) {
+    if (H <= 0 || W <= 0) return 1;
+    const long b = ((long)H * W + RT - 1) / RT;
+    return (int)(b > 512 ? 512 : b);
+}
+
+extern "C" int pd_view_synth_bwd_pose(const void* gwarped, const void* src, const void* coords, const void* depth,
+                                      const void* K, const void* inv_K, const void* T, void* gdepth, void* partial_ws,
+                                      void* gP, void* gT, int N, int C, int H, int W, int accumulate, void* stream) {
+    if (int rc = view_synth_args("pd_view_synth_bwd_pose", depth, src, K, inv_K, T, N, C, H, W)) return rc;
+    PD_REQUIRE(gwarped && coords && partial_ws && gT,
+               "pd_view_synth_bwd_pose: gwarped, coords, partial_ws and gT must not be null");
+    PD_REQUIRE((reinterpret_cast<uintptr_t>(coords) & 7u) == 0 && (reinterpret_cast<uintptr_t>(partial_ws) & 7u) == 0 &&
+                   (reinterpret_cast<uintptr_t>(gP) & 7u) == 0,
+               "pd_view_synth_bwd_pose: coords, partial_ws and gP must be 8-byte aligned");
+    if (N == 0) return PD_OK;
+    const int rows = pd_view_synth_pose_rows(H, W);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(view_synth_bwd_pose_kernel, dim3(rows, N), dim3(RT), 0, st, (const float*)gwarped, (const float*)src,
+                       (const float2*)coords, (const float*)depth, (const float*)K, (const float*)inv_K, (const float*)T,
+                       (float*)gdepth, (double*)partial_ws, C, H, W, accumulate);
+    hipLaunchKernelGGL(view_synth_pose_finalize_kernel, dim3(N), dim3(256), 0, st, (const double*)partial_ws, rows,
+                       (const float*)K, (double*)gP, (float*)gT);
+    return pd::check_launch("pd_view_synth_bwd_pose");
 }
 
 extern "C" int pd_depth_to_updisp_bwd(const void* gdepth, const void* depth, void* gup, long n, float min_depth, float max_depth,

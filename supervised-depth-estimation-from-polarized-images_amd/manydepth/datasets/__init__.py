@@ -52,6 +52,9 @@ indoor_dataset.py:361-366).  With ``frame_idxs == [0]`` an item is, key for key 
 ``lookup_aug=True`` (opt-in; the cost-volume student's lookup frames, trainer.py:491): every neighbour also arrives as
 ``("color_aug", i, 0)``, the resized frame under the item's own ColorJitter draw (the frame itself when the item is not
 jittered, when it is blank or when it is missing); synthetic items get the same keys.  Without the switch nothing changes.
+``need_poses=False`` (opt-in; the Trainer's pose-network mode, where the poses are predicted): a neighbour is present as
+soon as its picture exists, whether or not the tree has ``_pose/``; ``("poses", i)`` is then the identity unless both pose
+files exist.
 """
 import glob
 import os
@@ -95,8 +98,12 @@ class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
                  depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None,
-                 pol_dofp=None, pol_cdofp=None, lookup_aug=False):
+                 pol_dofp=None, pol_cdofp=None, lookup_aug=False, need_poses=True):
         super().__init__()
+        # need_poses: a neighbouring frame counts as present only with both ``_pose/%06d.txt`` files (the known-pose mode).
+        # False (the Trainer's pose-network mode, which predicts the poses): the picture alone decides ("frame_valid", i),
+        # so sequences that ship no pose files train.  Default: an item is what it was, bit for bit.
+        self.need_poses = bool(need_poses)
         # lookup_aug: the neighbouring frames also arrive as ("color_aug", i, 0), jittered with the item's own ColorJitter
         # draw -- the lookup frames of the cost-volume student (trainer.py:491).  Off: an item is what it was, bit for bit.
         self.lookup_aug = bool(lookup_aug)
@@ -254,10 +261,13 @@ class HAMMER_Dataset(Dataset):
         other = idx + i * self.offset
         rgb = os.path.join(folder, "rgb", "{:06d}{}".format(other, self.img_ext))
         pc, ps = (os.path.join(folder, "_pose", "{:06d}.txt".format(k)) for k in (idx, other))
-        if other >= 0 and all(os.path.isfile(p) for p in (rgb, pc, ps)):
+        have_poses = os.path.isfile(pc) and os.path.isfile(ps)
+        if other >= 0 and os.path.isfile(rgb) and (have_poses or not self.need_poses):
             im = Image.open(rgb).convert("RGB").resize((W, H), Image.LANCZOS)
             color = torch.from_numpy(np.asarray(im, dtype=np.float32).transpose(2, 0, 1) / 255.0)
-            pose = torch.from_numpy(self.relative_pose(pc, ps).astype(np.float32))
+            # need_poses=False (the poses are predicted): the picture alone makes the frame valid; ("poses", i) is then the
+            # relative pose where both files happen to exist and the identity otherwise -- nothing reads it in that mode
+            pose = torch.from_numpy(self.relative_pose(pc, ps).astype(np.float32)) if have_poses else torch.eye(4)
             ok = 1.0
         else:
             color, pose, ok, im = torch.zeros((3, H, W), dtype=torch.float32), torch.eye(4), 0.0, None

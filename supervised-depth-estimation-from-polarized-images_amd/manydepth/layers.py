@@ -22,6 +22,22 @@ def disp_to_depth(disp, min_depth, max_depth):
     return scaled_disp, depth
 
 
+def transformation_from_parameters(axisangle, translation, invert=False):
+    """layers.py:74-91: the network's (axisangle, translation) [B,1,3] into a 4x4 matrix [B,4,4] -- one launch
+    (ops.pose_matrix), evaluated in fp64 and rounded once, differentiable in both."""
+    return ops.pose_matrix(axisangle, translation, invert)
+
+
+def get_translation_matrix(translation_vector):
+    """layers.py:94-107: the pose of a zero rotation."""
+    return ops.pose_matrix(torch.zeros_like(translation_vector), translation_vector, False)
+
+
+def rot_from_axisangle(vec):
+    """layers.py:110-149 ([B,1,3] -> [B,4,4]): the pose of a zero translation."""
+    return ops.pose_matrix(vec, torch.zeros_like(vec), False)
+
+
 class Conv3x3(nn.Module):
     """ReflectionPad2d(1) + Conv2d(3) (layers.py:364-380)."""
 

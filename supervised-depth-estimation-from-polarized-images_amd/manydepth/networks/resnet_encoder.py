@@ -56,9 +56,9 @@ class BasicBlock(nn.Module):
 
 
 class ResNet18(nn.Module):
-    def __init__(self):
+    def __init__(self, in_ch=3):
         super().__init__()
-        self.conv1 = _cl(nn.Conv2d(3, 64, 7, 2, 3, bias=False))
+        self.conv1 = _cl(nn.Conv2d(in_ch, 64, 7, 2, 3, bias=False))
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
@@ -110,6 +110,46 @@ class ShallowResnetEncoder(nn.Module):
         for blk in e.layer2:
             x = blk(x)
         self.features.append(x)
+        return self.features
+
+
+class ResnetEncoder(nn.Module):
+    """The full five-level ResNet-18 encoder (reference resnet_encoder.py:736-781) for 1 or 2 stacked input images: the
+    pose network's encoder reads two frames, 6 channels (:26-69).  torchvision's names under ``encoder.``; the 3 n-channel
+    7x7 stem runs on the space-to-depth route with (x - 0.45) / 0.225 folded into its gather.  ``pretrained`` reads
+    $PD_RESNET18_WEIGHTS and, for two images, stores cat([conv1.weight] * 2, 1) / 2 (:62-68)."""
+
+    def __init__(self, num_layers, pretrained, num_input_images=1, **kwargs):
+        super().__init__()
+        if num_layers != 18:
+            raise ValueError("{} is not a supported number of resnet layers (the hot path uses 18)".format(num_layers))
+        if num_input_images not in (1, 2):
+            raise ValueError(f"num_input_images must be 1 or 2, got {num_input_images}")
+        self.num_ch_enc = np.array([64, 64, 128, 256, 512])
+        self.encoder = ResNet18(3 * num_input_images)
+        if pretrained:
+            path = os.environ.get("PD_RESNET18_WEIGHTS")
+            if path and os.path.exists(path):
+                loaded = dict(torch.load(path, map_location="cpu"))
+                loaded["conv1.weight"] = torch.cat([loaded["conv1.weight"]] * num_input_images, 1) / num_input_images
+                self.encoder.load_state_dict(loaded)
+                _cl(self.encoder.conv1)
+            else:
+                warnings.warn("weights_init=pretrained: no local resnet18 weights ($PD_RESNET18_WEIGHTS) and no "
+                              "network access -- training the pose encoder from scratch")
+
+    def forward(self, input_image):
+        e = self.encoder
+        tr = self.training
+        self.features = []
+        cfg = PF.ChainCfg(stride=2, pad=3, relu_pre=True, affine=(0.45, 0.225))
+        x = PF.conv_bn_chain(input_image.float(), e.conv1, e.bn1, cfg, training=tr)
+        self.features.append(x)
+        x = PF.maxpool3s2(x)
+        for layer in (e.layer1, e.layer2, e.layer3, e.layer4):
+            for blk in layer:
+                x = blk(x)
+            self.features.append(x)
         return self.features
 
 

@@ -46,6 +46,11 @@ def options_from_environment(opts, env=os.environ):
     # tools/xolp_stats.py (opt.xolp_norm; default: the reference's HAMMER constants, or a loaded checkpoint's pair)
     if env.get("PD_XOLP_NORM"):
         opts.xolp_norm = env["PD_XOLP_NORM"]
+    # PD_POSE_NETWORK=1: the photometric term with poses PREDICTED by a pose network (opt.pose_network; needs
+    # --depth_supervision True without --depth_supervision_only and without --pose_input); the reference's option table has no
+    # flag that could select it here, since --pose_input False alone keeps its present meaning
+    if env.get("PD_POSE_NETWORK") == "1":
+        opts.pose_network = True
     return opts
 
 

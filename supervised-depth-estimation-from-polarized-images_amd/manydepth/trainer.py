@@ -15,10 +15,16 @@ supervised terms, plus the neighbouring frames of ``--frame_ids`` warped into th
 the ground-truth relative poses of ``_pose/%06d.txt``, compared by monodepth2's reprojection loss (minimum over the frames,
 automasking; ``--no_ssim``, ``--disable_automasking``, ``--avg_reprojection`` are honoured).  It adds ``reproj_loss/{s}`` to
 ``loss/{s}`` and their mean over the scales to ``loss``; under data parallelism the term is normalised per rank; it is not
-captured yet (``PD_STEP_GRAPH=1`` is refused with it).  The cost-volume student's building blocks exist -- the plane sweep
-(``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training branch (``--train_student``: matching
-augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it, the pose network, ``--v1_multiscale``, DPT
-and stereo branches raise NotImplementedError.
+captured yet (``PD_STEP_GRAPH=1`` is refused with it).  With ``opt.pose_network = True`` (``PD_POSE_NETWORK=1``; needs
+``--depth_supervision True`` without ``--depth_supervision_only`` and without ``--pose_input``) the poses of that term are
+PREDICTED: ``pose_encoder`` (ResnetEncoder, two stacked frames) and ``pose`` (PoseDecoder) see the jittered frame pair of
+every neighbour in temporal order (trainer.py:222-236, 669-707), their output goes through transformation_from_parameters into
+the same warp, and the term trains depth and pose together; ``--supervise_pose``, ``--res_pose`` and the matching-pose half
+of predict_poses are not built, and ``PD_STEP_GRAPH=1`` / ``opt.bf16`` / ``torch.distributed`` are refused with it; its loaders
+take a neighbour's picture without asking for pose files (``HAMMER_Dataset(need_poses=False)``).  The cost-volume student's building
+blocks exist -- the plane sweep (``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training
+branch (``--train_student``: matching augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it,
+``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
 
 What runs where: every tensor operation of a training step is a hand-written HIP kernel from
 libpolardepth.so (polar preprocessing K1, implicit-GEMM convolutions K2, fused BN/ReLU/pool chains
@@ -64,6 +70,8 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
 
 def _unused_resnet_param(model_name, param_name):
     """ShallowResnetEncoder builds a full resnet18 but never runs layer3/layer4/fc (resnet_encoder.py:819-820)."""
+    if model_name == "pose_encoder":              # the full encoder runs every layer but the classifier
+        return param_name.split(".")[1] == "fc"
     return model_name == "rgb_encoder" and param_name.split(".")[1] in ("layer3", "layer4", "fc")
 
 
@@ -117,8 +125,25 @@ class Trainer:
                 raise NotImplementedError(f"--{flag}: outside the supervised hot path of this build")
         # the one further configuration: the supervised terms plus the photometric reprojection term from the neighbouring
         # frames, warped with the ground-truth relative poses (no pose network, no cost volume)
-        self.photometric = bool(self.opt.depth_supervision and self.opt.pose_input and not self.opt.depth_supervision_only
-                                and not getattr(self.opt, "v1_multiscale", False))
+        # ... or with the relative poses PREDICTED by a pose network that is trained along (monodepth2's setting;
+        # trainer.py:222-236, 669-707).  Not a reference CLI flag (--pose_input False alone keeps its meaning): selected on
+        # the options object (``opt.pose_network = True``; manydepth/train.py maps PD_POSE_NETWORK=1 onto it)
+        self.pose_network = bool(getattr(self.opt, "pose_network", False))
+        if self.pose_network:
+            if not self.opt.depth_supervision or self.opt.depth_supervision_only or self.opt.pose_input:
+                raise ValueError("opt.pose_network: needs --depth_supervision True, without --depth_supervision_only and "
+                                 "without --pose_input (the poses are predicted, not read)")
+            if os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False)):
+                raise NotImplementedError("PD_STEP_GRAPH=1 with opt.pose_network: this mode is not captured yet")
+            if _bf16_variant(self.opt):
+                raise NotImplementedError("opt.bf16 with opt.pose_network: the pose network has not been verified in bf16")
+            # the pose modules run once per neighbouring frame, so their gradient buffers are written twice per step; the
+            # gradient reducer marks a parameter ready -- and all-reduces its bucket -- after the FIRST write
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                raise NotImplementedError("torch.distributed with opt.pose_network: the gradient reducer expects one "
+                                          "backward pass per module and step; run this mode on one GPU")
+        self.photometric = bool(self.opt.depth_supervision and (self.opt.pose_input or self.pose_network)
+                                and not self.opt.depth_supervision_only and not getattr(self.opt, "v1_multiscale", False))
         if not (self.opt.depth_supervision_only and self.opt.depth_supervision) and not self.photometric:
             raise NotImplementedError("only --depth_supervision_only True --depth_supervision True is implemented "
                                       "(the path of train_supervised_GT.sh)")
@@ -193,6 +218,11 @@ class Trainer:
             if not self.opt.augment_normals:
                 raise ValueError("the separate normals decoder sits behind the normals encoder: it needs --augment_normals")
             self.models["normals_decoder"] = networks.NormalsDecoder(64)
+        if self.pose_network:                     # trainer.py:222-236 for pose_model_type "separate_resnet"
+            self.models["pose_encoder"] = networks.ResnetEncoder(18, self.opt.weights_init == "pretrained",
+                                                                 num_input_images=2)
+            self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc, num_input_features=1,
+                                                       num_frames_to_predict_for=2)
         for m in self.models.values():
             m.to(self.device)
         if self.distributed:                    # identical replicas: broadcast rank 0's initialisation
@@ -201,7 +231,7 @@ class Trainer:
                     torch.distributed.broadcast(t.data, 0)
 
         order = [n for n in ("rgb_encoder", "xolp_encoder", "normals_encoder", "joint_encoder", "mono_depth",
-                             "normals_decoder") if n in self.models]
+                             "normals_decoder", "pose_encoder", "pose") if n in self.models]
         self.store = ParamStore(self.models, order=order, unused=_unused_resnet_param, device=self.device)
         for n in order:
             self.parameters_to_train += list(self.models[n].parameters())
@@ -235,7 +265,8 @@ class Trainer:
         mk = lambda path, files, tr: self.dataset(path, files, self.opt.height, self.opt.width, self.frame_ids, 4, is_train=tr,
                                                   img_ext='.png', offset=self.opt.offset, modality=self.opt.modality,
                                                   supervised_depth=True, supervised_depth_only=not self.photometric,
-                                                  depth_modality=self.opt.depth_modality)
+                                                  depth_modality=self.opt.depth_modality, lookup_aug=self.pose_network,
+                                                  need_poses=not self.pose_network)
         train_dataset, val_dataset, test_dataset = mk(self.data_path, train_files, True), \
             mk(self.data_path, val_files, False), mk(self.data_path_val, test_files, False)
         if self.pol_calibration is not None:
@@ -436,10 +467,28 @@ class Trainer:
         else:
             with torch.no_grad():
                 mono_outputs = self._forward_models(inputs)
+        if self.pose_network:                     # --freeze_teacher_and_pose: the pose pass runs without a tape too
+            with torch.set_grad_enabled(self.train_teacher_and_pose and torch.is_grad_enabled()):
+                mono_outputs.update(self.predict_poses(inputs))
         for scale in self.opt.scales:
             mono_outputs[("disp", 0, scale)] = mono_outputs[("disp", scale)]
         losses = self.compute_losses(inputs, mono_outputs, is_multi=False)
         return mono_outputs, losses, mono_outputs
+
+    def predict_poses(self, inputs):
+        """The first half of trainer.py:669-707 (``opt.pose_network``): one pass of the pose network per neighbouring frame,
+        the two jittered frames stacked in temporal order -- NOT one batched pass over the frames: the BatchNorm statistics
+        are per pass in the reference.  The decoder's tail and both matrices are one launch (csrc/pose.hip)."""
+        outputs = {}
+        cur = inputs[("color_aug", 0, 0)].float()
+        for f_i in self.frame_ids[1:]:
+            other = inputs[("color_aug", f_i, 0)].float()
+            pair = [other, cur] if f_i < 0 else [cur, other]
+            feats = self.models["pose_encoder"](torch.cat(pair, 1))
+            axisangle, translation, T, T_inv = self.models["pose"].forward_with_matrices([feats], invert=f_i < 0)
+            outputs[("axisangle", 0, f_i)], outputs[("translation", 0, f_i)] = axisangle, translation
+            outputs[("cam_T_cam", 0, f_i)], outputs[("cam_T_cam_inv", 0, f_i)] = T, T_inv
+        return outputs
 
     def compute_losses(self, inputs, outputs, is_multi=False):
         """Supervised branch of trainer.py:1126-1296; also fills ("depth",0,s) / ("mono_depth",0,s)
@@ -465,7 +514,8 @@ class Trainer:
                 noise = [torch.randn(depths[0].shape, device=depths[0].device).mul_(1e-5) for _ in scales]
             reproj = PF.photometric_loss(self.loss_cfg, disps, depths, inputs[("color", 0, 0)],
                                          [inputs[("color", i, 0)] for i in ids], inputs[("K", 0)], inputs[("inv_K", 0)],
-                                         [inputs[("poses", i)] for i in ids],
+                                         [outputs[("cam_T_cam", 0, i)] if self.pose_network else inputs[("poses", i)]
+                                          for i in ids],
                                          torch.stack([inputs[("frame_valid", i)] for i in ids], 1).float(), noise=noise,
                                          no_ssim=self.opt.no_ssim, automask=automask, avg=self.opt.avg_reprojection)
             for i, s in enumerate(scales):        # trainer.py:1234-1236, 1262-1265

@@ -132,6 +132,12 @@ SIGNATURES = {
     "pd_depth_metrics": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _l, _f, _f, _vp]),
     "pd_view_synth_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pd_view_synth_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "pd_view_synth_pose_rows": (_i, [_i, _i]),
+    "pd_view_synth_bwd_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "pd_pose_matrix_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "pd_pose_matrix_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "pd_pose_head_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "pd_pose_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "pd_depth_to_updisp_bwd": (_i, [_vp, _vp, _vp, _l, _f, _f, _vp]),
     "pd_reproj_combine_rows": (_i, [_i, _i, _i]),
     "pd_reproj_combine_fwd": (_i, [_vpp, _vpp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1180,6 +1180,7 @@ def photometric_loss(cfg, disps, depths, target, sources, K, inv_K, poses, valid
     disps    the disparity maps [N,1,hs,ws] the term is differentiable in (an entry, or the list, may be None: that depth
              map is data); depths: the full-resolution depth maps [N,1,H,W] ``multiscale_loss`` returned for them
     target   [N,3,H,W] ("color", 0, 0); sources: F frames [N,3,H,W]; poses: F matrices [N,4,4] current -> source camera
+             (known poses are data; a predicted pose that requires a gradient receives one through ``ops.view_synthesis``)
     K, inv_K [N,4,4] of scale 0; valid [N,F], 0 = the frame does not exist (None: all do)
     noise    the automask tie-breaker added to the identity value: one [N,1,H,W] map for every scale or a list of one per
              scale (trainer.py:1193-1194 draws one per scale); ignored without automasking
@@ -1326,6 +1327,28 @@ class ConvBiasActFn(torch.autograd.Function):
 
 def conv_bias_act(x, conv, act=ops.ACT_NONE):
     return ConvBiasActFn.apply(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0], int(act))
+
+
+class PoseHeadFn(ops._PoseHeadFn):
+    """ops.pose_head for a module's 1x1 convolution: the weight and bias gradients are added to the parameters' gradient
+    buffers (grad_buf, like every convolution here), not returned to autograd."""
+
+    @staticmethod
+    def backward(ctx, gaa, gtr, gT, gTi):
+        weight, bias = ctx.params
+        gw = grad_buf(weight) if weight.requires_grad else torch.zeros_like(weight)
+        gb = grad_buf(bias) if bias.requires_grad else torch.zeros_like(bias)
+        gx = ops.pose_head_bwd(ctx.saved_tensors, ctx.geom, (gaa, gtr, gT, gTi), gw, gb, accumulate=True)
+        for p in (weight, bias):
+            _ready(p)
+        return (gx if ctx.needs_input_grad[0] else None), None, None, None
+
+
+def pose_head(x, conv, invert=False):
+    """The tail of PoseDecoder.forward through ``conv`` = its ("pose", 2) 1x1 convolution (ops.pose_head): (axisangle,
+    translation, cam_T_cam, cam_T_cam_inv)."""
+    _need_cuda4(x, "pose_head")
+    return PoseHeadFn.apply(ops.as_nhwc(x.float()), conv.weight, conv.bias, bool(invert))
 
 
 class ReluFn(torch.autograd.Function):

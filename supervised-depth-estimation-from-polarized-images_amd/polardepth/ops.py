@@ -380,7 +380,8 @@ def _dev_ptrs(tensors):
 
 class _ViewSynthFn(torch.autograd.Function):
     """BackprojectDepth + Project3D + grid_sample(border, align_corners=True) for one source frame (pd_view_synth_fwd /
-    _bwd): differentiable in depth only -- the source, the intrinsics and the pose are data."""
+    _bwd): differentiable in depth and, where the pose requires a gradient, in T (pd_view_synth_bwd_pose, one pass for
+    both) -- the source and the intrinsics are data."""
 
     @staticmethod
     def forward(ctx, depth, src, K, inv_K, T):
@@ -397,6 +398,14 @@ class _ViewSynthFn(torch.autograd.Function):
     def backward(ctx, gwarped, _gcoords):
         depth, src, K, inv_K, T, coords = ctx.saved_tensors
         N, C, H, W = src.shape
+        if ctx.needs_input_grad[4]:
+            gdepth = torch.empty_like(depth) if ctx.needs_input_grad[0] else None
+            part = torch.empty((N, lib.pd_view_synth_pose_rows(H, W), 12), dtype=torch.float64, device=src.device)
+            gT = torch.empty((N, 4, 4), dtype=torch.float32, device=src.device)
+            check(lib.pd_view_synth_bwd_pose(ptr(gwarped.float().contiguous()), ptr(src), ptr(coords), ptr(depth), ptr(K),
+                                             ptr(inv_K), ptr(T), ptr(gdepth), ptr(part), None, ptr(gT), N, C, H, W, 0,
+                                             stream_ptr()), "pd_view_synth_bwd_pose")
+            return gdepth, None, None, None, gT
         gdepth = torch.empty_like(depth)
         check(lib.pd_view_synth_bwd(ptr(gwarped.float().contiguous()), ptr(src), ptr(coords), ptr(depth), ptr(K), ptr(inv_K),
                                     ptr(T), ptr(gdepth), N, C, H, W, 0, stream_ptr()), "pd_view_synth_bwd")
@@ -407,7 +416,9 @@ def view_synthesis(depth, src, K, inv_K, T):
     """trainer.py:1021-1044 for one neighbouring frame: ``src`` [N,C,H,W] warped into the current view through ``depth``
     [N,1,H,W], the intrinsics ``K`` / ``inv_K`` [N,4,4] and the relative pose ``T`` [N,4,4] (current camera -> source camera).
     Returns (warped [N,C,H,W], coords [N,H,W,2]): coords are the unclamped source PIXEL coordinates (u, v) of every pixel
-    (include/polardepth.h states the arithmetic).  Differentiable in depth."""
+    (include/polardepth.h states the arithmetic).  Differentiable in depth, and in ``T`` where it requires a gradient (a
+    predicted pose: ``pose_matrix`` / ``pose_head``): the pose gradient is a deterministic fp64 reduction over the pixels,
+    formed in the same pass as the depth gradient.  A pose that requires no gradient costs what it did."""
     _require_cuda(depth, src, K, inv_K, T)
     if src.dim() != 4 or depth.dim() != 4 or depth.shape[1] != 1 or depth.shape[0] != src.shape[0] or \
             depth.shape[2:] != src.shape[2:]:
@@ -478,6 +489,107 @@ def reproj_combine(reproj, identity=None, noise=None, valid=None, avg=False, det
                                              None if noise is None else f(noise).detach(),
                                              None if valid is None else f(valid).detach(), bool(avg), *[f(t) for t in reproj])
     return (loss, sel, sums) if details else loss
+
+
+# ------------------------------------------------------------------ pose network tail (csrc/pose.hip)
+class _PoseMatrixFn(torch.autograd.Function):
+    """transformation_from_parameters (pd_pose_matrix_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, axisangle, translation, invert):
+        N = axisangle.shape[0]
+        T = torch.empty((N, 4, 4), dtype=torch.float32, device=axisangle.device)
+        check(lib.pd_pose_matrix_fwd(ptr(axisangle), ptr(translation), ptr(T), N, int(invert), stream_ptr()),
+              "pd_pose_matrix_fwd")
+        ctx.invert = int(invert)
+        ctx.save_for_backward(axisangle, translation)
+        return T
+
+    @staticmethod
+    def backward(ctx, gT):
+        axisangle, translation = ctx.saved_tensors
+        N = axisangle.shape[0]
+        ga, gt = torch.empty_like(axisangle), torch.empty_like(translation)
+        check(lib.pd_pose_matrix_bwd(ptr(gT.float().contiguous()), ptr(axisangle), ptr(translation), ptr(ga), ptr(gt), N,
+                                     ctx.invert, stream_ptr()), "pd_pose_matrix_bwd")
+        return ga, gt, None
+
+
+def pose_matrix(axisangle, translation, invert=False):
+    """layers.py:74-91 ``transformation_from_parameters``: ``axisangle`` and ``translation`` ([N,1,3] or [N,3]) to the 4x4
+    matrix ``T`` [N,4,4] -- Trans(t) R, or with ``invert`` R^T Trans(-t) -- evaluated in fp64 and rounded once
+    (include/polardepth.h states the order).  Differentiable in both."""
+    _require_cuda(axisangle, translation)
+    N = axisangle.shape[0]
+    if axisangle.numel() != 3 * N or translation.numel() != 3 * N or translation.shape[0] != N:
+        raise ValueError(f"pose_matrix: axisangle and translation must be [N,1,3] or [N,3], got {tuple(axisangle.shape)} / "
+                         f"{tuple(translation.shape)}")
+    f = lambda t: t.float().reshape(N, 3).contiguous()
+    return _PoseMatrixFn.apply(f(axisangle), f(translation), bool(invert))
+
+
+class _PoseHeadFn(torch.autograd.Function):
+    """PoseDecoder's tail and both matrices of slot 0 (pd_pose_head_fwd / _bwd); x is NHWC storage of [N,Cin,h,w]."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, invert):
+        N, Cin, h, w = x.shape
+        Co = weight.shape[0]
+        dev = x.device
+        nf = Co // 6
+        aa = torch.empty((N, nf, 1, 3), dtype=torch.float32, device=dev)
+        tr = torch.empty((N, nf, 1, 3), dtype=torch.float32, device=dev)
+        T = torch.empty((N, 4, 4), dtype=torch.float32, device=dev)
+        Ti = torch.empty((N, 4, 4), dtype=torch.float32, device=dev)
+        mean = torch.empty((N, Cin), dtype=torch.float64, device=dev)
+        check(lib.pd_pose_head_fwd(ptr(x), ptr(weight), ptr(bias), ptr(aa), ptr(tr), ptr(T), ptr(Ti), ptr(mean), N, h, w, Cin,
+                                   Co, int(invert), stream_ptr()), "pd_pose_head_fwd")
+        ctx.geom = (N, h, w, Cin, Co, int(invert))
+        ctx.params = (weight, bias)
+        ctx.save_for_backward(weight, mean, aa, tr)
+        ctx.set_materialize_grads(False)          # an unused output hands None to the kernel, not a tensor of zeros
+        return aa, tr, T, Ti
+
+    @staticmethod
+    def backward(ctx, gaa, gtr, gT, gTi):
+        weight = ctx.saved_tensors[0]
+        gw = torch.empty_like(weight)
+        gb = torch.empty(weight.shape[0], dtype=torch.float32, device=weight.device)
+        gx = pose_head_bwd(ctx.saved_tensors, ctx.geom, (gaa, gtr, gT, gTi), gw, gb, accumulate=False)
+        return gx, gw, gb, None
+
+
+def pose_head_bwd(saved, geom, grads, gw, gb, accumulate):
+    """pd_pose_head_bwd for what _PoseHeadFn.forward saved: returns gx and writes (``accumulate``: adds to) ``gw`` / ``gb``,
+    which have the storage of the 1x1 convolution's weight and bias (functional.PoseHeadFn hands in the gradient buffers)."""
+    weight, mean, aa, tr = saved
+    N, h, w, Cin, Co, invert = geom
+    gaa, gtr, gT, gTi = (None if t is None else t.float().contiguous() for t in grads)
+    gx = empty_nhwc(N, Cin, h, w, weight.device)
+    ws = torch.empty((N, Co), dtype=torch.float64, device=weight.device)
+    check(lib.pd_pose_head_bwd(ptr(gT), ptr(gTi), ptr(gaa), ptr(gtr), ptr(aa), ptr(tr), ptr(weight), ptr(mean), ptr(gx),
+                               ptr(gw), ptr(gb), ptr(ws), N, h, w, Cin, Co, invert, int(accumulate), stream_ptr()),
+          "pd_pose_head_bwd")
+    return gx
+
+
+def pose_head(x, weight, bias, invert=False):
+    """The tail of PoseDecoder.forward (pose_decoder.py:41-50) from the input of ("pose", 2) on, in one launch: ``x``
+    [N,Cin,h,w] (channels_last), ``weight`` [Co,Cin,1,1] or [Co,Cin] and ``bias`` [Co] of the 1x1 convolution, Co = 6 nf.
+    Returns (axisangle [N,nf,1,3], translation [N,nf,1,3], T [N,4,4], T_inv [N,4,4]): the matrices are
+    ``pose_matrix(axisangle[:, 0], translation[:, 0], invert)`` and the same with ``invert`` flipped (the reference's
+    cam_T_cam / cam_T_cam_inv).  Differentiable in x, weight and bias through all four outputs."""
+    _require_cuda(x, weight, bias)
+    if x.dim() != 4:
+        raise ValueError(f"pose_head: x must be [N,Cin,h,w], got {tuple(x.shape)}")
+    Co, Cin = weight.shape[0], x.shape[1]
+    if weight.numel() != Co * Cin or tuple(bias.shape) != (Co,):
+        raise ValueError(f"pose_head: weight [Co,{Cin}(,1,1)] and bias [Co] expected, got {tuple(weight.shape)} / "
+                         f"{tuple(bias.shape)}")
+    if Cin % 64 or Cin > 1024 or Co % 6:
+        raise ValueError(f"pose_head: Cin must be a multiple of 64 (<= 1024) and Co a multiple of 6, got {Cin} / {Co}")
+    return _PoseHeadFn.apply(as_nhwc(x.float()), weight.float().reshape(Co, Cin).contiguous(), bias.float().contiguous(),
+                             bool(invert))
 
 
 # ------------------------------------------------------------------ multi-frame cost volume (csrc/matching.hip)

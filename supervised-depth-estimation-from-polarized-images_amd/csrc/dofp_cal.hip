@@ -300,7 +300,7 @@ extern "C" int pd_frame_moments(const void* frames, int dtype, const void* dark,
                "pd_frame_moments: %d frames of %d x %d are too large for the kernel's index arithmetic", N, H2, W2);
     PD_REQUIRE(pd::aligned16(frames) && pd::aligned16(dark) && pd::aligned16(out),
                "pd_frame_moments: frames, dark and out must be 16-byte aligned");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(weights) & 7u) == 0, "pd_frame_moments: weights must be 8-byte aligned");
+    PD_REQUIRE(pd::aligned8(weights), "pd_frame_moments: weights must be 8-byte aligned");
     const int groups = (H2 / 2) * (W2 / 2);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == PD_POLAR_U8) launch_moments<uint8_t>(frames, dark, weights, out, N, Q, groups, accumulate != 0, st);
@@ -326,7 +326,7 @@ extern "C" int pd_dofp_cal_solve(const double* moments, const double* rinv, cons
     PD_CAL_SIDES("pd_dofp_cal_solve");
     PD_REQUIRE((long)H2 * W2 <= (1L << 30), "pd_dofp_cal_solve: a frame of %d x %d is too large for the kernel's index arithmetic",
                H2, W2);
-    PD_REQUIRE(pd::aligned16(moments) && pd::aligned16(gain) && (reinterpret_cast<uintptr_t>(quality) & 3u) == 0,
+    PD_REQUIRE(pd::aligned16(moments) && pd::aligned16(gain) && pd::aligned4(quality),
                "pd_dofp_cal_solve: moments and gain must be 16-byte aligned (quality: 4-byte)");
     hipLaunchKernelGGL(dofp_cal_solve_kernel, dim3(grid_for((long)(H2 / 2) * (W2 / 2))), dim3(kThreads), 0, (hipStream_t)stream,
                        moments, gain, quality, k, H2 / 2, W2 / 2);

@@ -7,6 +7,7 @@
 // torchvision BasicBlock bn/relu/add, resnet maxpool (resnet_encoder.py:813-818),
 // layers.py:446-449 upsample + depth_decoder.py:64-67 cat, trainer.py:238-240,442 Adam.
 #include "pd_common.h"
+#include "wave_ops.hpp"
 #include <cstdlib>
 #include <cstdint>
 
@@ -446,14 +447,7 @@ __global__ __launch_bounds__(EW_T) void chain_bwd_kernel(const ChainArgs a) {
     }
 }
 
-// i -> (i / d, i % d) for a positive divisor: 32-bit unsigned arithmetic whenever the index fits (every grid-stride index
-// of the training step does); a 64-bit division is ~5x the instructions, and the pixel decode below needs three
-__device__ __forceinline__ long divmod(long i, int d, int& rem) {
-    if (i >> 32) { const long q = i / d; rem = (int)(i - q * d); return q; }
-    const unsigned u = (unsigned)i, q = u / (unsigned)d;
-    rem = (int)(u - q * (unsigned)d);
-    return (long)q;
-}
+using pd_wave::divmod;
 
 // grad of the residual input of a post-add ReLU block: dres = dy * (out > 0)
 __global__ __launch_bounds__(EW_T) void relu_mask_kernel(const float* __restrict__ dy, long ld_dy,

@@ -1,15 +1,17 @@
 // Shared by csrc/reproj.hip (pd_reproj_combine_*) and csrc/student.hip (pd_student_combine_*): the per-pixel minimum / mean
-// over the valid neighbouring frames, and the two-stage fp64 reduction of K masked sums in a fixed order.
+// over the valid neighbouring frames, the two-stage fp64 reduction of K masked sums in a fixed order, and the argument check
+// of their entry points.
 //
 // Order of the sums (what makes them bit-reproducible): per thread over its grid-stride pixels, per wavefront by xor
 // shuffles (32, 16, ... 1), per workgroup ((w0 + w1) + w2) + w3 over its four wavefronts, one row of K doubles per
 // workgroup; then ONE workgroup of 256 threads: thread t adds rows t, t + 256, ... and a binary tree over LDS adds the 256.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "pd_common.h"
+#include "wave_ops.hpp"
 
 namespace pd_frames {
 
-constexpr int RT = 256;            // threads per workgroup of every kernel that uses block_rows / finalize_rows
+constexpr int RT = pd::GRID_THREADS;   // threads per workgroup of every kernel that uses block_rows / finalize_rows
 constexpr int MAX_FRAMES = 8;      // = PD_REPROJ_MAX_FRAMES
 
 struct FrameArgs {
@@ -47,12 +49,6 @@ __device__ __forceinline__ float over_frames(const float* const* maps, const flo
     return o.m;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // the workgroup's K sums -> partial[blockIdx.x * K + k]; sm: RT / 64 * K doubles of LDS.  Every thread must call it.
 template <int K>
 __device__ __forceinline__ void block_rows(double (&acc)[K], double* sm, double* __restrict__ partial) {
@@ -60,7 +56,7 @@ __device__ __forceinline__ void block_rows(double (&acc)[K], double* sm, double*
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const double v = wave_sum_d(acc[k]);
+        const double v = pd_wave::wave_sum(acc[k]);
         if (lane == 0) sm[wave * K + k] = v;
     }
     __syncthreads();
@@ -95,12 +91,13 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ partial
     for (int k = 0; k < K; ++k) out[k] = sm[k * 256];
 }
 
-// workgroups of a flat grid-stride kernel over n work items: at most 2048, at least 1
-inline unsigned rgrid(long n) {
-    long b = (n + RT - 1) / RT;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (unsigned)b;
+// the frame count, shape and `avg` of the pd_*_combine_* entry points
+inline int combine_args(const char* who, int F, int N, int H, int W, int avg) {
+    PD_REQUIRE(F >= 1 && F <= MAX_FRAMES, "%s: 1 <= F <= %d frames, got %d", who, MAX_FRAMES, F);
+    PD_REQUIRE(N >= 0 && H > 0 && W > 0, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    PD_REQUIRE((long)H * W <= (1L << 30), "%s: image too large (%d x %d)", who, H, W);
+    PD_REQUIRE(avg == 0 || avg == 1, "%s: avg must be 0 or 1, got %d", who, avg);
+    return PD_OK;
 }
 
 }  // namespace pd_frames

@@ -12,18 +12,16 @@
 // All sums are reduced per wavefront (shuffles), then per workgroup, written as fp32 partials and
 // finished in fp64 by a one-block kernel -- no float atomics, run-to-run deterministic.
 #include "pd_common.h"
+#include "wave_ops.hpp"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
+using pd_wave::divmod;
+using pd_wave::wave_sum;
 constexpr int LT = 256;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+static_assert(LT == pd::GRID_THREADS, "pd::flat_grid sizes grids for 256 threads");
 
 // block-wide sum of K values; result valid in thread 0
 template <int K>
@@ -38,22 +36,6 @@ __device__ __forceinline__ void block_sum(float (&v)[K], float* smem /* [4][K] *
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < K; ++k) v[k] = smem[k] + smem[K + k] + smem[2 * K + k] + smem[3 * K + k];
-}
-
-inline unsigned lgrid(long n) {
-    long b = (n + LT - 1) / LT;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
-// i -> (i / d, i % d) for a positive divisor: 32-bit unsigned arithmetic whenever the index fits; a 64-bit division is ~5x
-// the instructions and every per-pixel kernel below decodes (n, y, x) with two of them
-__device__ __forceinline__ long divmod(long i, int d, int& rem) {
-    if (i >> 32) { const long q = i / d; rem = (int)(i - q * d); return q; }
-    const unsigned u = (unsigned)i, q = u / (unsigned)d;
-    rem = (int)(u - q * (unsigned)d);
-    return (long)q;
 }
 
 // torch upsample_bilinear2d source index (align_corners=False)
@@ -553,8 +535,7 @@ __device__ __forceinline__ void image_mean_body(double (&sm)[16], const float* _
         s0 += v.x; s1 += v.y; s2 += v.z; s3 += v.w;
     }
     for (int i = 4 * P4 + threadIdx.x; i < P; i += 1024) s0 += d[i];
-    double s = (s0 + s1) + (s2 + s3);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const double s = wave_sum((s0 + s1) + (s2 + s3));
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -622,8 +603,7 @@ __device__ __forceinline__ void smooth_bwd_g_body(double (&smd)[4], const float*
     long run_n = -1;
     auto flush = [&]() {                       // block-uniform
         if (run_n >= 0) {
-            double v = run;
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            const double v = wave_sum(run);
             if ((threadIdx.x & 63) == 0) smd[threadIdx.x >> 6] = v;
             __syncthreads();
             if (threadIdx.x == 0) atomicAdd(&gd_acc[run_n], (smd[0] + smd[1]) + (smd[2] + smd[3]));
@@ -902,14 +882,14 @@ __global__ void loss_weights_kernel(const float* __restrict__ gvals, const LossM
 }  // namespace
 
 // ============================================================================ C ABI
-extern "C" int pd_loss_rows(long n) { return (int)lgrid(n); }
+extern "C" int pd_loss_rows(long n) { return (int)pd::flat_grid(n); }
 
 extern "C" int pd_disp_to_depth(const void* disp, void* depth, void* updisp, int N, int hs, int ws, int H, int W,
                                 float min_depth, float max_depth, void* stream) {
     PD_REQUIRE(disp && depth && N >= 0 && hs > 0 && ws > 0 && H >= hs && W >= ws, "pd_disp_to_depth: bad arguments");
     PD_REQUIRE(min_depth > 0 && max_depth > min_depth, "pd_disp_to_depth: bad depth range");
     if (N == 0) return PD_OK;
-    hipLaunchKernelGGL(disp_to_depth_kernel, dim3(lgrid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(disp_to_depth_kernel, dim3(pd::flat_grid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream,
                        (const float*)disp, (float*)depth, (float*)updisp, N, hs, ws, H, W, 1.f / max_depth,
                        1.f / min_depth);
     return pd::check_launch("pd_disp_to_depth");
@@ -921,7 +901,7 @@ extern "C" int pd_up_gather_bwd(const void* gup, void* gdisp, int N, int hs, int
     PD_REQUIRE(H % hs == 0 && W % ws == 0, "pd_up_gather_bwd: full size must be an integer multiple of the scale size");
     if (N == 0) return PD_OK;
     const int f = generic ? 0 : H / hs;                                // generic != 0: the any-ratio kernel (tests compare the two)
-    const unsigned grid = lgrid((long)N * hs * ws);
+    const unsigned grid = pd::flat_grid((long)N * hs * ws);
 #define PD_UPG(F) hipLaunchKernelGGL(up_gather_bwd_f_kernel<F>, dim3(grid), dim3(LT), 0, (hipStream_t)stream, \
                                      (const float*)gup, (float*)gdisp, N, hs, ws, H, W, accumulate)
     if (W / ws == f && f == 1) PD_UPG(1);
@@ -938,7 +918,7 @@ extern "C" int pd_up_gather_bwd(const void* gup, void* gdisp, int N, int hs, int
 extern "C" int pd_gt_normals(const void* gt, const void* K, void* gtn, int N, int H, int W, float min_depth,
                              float max_depth, void* stream) {
     PD_REQUIRE(gt && K && gtn && N > 0 && H > 0 && W > 0 && pd::aligned16(gtn), "pd_gt_normals: bad arguments");
-    hipLaunchKernelGGL(gt_normals_kernel, dim3(lgrid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream, (const float*)gt,
+    hipLaunchKernelGGL(gt_normals_kernel, dim3(pd::flat_grid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream, (const float*)gt,
                        (const float*)K, (float4*)gtn, N, H, W, min_depth, max_depth);
     return pd::check_launch("pd_gt_normals");
 }
@@ -947,7 +927,7 @@ extern "C" int pd_sup_loss_fwd(const void* pred, const void* gt, const void* K, 
                                int H, int W, float min_depth, float max_depth, int with_normals, void* stream) {
     PD_REQUIRE(pred && gt && partial && (K || !with_normals) && N > 0 && H > 0 && W > 0 && pd::aligned16(gt_normals),
                "pd_sup_loss_fwd: bad arguments");
-    hipLaunchKernelGGL(sup_fwd_kernel, dim3(lgrid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(sup_fwd_kernel, dim3(pd::flat_grid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream,
                        (const float*)pred, (const float*)gt, (const float*)K, (const float4*)gt_normals, (float*)partial, N,
                        H, W, min_depth, max_depth, with_normals);
     return pd::check_launch("pd_sup_loss_fwd");
@@ -957,7 +937,7 @@ extern "C" int pd_normals_loss_masked(const void* pred, const void* gt, const vo
                                       void* out, int N, int H, int W, void* stream) {
     PD_REQUIRE(pred && gt && K && mask && partial_ws && out && N > 0 && H > 0 && W > 0, "pd_normals_loss_masked: bad arguments");
     const long total = (long)N * H * W;
-    const int rows = (int)lgrid(total);
+    const int rows = (int)pd::flat_grid(total);
     hipLaunchKernelGGL(normals_loss_masked_kernel, dim3(rows), dim3(LT), 0, (hipStream_t)stream, (const float*)pred,
                        (const float*)gt, (const float*)K, (const float*)mask, (float*)partial_ws, N, H, W);
     hipLaunchKernelGGL(ratio_of_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial_ws, rows,
@@ -970,7 +950,7 @@ extern "C" int pd_normals_pred_loss_fwd(const void* pred, long ld, const void* g
     PD_REQUIRE(pred && gt_normals && gt && partial_ws && out && N > 0 && H > 0 && W > 0 && ld >= 3 && pd::aligned16(gt_normals),
                "pd_normals_pred_loss_fwd: bad arguments");
     const long total = (long)N * H * W;
-    const int rows = (int)lgrid(total);
+    const int rows = (int)pd::flat_grid(total);
     hipLaunchKernelGGL(normals_pred_fwd_kernel, dim3(rows), dim3(LT), 0, (hipStream_t)stream, (const float*)pred, ld,
                        (const float4*)gt_normals, (const float*)gt, (float*)partial_ws, total, min_depth, max_depth);
     hipLaunchKernelGGL(ratio_and_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial_ws, rows,
@@ -984,7 +964,7 @@ extern "C" int pd_normals_pred_loss_bwd(const void* pred, long ld, const void* g
     PD_REQUIRE(pred && gt_normals && gt && gout && loss_count && dpred && N > 0 && H > 0 && W > 0 && ld >= 3 && ld_dpred >= 3 &&
                    pd::aligned16(gt_normals), "pd_normals_pred_loss_bwd: bad arguments");
     const long total = (long)N * H * W;
-    hipLaunchKernelGGL(normals_pred_bwd_kernel, dim3(lgrid(total)), dim3(LT), 0, (hipStream_t)stream, (const float*)pred, ld,
+    hipLaunchKernelGGL(normals_pred_bwd_kernel, dim3(pd::flat_grid(total)), dim3(LT), 0, (hipStream_t)stream, (const float*)pred, ld,
                        (const float4*)gt_normals, (const float*)gt, (const float*)gout, (const float*)loss_count, (float*)dpred,
                        ld_dpred, total, min_depth, max_depth);
     return pd::check_launch("pd_normals_pred_loss_bwd");
@@ -997,7 +977,7 @@ extern "C" int pd_sup_loss_bwd(const void* pred, const void* gt, const void* K, 
                "pd_sup_loss_bwd: bad arguments");
     PD_REQUIRE(!with_normals || K, "pd_sup_loss_bwd: the normals term needs K");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = lgrid((long)N * H * W);
+    const unsigned grid = pd::flat_grid((long)N * H * W);
     const bool two_pass = two_pass_form != 0;                          // the form with the [N,H,W,6] intermediate (tests compare the two)
     if (with_normals && !two_pass) {
         const int tiles_h = (H + SB_TR - 1) / SB_TR, tiles_w = (W + SB_TW - 1) / SB_TW;
@@ -1025,7 +1005,7 @@ extern "C" int pd_smooth_fwd(const void* disp, const void* img, void* mean, void
     PD_REQUIRE(disp && img && partial && N > 0 && h > 1 && w > 1, "pd_smooth_fwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if (mean) hipLaunchKernelGGL(image_mean_kernel, dim3(N), dim3(1024), 0, st, (const float*)disp, (float*)mean, h * w);
-    hipLaunchKernelGGL(smooth_fwd_kernel, dim3(lgrid((long)N * h * w)), dim3(LT), 0, st, (const float*)disp,
+    hipLaunchKernelGGL(smooth_fwd_kernel, dim3(pd::flat_grid((long)N * h * w)), dim3(LT), 0, st, (const float*)disp,
                        (const float*)img, (const float*)mean, (float*)partial, (float2*)edge_w, N, h, w);
     return pd::check_launch("pd_smooth_fwd");
 }
@@ -1035,7 +1015,7 @@ extern "C" int pd_smooth_bwd(const void* disp, const void* img, const void* mean
     PD_REQUIRE(disp && img && wts && g_ws && gd_acc && gdisp && N > 0 && h > 1 && w > 1, "pd_smooth_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(gd_acc, 0, sizeof(double) * N, st) != hipSuccess) return pd::fail(PD_ELAUNCH, "pd_smooth_bwd: memset");
-    const unsigned grid = lgrid((long)N * h * w);
+    const unsigned grid = pd::flat_grid((long)N * h * w);
     hipLaunchKernelGGL(smooth_bwd_g_kernel, dim3(grid), dim3(LT), 0, st, (const float*)disp, (const float*)img,
                        (const float*)mean, (const float*)wts, (const float2*)edge_w, (float*)g_ws, (double*)gd_acc, N, h, w);
     hipLaunchKernelGGL(smooth_bwd_final_kernel, dim3(grid), dim3(LT), 0, st, (const float*)g_ws, (const float*)mean,
@@ -1049,7 +1029,7 @@ static int ms_fill(MsArgs& a, const void* const* disps, const void* const* color
     PD_REQUIRE(S > 0 && S <= 8 && N > 0 && H > 0 && W > 0 && disps && depths && hs && ws, "pd_multiscale_loss: bad arguments");
     a = MsArgs{};
     a.S = S; a.N = N; a.H = H; a.W = W;
-    a.nb_full = lgrid((long)N * H * W);
+    a.nb_full = pd::flat_grid((long)N * H * W);
     for (int s = 0; s < S; ++s) {
         PD_REQUIRE(disps[s] && depths[s] && hs[s] > 1 && ws[s] > 1 && H % hs[s] == 0 && W % ws[s] == 0 && H / hs[s] == W / ws[s] &&
                        (H / hs[s] == 1 || H / hs[s] == 2 || H / hs[s] == 4 || H / hs[s] == 8),
@@ -1058,7 +1038,7 @@ static int ms_fill(MsArgs& a, const void* const* disps, const void* const* color
         a.depth[s] = (float*)depths[s]; a.mean[s] = means ? (float*)means[s] : nullptr;
         a.edge[s] = edge_ws ? (float2*)edge_ws[s] : nullptr;
         a.hs[s] = hs[s]; a.ws[s] = ws[s];
-        a.nb_s[s] = lgrid((long)N * hs[s] * ws[s]);
+        a.nb_s[s] = pd::flat_grid((long)N * hs[s] * ws[s]);
     }
     return PD_OK;
 }
@@ -1346,7 +1326,7 @@ extern "C" int pd_ssim_fwd(const void* x, const void* y, void* out, int N, int C
                            void* stream) {
     PD_REQUIRE(x && y && out && N >= 0 && C > 0 && H >= 2 && W >= 2 && (mode == 0 || mode == 1), "pd_ssim_fwd: bad arguments");
     if (N == 0) return PD_OK;
-    hipLaunchKernelGGL(ssim_kernel, dim3(lgrid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream, (const float*)x,
+    hipLaunchKernelGGL(ssim_kernel, dim3(pd::flat_grid((long)N * H * W)), dim3(LT), 0, (hipStream_t)stream, (const float*)x,
                        (const float*)y, (float*)out, N, C, H, W, mode, no_ssim);
     return pd::check_launch("pd_ssim_fwd");
 }
@@ -1355,7 +1335,7 @@ extern "C" int pd_ssim_bwd(const void* x, const void* y, const void* gout, void*
                            int W, int mode, int no_ssim, void* stream) {
     PD_REQUIRE(x && y && gout && coef_ws && gx && N > 0 && C > 0 && H > 1 && W > 1, "pd_ssim_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = lgrid((long)N * C * H * W);
+    const unsigned grid = pd::flat_grid((long)N * C * H * W);
     if (!no_ssim)
         hipLaunchKernelGGL(ssim_bwd_a_kernel, dim3(grid), dim3(LT), 0, st, (const float*)x, (const float*)y, (const float*)gout,
                            (float*)coef_ws, N, C, H, W, mode);

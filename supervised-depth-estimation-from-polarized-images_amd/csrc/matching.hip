@@ -10,7 +10,8 @@
 // C-float taps, read where the edge mask is 1 and nowhere else, and the per-pixel finish needs that pixel's D sums only.
 //
 // One workgroup (256 threads) owns MP = 8 consecutive pixels of one batch item (blockIdx.y) and ALL their bins:
-//   phase A  one lane per (pixel, bin): the fp64 projection and the edge mask of the frame -> LDS (u, v), u = -1 where masked
+//   phase A  one lane per (pixel, bin): the fp64 projection (view_geom.hpp, the expressions csrc/reproj.hip warps with) and
+//            the edge mask of the frame -> LDS (u, v), u = -1 where masked
 //   phase B  a wavefront owns a pixel (pixels w and w + 4 in turn), its four 16-lane rows take bins d = row, row + 4, ...:
 //            lane l of a row holds channels 4l..4l+3 (+64k) of the pixel's `cur` in registers across all bins and frames, a tap
 //            is one 16-byte load per lane (256 B per row at C = 64), the L1 distance is summed per lane and by a 4-step
@@ -18,6 +19,7 @@
 //   finish   32 lanes per pixel: c = s / (n + 1e-7), maximum, count of c > 0, first minimum, stores.
 // No atomics, no second launch, no inline assembly; nothing but `cost`, `missing` and three maps is written.
 #include "pd_common.h"
+#include "view_geom.hpp"
 
 namespace {
 
@@ -51,21 +53,17 @@ __device__ __forceinline__ float row_sum16(float v) {
     return v;
 }
 
-__device__ __forceinline__ float l1_4(float4 a, float4 b, float4 c, float4 d, float w00, float w10, float w01, float w11,
-                                      float4 cur, float acc) {
-    const float wx = ((a.x * w00 + b.x * w10) + c.x * w01) + d.x * w11;
-    const float wy = ((a.y * w00 + b.y * w10) + c.y * w01) + d.y * w11;
-    const float wz = ((a.z * w00 + b.z * w10) + c.z * w01) + d.z * w11;
-    const float ww = ((a.w * w00 + b.w * w10) + c.w * w01) + d.w * w11;
-    acc += fabsf(wx - cur.x);
-    acc += fabsf(wy - cur.y);
-    acc += fabsf(wz - cur.z);
-    acc += fabsf(ww - cur.w);
+__device__ __forceinline__ float l1_4(float4 a, float4 b, float4 c, float4 d, const pd_geom::Bilinear& bl, float4 cur,
+                                      float acc) {
+    acc += fabsf(bl.blend(a.x, b.x, c.x, d.x) - cur.x);
+    acc += fabsf(bl.blend(a.y, b.y, c.y, d.y) - cur.y);
+    acc += fabsf(bl.blend(a.z, b.z, c.z, d.z) - cur.z);
+    acc += fabsf(bl.blend(a.w, b.w, c.w, d.w) - cur.w);
     return acc;
 }
 
 __global__ __launch_bounds__(MT) void cost_volume_kernel(const MatchArgs a) {
-    __shared__ double sP[MF * 12];     // (K T)[:3,:] of every frame, row-major 3x4
+    __shared__ double sP[MF][12];      // (K T)[:3,:] of every frame, row-major 3x4
     __shared__ double sIK[9];          // inv_K[:3,:3]
     __shared__ float sValid[MF];
     __shared__ float sBins[MD];
@@ -81,14 +79,10 @@ __global__ __launch_bounds__(MT) void cost_volume_kernel(const MatchArgs a) {
     const int E = MP * D;
 
     if (t < 12 * F) {
-        const int f = t / 12, q = t - 12 * f, i = q >> 2, j = q & 3;
-        const float* k = a.K + b * 16 + i * 4;
-        const float* c = a.T + (b * F + f) * 16 + j;
-        sP[t] = (((double)k[0] * (double)c[0] + (double)k[1] * (double)c[4]) + (double)k[2] * (double)c[8]) +
-                (double)k[3] * (double)c[12];
+        const int f = t / 12, q = t - 12 * f;
+        sP[f][q] = pd_geom::cam_P(a.K + b * 16, a.T + (b * F + f) * 16, q);
     } else if (t >= 128 && t < 137) {
-        const int q = t - 128;
-        sIK[q] = (double)a.iK[b * 16 + (q / 3) * 4 + q % 3];
+        sIK[t - 128] = pd_geom::cam_iK(a.iK, b, t - 128);
     } else if (t >= 160 && t < 160 + F) {
         sValid[t - 160] = a.valid ? a.valid[b * F + (t - 160)] : 1.f;
     }
@@ -103,7 +97,6 @@ __global__ __launch_bounds__(MT) void cost_volume_kernel(const MatchArgs a) {
     for (int f = 0; f < F; ++f) {
         if (sValid[f] == 0.f) continue;                       // the same for the whole workgroup
         // ---- phase A: project every (pixel, bin) of this frame
-        const double* P = sP + 12 * f;
         for (int e = t; e < E; e += MT) {
             const int pl = e / D, d = e - pl * D;
             const int pix = pix0 + pl;
@@ -111,16 +104,10 @@ __global__ __launch_bounds__(MT) void cost_volume_kernel(const MatchArgs a) {
             if (pix < HW) {
                 const int y = pix / w, x = pix - y * w;
                 if (x >= 2 && x < w - 2 && y >= 2 && y < h - 2) {
-                    const double xd = (double)x, yd = (double)y, dep = (double)sBins[d];
-                    double r[3], hh[3];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) r[i] = (sIK[3 * i] * xd + sIK[3 * i + 1] * yd) + sIK[3 * i + 2];
-                    const double p0 = dep * r[0], p1 = dep * r[1], p2 = dep * r[2];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        hh[i] = ((P[4 * i] * p0 + P[4 * i + 1] * p1) + P[4 * i + 2] * p2) + P[4 * i + 3];
-                    const double hz = hh[2] + 1e-7;
-                    const float uf = (float)(hh[0] / hz), vf = (float)(hh[1] / hz);
+                    double r[3], q[3], p[3], u, v, hz;
+                    pd_geom::ray(sIK, x, y, r);
+                    pd_geom::project_ray(sP[f], r, (double)sBins[d], u, v, hz, q, p);
+                    const float uf = (float)u, vf = (float)v;
                     if (uf >= 2.f && uf <= xhi && vf >= 2.f && vf <= yhi) uv = make_float2(uf, vf);   // false for NaN
                 }
             }
@@ -140,9 +127,7 @@ __global__ __launch_bounds__(MT) void cost_volume_kernel(const MatchArgs a) {
                 const float2 uv = sUV[e];
                 if (uv.x < 0.f) continue;                     // (pixel, bin) granularity: the 16 lanes of a row agree
                 const float fx = floorf(uv.x), fy = floorf(uv.y);
-                const float wx1 = uv.x - fx, wy1 = uv.y - fy;
-                const float wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-                const float w00 = wx0 * wy0, w10 = wx1 * wy0, w01 = wx0 * wy1, w11 = wx1 * wy1;
+                const pd_geom::Bilinear bl(uv.x - fx, uv.y - fy);
                 // 2 <= u <= w-2 and 2 <= v <= h-2: all four taps are inside the image
                 const float* s00 = src + ((long)(int)fy * w + (int)fx) * C;
                 const float* s01 = s00 + (long)w * C;
@@ -150,11 +135,11 @@ __global__ __launch_bounds__(MT) void cost_volume_kernel(const MatchArgs a) {
                 if (sub < C4)
                     acc = l1_4(*reinterpret_cast<const float4*>(s00 + 4 * sub), *reinterpret_cast<const float4*>(s00 + C + 4 * sub),
                                *reinterpret_cast<const float4*>(s01 + 4 * sub), *reinterpret_cast<const float4*>(s01 + C + 4 * sub),
-                               w00, w10, w01, w11, cur0, acc);
+                               bl, cur0, acc);
                 for (int q = sub + 16; q < C4; q += 16)
                     acc = l1_4(*reinterpret_cast<const float4*>(s00 + 4 * q), *reinterpret_cast<const float4*>(s00 + C + 4 * q),
                                *reinterpret_cast<const float4*>(s01 + 4 * q), *reinterpret_cast<const float4*>(s01 + C + 4 * q),
-                               w00, w10, w01, w11, *reinterpret_cast<const float4*>(cp + 4 * q), acc);
+                               bl, *reinterpret_cast<const float4*>(cp + 4 * q), acc);
                 const float diff = row_sum16(acc) / (float)C;
                 if (sub == 0) {
                     sSum[e] += diff;

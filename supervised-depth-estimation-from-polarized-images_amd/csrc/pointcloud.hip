@@ -15,6 +15,7 @@
 //                        `unmatched`.  The bin of a distance is the number of table entries edges2[j] <= d2, by a nine-step
 //                        binary search over a copy of the caller's 511 floats in LDS.
 #include "class_records.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -98,11 +99,7 @@ __global__ __launch_bounds__(kThreads) void backproject_kernel(const float* __re
     }
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
+using pd_wave::wave_max;
 
 // every w = 1 target of one tile against the four queries of each lane; tp is wave-uniform
 __device__ __forceinline__ void scan_tile(const float4* __restrict__ tp, const float (&qx)[4], const float (&qy)[4],

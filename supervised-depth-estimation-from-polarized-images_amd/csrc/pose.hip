@@ -10,6 +10,7 @@
 // the plane per channel first and multiplies a [Co, Cin] matrix with ONE vector.  Everything is fp64 inside from the fp32
 // inputs and rounded once; every sum has a stated order; no atomics, no host synchronisation, capturable.
 #include "pd_common.h"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -117,11 +118,7 @@ __global__ __launch_bounds__(64) void pose_matrix_bwd_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------ decoder tail, one workgroup per item
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+using pd_wave::wave_sum;
 
 // mean[c]: thread t owns channels t, t + 256, ...; pixels ascending, then / (h w).  A wavefront reads 64 consecutive
 // channels of one pixel: coalesced.  o[k]: wavefront k % 4 takes output k; lane l sums w[k][c] mean[c] over c = l, l + 64,
@@ -272,7 +269,7 @@ extern "C" int pd_pose_head_fwd(const void* x, const void* w, const void* b, voi
     if (int rc = pose_head_args("pd_pose_head_fwd", N, h, wd, Cin, Co, invert)) return rc;
     PD_REQUIRE(x && w && b && axisangle && translation && T && T_inv && mean,
                "pd_pose_head_fwd: x, w, b, axisangle, translation, T, T_inv and mean must not be null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(mean) & 7u) == 0, "pd_pose_head_fwd: mean must be 8-byte aligned");
+    PD_REQUIRE(pd::aligned8(mean), "pd_pose_head_fwd: mean must be 8-byte aligned");
     if (N == 0) return PD_OK;
     hipLaunchKernelGGL(pose_head_fwd_kernel, dim3(N), dim3(PT), 0, (hipStream_t)stream, (const float*)x, (const float*)w,
                        (const float*)b, (float*)axisangle, (float*)translation, (float*)T, (float*)T_inv, (double*)mean, h * wd,
@@ -287,7 +284,7 @@ extern "C" int pd_pose_head_bwd(const void* gT, const void* gT_inv, const void* 
     if (int rc = pose_head_args("pd_pose_head_bwd", N, h, wd, Cin, Co, invert)) return rc;
     PD_REQUIRE(axisangle && translation && w && mean && gx && gw && gb && gpre_ws,
                "pd_pose_head_bwd: axisangle, translation, w, mean, gx, gw, gb and gpre_ws must not be null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(mean) & 7u) == 0 && (reinterpret_cast<uintptr_t>(gpre_ws) & 7u) == 0,
+    PD_REQUIRE(pd::aligned8(mean) && pd::aligned8(gpre_ws),
                "pd_pose_head_bwd: mean and gpre_ws must be 8-byte aligned");
     PD_REQUIRE(accumulate == 0 || accumulate == 1, "pd_pose_head_bwd: accumulate must be 0 or 1, got %d", accumulate);
     if (N == 0) return PD_OK;

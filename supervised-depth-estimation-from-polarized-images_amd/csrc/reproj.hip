@@ -10,6 +10,9 @@
 // With align_corners=True the division by W-1 / H-1, the (. - 0.5) * 2 of Project3D and grid_sample's own
 // un-normalisation cancel: (u, v) ARE source pixel coordinates, and that is what `coords` holds.
 //
+// The projection (steps in fp64, their order of operations) and the border rule of a tap are in view_geom.hpp, which
+// csrc/matching.hip shares.
+//
 // Gather / stream kernels.  blockIdx.y is the batch item, so K, inv_K and T are the same for a whole workgroup: the first
 // 12 + 9 threads form (K T)[:3,:] and inv_K[:3,:3] in fp64 into LDS once, every pixel reads them back as broadcasts.
 // Depth reads and warped / coords / gdepth writes are coalesced (thread = pixel, x fastest); the four taps of a pixel
@@ -19,80 +22,14 @@
 // fp64 in the fixed order of frame_reduce.hpp (rows per item, then one finalising workgroup per item that applies K^T).
 #include "pd_common.h"
 #include "frame_reduce.hpp"
+#include "view_geom.hpp"
 
 namespace {
 
+using pd_geom::Axis;
+using pd_geom::axis_of;
+using pd_geom::CamLds;
 constexpr int RT = pd_frames::RT;
-constexpr int RP_MAX_FRAMES = pd_frames::MAX_FRAMES;   // = PD_REPROJ_MAX_FRAMES
-
-// ------------------------------------------------------------------ camera of one batch item, in LDS
-struct CamLds {
-    double P[12];   // (K T)[:3,:], row-major 3x4
-    double iK[9];   // inv_K[:3,:3]
-};
-
-__device__ __forceinline__ void load_cam(CamLds& cam, const float* __restrict__ K, const float* __restrict__ iK,
-                                         const float* __restrict__ T, long n) {
-    const int t = threadIdx.x;
-    if (t < 12) {
-        const int i = t >> 2, j = t & 3;
-        const float* k = K + n * 16 + i * 4;
-        const float* c = T + n * 16 + j;
-        // k ascending, plain multiply-adds (the file is built with -ffp-contract=off)
-        cam.P[t] = (((double)k[0] * (double)c[0] + (double)k[1] * (double)c[4]) + (double)k[2] * (double)c[8]) +
-                   (double)k[3] * (double)c[12];
-    } else if (t < 21) {
-        const int q = t - 12;
-        cam.iK[q] = (double)iK[n * 16 + (q / 3) * 4 + q % 3];
-    }
-    __syncthreads();
-}
-
-// steps 1-4 of the header in fp64; q = A r is returned for the backward pass (h = depth * q + b)
-// p = depth * r, the camera point, is returned as well: the pose gradient needs it
-__device__ __forceinline__ void project(const CamLds& cam, int x, int y, double d, double& u, double& v, double& hz,
-                                        double (&q)[3], double (&p)[3]) {
-    const double xd = (double)x, yd = (double)y;
-    double r[3], h[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) r[i] = (cam.iK[3 * i] * xd + cam.iK[3 * i + 1] * yd) + cam.iK[3 * i + 2];
-    const double p0 = d * r[0], p1 = d * r[1], p2 = d * r[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        h[i] = ((cam.P[4 * i] * p0 + cam.P[4 * i + 1] * p1) + cam.P[4 * i + 2] * p2) + cam.P[4 * i + 3];
-        q[i] = (cam.P[4 * i] * r[0] + cam.P[4 * i + 1] * r[1]) + cam.P[4 * i + 2] * r[2];
-    }
-    hz = h[2] + 1e-7;
-    u = h[0] / hz;
-    v = h[1] / hz;
-    p[0] = p0; p[1] = p1; p[2] = p2;
-}
-__device__ __forceinline__ void project(const CamLds& cam, int x, int y, double d, double& u, double& v, double& hz,
-                                        double (&q)[3]) {
-    double p[3];
-    project(cam, x, y, d, u, v, hz, q, p);
-}
-
-// border padding of one axis: the clamped coordinate, its cell and the weight of the upper tap; `free_axis` is false where
-// the coordinate was clamped (PyTorch's rule: c <= 0 or c >= size-1) or is not finite -- the gradient is then exactly zero
-struct Axis {
-    int i0, i1;
-    float w1;
-    bool free_axis;
-};
-__device__ __forceinline__ Axis axis_of(float c, int size) {
-    Axis a;
-    const float hi = (float)(size - 1);
-    a.free_axis = (c > 0.f) && (c < hi);          // false for NaN and both infinities as well
-    float cc = c;
-    if (!(fabsf(c) <= 3.0e38f)) cc = 0.f;         // non-finite -> 0
-    cc = fminf(fmaxf(cc, 0.f), hi);
-    const float f = floorf(cc);
-    a.i0 = (int)f;
-    a.i1 = a.i0 + (a.i0 < size - 1);              // cc == size-1: the upper tap has weight 0, keep it in bounds
-    a.w1 = cc - f;
-    return a;
-}
 
 __global__ __launch_bounds__(RT) void view_synth_fwd_kernel(const float* __restrict__ depth, const float* __restrict__ src,
                                                             const float* __restrict__ K, const float* __restrict__ iK,
@@ -100,34 +37,36 @@ __global__ __launch_bounds__(RT) void view_synth_fwd_kernel(const float* __restr
                                                             float2* __restrict__ coords, int C, int H, int W) {
     __shared__ CamLds cam;
     const long n = blockIdx.y;
-    load_cam(cam, K, iK, T, n);
+    pd_geom::load_cam(cam, K, iK, T, n);
     const int HW = H * W;
     const float* s = src + n * C * (long)HW;
     for (int i = blockIdx.x * RT + threadIdx.x; i < HW; i += gridDim.x * RT) {
         const int y = i / W, x = i - y * W;
-        double u, v, hz, q[3];
-        project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q);
+        double u, v, hz, q[3], p[3];
+        pd_geom::project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q, p);
         const float uf = (float)u, vf = (float)v;
         coords[n * HW + i] = make_float2(uf, vf);
         const Axis ax = axis_of(uf, W), ay = axis_of(vf, H);
-        const float wx0 = 1.f - ax.w1, wy0 = 1.f - ay.w1;
-        const float w00 = wx0 * wy0, w10 = ax.w1 * wy0, w01 = wx0 * ay.w1, w11 = ax.w1 * ay.w1;
+        const pd_geom::Bilinear b(ax.w1, ay.w1);
         const int o00 = ay.i0 * W + ax.i0, o10 = ay.i0 * W + ax.i1, o01 = ay.i1 * W + ax.i0, o11 = ay.i1 * W + ax.i1;
         for (int c = 0; c < C; ++c) {
             const float* pc = s + (long)c * HW;
-            warped[(n * C + c) * (long)HW + i] = ((pc[o00] * w00 + pc[o10] * w10) + pc[o01] * w01) + pc[o11] * w11;
+            warped[(n * C + c) * (long)HW + i] = b.blend(pc[o00], pc[o10], pc[o01], pc[o11]);
         }
     }
 }
 
-__global__ __launch_bounds__(RT) void view_synth_bwd_kernel(const float* __restrict__ gw, const float* __restrict__ src,
-                                                            const float2* __restrict__ coords, const float* __restrict__ depth,
-                                                            const float* __restrict__ K, const float* __restrict__ iK,
-                                                            const float* __restrict__ T, float* __restrict__ gdepth, int C,
-                                                            int H, int W, int accumulate) {
+// The backward warp of item blockIdx.y: gdepth of every pixel and, with POSE, that thread's part of the 12 sums of
+// d loss / d P in `acc`.  Both kernels below are this body, so the pose form's gdepth has the bits of the plain form's.
+template <bool POSE>
+__device__ __forceinline__ void view_synth_bwd_item(const float* __restrict__ gw, const float* __restrict__ src,
+                                                    const float2* __restrict__ coords, const float* __restrict__ depth,
+                                                    const float* __restrict__ K, const float* __restrict__ iK,
+                                                    const float* __restrict__ T, float* __restrict__ gdepth, int C, int H,
+                                                    int W, int accumulate, double (&acc)[POSE ? 12 : 1]) {
     __shared__ CamLds cam;
     const long n = blockIdx.y;
-    load_cam(cam, K, iK, T, n);
+    pd_geom::load_cam(cam, K, iK, T, n);
     const int HW = H * W;
     const float* s = src + n * C * (long)HW;
     for (int i = blockIdx.x * RT + threadIdx.x; i < HW; i += gridDim.x * RT) {
@@ -146,73 +85,53 @@ __global__ __launch_bounds__(RT) void view_synth_bwd_kernel(const float* __restr
                 gu += gc * ((v10 - v00) * wy0 + (v11 - v01) * ay.w1);
                 gv += gc * ((v01 - v00) * wx0 + (v11 - v10) * ax.w1);
             }
-            double u, v, hz, q[3];
-            project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q);
+            double u, v, hz, q[3], p[3];
+            pd_geom::project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q, p);
             // h = depth * q + b:  d u / d depth = (q.x - u q.z) / (h.z + 1e-7), likewise v
             const double du = ax.free_axis ? (q[0] - u * q[2]) / hz : 0.0;
             const double dv = ay.free_axis ? (q[1] - v * q[2]) / hz : 0.0;
             g = (float)((double)gu * du + (double)gv * dv);
+            if constexpr (POSE) {
+                // d loss / d h = (a0, a1, a2); h = P (p, 1).  A clamped axis adds nothing (never 0 * inf)
+                double a2 = 0.0;
+                if (ax.free_axis) {
+                    const double a0 = (double)gu / hz;
+                    acc[0] += a0 * p[0]; acc[1] += a0 * p[1]; acc[2] += a0 * p[2]; acc[3] += a0;
+                    a2 = a0 * u;
+                }
+                if (ay.free_axis) {
+                    const double a1 = (double)gv / hz;
+                    acc[4] += a1 * p[0]; acc[5] += a1 * p[1]; acc[6] += a1 * p[2]; acc[7] += a1;
+                    a2 = a2 + a1 * v;
+                }
+                a2 = -a2;
+                acc[8] += a2 * p[0]; acc[9] += a2 * p[1]; acc[10] += a2 * p[2]; acc[11] += a2;
+            }
         }
-        gdepth[n * HW + i] = accumulate ? gdepth[n * HW + i] + g : g;
+        if (!POSE || gdepth) gdepth[n * HW + i] = accumulate ? gdepth[n * HW + i] + g : g;
     }
 }
 
-// view_synth_bwd_kernel's gdepth (same expressions, hence the same bits) and, from the same taps, the 12 sums of
-// d loss / d P per item: one row of 12 doubles per workgroup (frame_reduce.hpp), gridDim.x rows per item
+__global__ __launch_bounds__(RT) void view_synth_bwd_kernel(const float* __restrict__ gw, const float* __restrict__ src,
+                                                            const float2* __restrict__ coords, const float* __restrict__ depth,
+                                                            const float* __restrict__ K, const float* __restrict__ iK,
+                                                            const float* __restrict__ T, float* __restrict__ gdepth, int C,
+                                                            int H, int W, int accumulate) {
+    double none[1];
+    view_synth_bwd_item<false>(gw, src, coords, depth, K, iK, T, gdepth, C, H, W, accumulate, none);
+}
+
+// one row of 12 doubles per workgroup (frame_reduce.hpp), gridDim.x rows per item; gdepth may be null
 __global__ __launch_bounds__(RT) void view_synth_bwd_pose_kernel(const float* __restrict__ gw, const float* __restrict__ src,
                                                                  const float2* __restrict__ coords,
                                                                  const float* __restrict__ depth, const float* __restrict__ K,
                                                                  const float* __restrict__ iK, const float* __restrict__ T,
                                                                  float* __restrict__ gdepth, double* __restrict__ partial,
                                                                  int C, int H, int W, int accumulate) {
-    __shared__ CamLds cam;
     __shared__ double sm[4 * 12];
-    const long n = blockIdx.y;
-    load_cam(cam, K, iK, T, n);
-    const int HW = H * W;
-    const float* s = src + n * C * (long)HW;
-    double acc[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) acc[k] = 0.0;
-    for (int i = blockIdx.x * RT + threadIdx.x; i < HW; i += gridDim.x * RT) {
-        const int y = i / W, x = i - y * W;
-        const float2 uv = coords[n * HW + i];
-        const Axis ax = axis_of(uv.x, W), ay = axis_of(uv.y, H);
-        float g = 0.f;
-        if (ax.free_axis || ay.free_axis) {
-            const float wx0 = 1.f - ax.w1, wy0 = 1.f - ay.w1;
-            const int o00 = ay.i0 * W + ax.i0, o10 = ay.i0 * W + ax.i1, o01 = ay.i1 * W + ax.i0, o11 = ay.i1 * W + ax.i1;
-            float gu = 0.f, gv = 0.f;
-            for (int c = 0; c < C; ++c) {
-                const float* pc = s + (long)c * HW;
-                const float v00 = pc[o00], v10 = pc[o10], v01 = pc[o01], v11 = pc[o11];
-                const float gc = gw[(n * C + c) * (long)HW + i];
-                gu += gc * ((v10 - v00) * wy0 + (v11 - v01) * ay.w1);
-                gv += gc * ((v01 - v00) * wx0 + (v11 - v10) * ax.w1);
-            }
-            double u, v, hz, q[3], p[3];
-            project(cam, x, y, (double)depth[n * HW + i], u, v, hz, q, p);
-            const double du = ax.free_axis ? (q[0] - u * q[2]) / hz : 0.0;
-            const double dv = ay.free_axis ? (q[1] - v * q[2]) / hz : 0.0;
-            g = (float)((double)gu * du + (double)gv * dv);
-            // d loss / d h = (a0, a1, a2); h = P (p, 1).  A clamped axis adds nothing (never 0 * inf)
-            double a2 = 0.0;
-            if (ax.free_axis) {
-                const double a0 = (double)gu / hz;
-                acc[0] += a0 * p[0]; acc[1] += a0 * p[1]; acc[2] += a0 * p[2]; acc[3] += a0;
-                a2 = a0 * u;
-            }
-            if (ay.free_axis) {
-                const double a1 = (double)gv / hz;
-                acc[4] += a1 * p[0]; acc[5] += a1 * p[1]; acc[6] += a1 * p[2]; acc[7] += a1;
-                a2 = a2 + a1 * v;
-            }
-            a2 = -a2;
-            acc[8] += a2 * p[0]; acc[9] += a2 * p[1]; acc[10] += a2 * p[2]; acc[11] += a2;
-        }
-        if (gdepth) gdepth[n * HW + i] = accumulate ? gdepth[n * HW + i] + g : g;
-    }
-    pd_frames::block_rows<12>(acc, sm, partial + n * (long)gridDim.x * 12);
+    double acc[12] = {};
+    view_synth_bwd_item<true>(gw, src, coords, depth, K, iK, T, gdepth, C, H, W, accumulate, acc);
+    pd_frames::block_rows<12>(acc, sm, partial + blockIdx.y * (long)gridDim.x * 12);
 }
 
 // one workgroup per item: the rows of that item in the order of finalize_rows, then gT = K[:3,:]^T gP, rounded once
@@ -251,7 +170,6 @@ __global__ __launch_bounds__(RT) void depth_to_updisp_bwd_kernel(const float* __
 // FrameArgs, over_frames and the two-stage fp64 reducer live in frame_reduce.hpp (csrc/student.hip shares them)
 using pd_frames::FrameArgs;
 using pd_frames::over_frames;
-using pd_frames::rgrid;
 
 __global__ __launch_bounds__(RT) void combine_fwd_kernel(const FrameArgs a, int F, int has_identity,
                                                          const float* __restrict__ noise, const float* __restrict__ valid,
@@ -310,14 +228,6 @@ __global__ __launch_bounds__(RT) void combine_bwd_kernel(const FrameArgs a, int 
     }
 }
 
-// blocks along x for a per-item grid (blockIdx.y = item): about 4096 workgroups in all, the rest by grid stride
-inline unsigned item_grid(int N, long HW) {
-    long b = (HW + RT - 1) / RT;
-    const long cap = N >= 4096 ? 1 : 4096 / N;
-    if (b > cap) b = cap;
-    return (unsigned)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 // ============================================================================ C ABI
@@ -333,9 +243,9 @@ extern "C" int pd_view_synth_fwd(const void* depth, const void* src, const void*
                                  void* warped, void* coords, int N, int C, int H, int W, void* stream) {
     if (int rc = view_synth_args("pd_view_synth_fwd", depth, src, K, inv_K, T, N, C, H, W)) return rc;
     PD_REQUIRE(warped && coords, "pd_view_synth_fwd: warped and coords must not be null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(coords) & 7u) == 0, "pd_view_synth_fwd: coords must be 8-byte aligned");
+    PD_REQUIRE(pd::aligned8(coords), "pd_view_synth_fwd: coords must be 8-byte aligned");
     if (N == 0) return PD_OK;
-    hipLaunchKernelGGL(view_synth_fwd_kernel, dim3(item_grid(N, (long)H * W), N), dim3(RT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(view_synth_fwd_kernel, dim3(pd::item_grid(N, (long)H * W), N), dim3(RT), 0, (hipStream_t)stream,
                        (const float*)depth, (const float*)src, (const float*)K, (const float*)inv_K, (const float*)T,
                        (float*)warped, (float2*)coords, C, H, W);
     return pd::check_launch("pd_view_synth_fwd");
@@ -346,9 +256,9 @@ extern "C" int pd_view_synth_bwd(const void* gwarped, const void* src, const voi
                                  void* stream) {
     if (int rc = view_synth_args("pd_view_synth_bwd", depth, src, K, inv_K, T, N, C, H, W)) return rc;
     PD_REQUIRE(gwarped && coords && gdepth, "pd_view_synth_bwd: gwarped, coords and gdepth must not be null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(coords) & 7u) == 0, "pd_view_synth_bwd: coords must be 8-byte aligned");
+    PD_REQUIRE(pd::aligned8(coords), "pd_view_synth_bwd: coords must be 8-byte aligned");
     if (N == 0) return PD_OK;
-    hipLaunchKernelGGL(view_synth_bwd_kernel, dim3(item_grid(N, (long)H * W), N), dim3(RT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(view_synth_bwd_kernel, dim3(pd::item_grid(N, (long)H * W), N), dim3(RT), 0, (hipStream_t)stream,
                        (const float*)gwarped, (const float*)src, (const float2*)coords, (const float*)depth, (const float*)K,
                        (const float*)inv_K, (const float*)T, (float*)gdepth, C, H, W, accumulate);
     return pd::check_launch("pd_view_synth_bwd");
@@ -367,8 +277,7 @@ extern "C" int pd_view_synth_bwd_pose(const void* gwarped, const void* src, cons
     if (int rc = view_synth_args("pd_view_synth_bwd_pose", depth, src, K, inv_K, T, N, C, H, W)) return rc;
     PD_REQUIRE(gwarped && coords && partial_ws && gT,
                "pd_view_synth_bwd_pose: gwarped, coords, partial_ws and gT must not be null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(coords) & 7u) == 0 && (reinterpret_cast<uintptr_t>(partial_ws) & 7u) == 0 &&
-                   (reinterpret_cast<uintptr_t>(gP) & 7u) == 0,
+    PD_REQUIRE(pd::aligned8(coords) && pd::aligned8(partial_ws) && pd::aligned8(gP),
                "pd_view_synth_bwd_pose: coords, partial_ws and gP must be 8-byte aligned");
     if (N == 0) return PD_OK;
     const int rows = pd_view_synth_pose_rows(H, W);
@@ -387,33 +296,24 @@ extern "C" int pd_depth_to_updisp_bwd(const void* gdepth, const void* depth, voi
     PD_REQUIRE(n >= 0, "pd_depth_to_updisp_bwd: bad element count %ld", n);
     PD_REQUIRE(min_depth > 0 && max_depth > min_depth, "pd_depth_to_updisp_bwd: bad depth range");
     if (n == 0) return PD_OK;
-    hipLaunchKernelGGL(depth_to_updisp_bwd_kernel, dim3(rgrid(n)), dim3(RT), 0, (hipStream_t)stream, (const float*)gdepth,
-                       (const float*)depth, (float*)gup, n, 1.f / min_depth - 1.f / max_depth);
+    hipLaunchKernelGGL(depth_to_updisp_bwd_kernel, dim3(pd::flat_grid(n)), dim3(RT), 0, (hipStream_t)stream,
+                       (const float*)gdepth, (const float*)depth, (float*)gup, n, 1.f / min_depth - 1.f / max_depth);
     return pd::check_launch("pd_depth_to_updisp_bwd");
 }
 
 extern "C" int pd_reproj_combine_rows(int N, int H, int W) {
     if (N <= 0 || H <= 0 || W <= 0) return 1;
-    return (int)rgrid((long)N * H * W);
-}
-
-static int combine_args(const char* who, int F, int N, int H, int W, int avg) {
-    PD_REQUIRE(F >= 1 && F <= RP_MAX_FRAMES, "%s: 1 <= F <= %d frames, got %d", who, RP_MAX_FRAMES, F);
-    PD_REQUIRE(N >= 0 && H > 0 && W > 0, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
-    PD_REQUIRE((long)H * W <= (1L << 30), "%s: image too large (%d x %d)", who, H, W);
-    PD_REQUIRE(avg == 0 || avg == 1, "%s: avg must be 0 or 1, got %d", who, avg);
-    return PD_OK;
+    return (int)pd::flat_grid((long)N * H * W);
 }
 
 extern "C" int pd_reproj_combine_fwd(const void* const* reproj, const void* const* identity, int F, const void* noise,
                                      const void* valid, void* sel, void* partial_ws, void* sums, void* loss, int N, int H,
                                      int W, int avg, void* stream) {
-    if (int rc = combine_args("pd_reproj_combine_fwd", F, N, H, W, avg)) return rc;
+    if (int rc = pd_frames::combine_args("pd_reproj_combine_fwd", F, N, H, W, avg)) return rc;
     PD_REQUIRE(reproj && sel && partial_ws && sums && loss,
                "pd_reproj_combine_fwd: reproj, sel, partial_ws, sums and loss must not be null");
     PD_REQUIRE(identity || !noise, "pd_reproj_combine_fwd: noise is added to the identity maps, which are null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(partial_ws) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7u) == 0,
-               "pd_reproj_combine_fwd: partial_ws and sums must be 8-byte aligned");
+    PD_REQUIRE(pd::aligned8(partial_ws) && pd::aligned8(sums), "pd_reproj_combine_fwd: partial_ws and sums must be 8-byte aligned");
     FrameArgs a = {};
     for (int f = 0; f < F; ++f) {
         PD_REQUIRE(reproj[f] && (!identity || identity[f]), "pd_reproj_combine_fwd: map %d is null", f);
@@ -432,16 +332,16 @@ extern "C" int pd_reproj_combine_fwd(const void* const* reproj, const void* cons
 
 extern "C" int pd_reproj_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid,
                                      void* const* greproj, int F, int N, int H, int W, int avg, void* stream) {
-    if (int rc = combine_args("pd_reproj_combine_bwd", F, N, H, W, avg)) return rc;
+    if (int rc = pd_frames::combine_args("pd_reproj_combine_bwd", F, N, H, W, avg)) return rc;
     PD_REQUIRE(gloss && sel && sums && greproj, "pd_reproj_combine_bwd: gloss, sel, sums and greproj must not be null");
-    PD_REQUIRE((reinterpret_cast<uintptr_t>(sums) & 7u) == 0, "pd_reproj_combine_bwd: sums must be 8-byte aligned");
+    PD_REQUIRE(pd::aligned8(sums), "pd_reproj_combine_bwd: sums must be 8-byte aligned");
     FrameArgs a = {};
     for (int f = 0; f < F; ++f) {
         PD_REQUIRE(greproj[f], "pd_reproj_combine_bwd: map %d is null", f);
         a.greproj[f] = (float*)greproj[f];
     }
     if (N == 0) return PD_OK;
-    hipLaunchKernelGGL(combine_bwd_kernel, dim3(rgrid((long)N * H * W)), dim3(RT), 0, (hipStream_t)stream, a, F,
-                       (const float*)gloss, (const unsigned char*)sel, (const double*)sums, (const float*)valid, N, H * W, avg);
+    hipLaunchKernelGGL(combine_bwd_kernel, dim3(pd::flat_grid((long)N * H * W)), dim3(RT), 0, (hipStream_t)stream, a,
+                       F, (const float*)gloss, (const unsigned char*)sel, (const double*)sums, (const float*)valid, N, H * W, avg);
     return pd::check_launch("pd_reproj_combine_bwd");
 }

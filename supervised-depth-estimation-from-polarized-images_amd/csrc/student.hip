@@ -18,28 +18,12 @@ namespace {
 
 using pd_frames::FrameArgs;
 using pd_frames::OverFrames;
-using pd_frames::rgrid;
+using pd_wave::wave_max;
+using pd_wave::wave_min;
+using pd_wave::wave_or;
 constexpr int RT = pd_frames::RT;
-constexpr int MAX_FRAMES = pd_frames::MAX_FRAMES;
-constexpr int MASK_ROWS_CAP = 4096;   // workgroups of masks_kernel over the whole batch, about
 
 // ------------------------------------------------------------------ pd_student_masks
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_or(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
-
 // minimum / maximum that ignore NaN (fminf / fmaxf) plus a flag: the pair becomes NaN at the end if the flag is set
 struct MinMax {
     float mn = __builtin_inff(), mx = -__builtin_inff();
@@ -129,13 +113,6 @@ __global__ __launch_bounds__(RT) void minmax_finalize_kernel(const float* __rest
     if (threadIdx.x == 0) mm.store(minmax + n * 2);
 }
 
-inline int mask_rows(int N, int h, int w) {
-    if (N <= 0 || h <= 0 || w <= 0) return 1;
-    long b = (4L * h * w + RT - 1) / RT;
-    const long cap = N >= MASK_ROWS_CAP ? 1 : MASK_ROWS_CAP / N;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
 
 // ------------------------------------------------------------------ pd_depth_bins_update
 __global__ __launch_bounds__(128) void bins_update_kernel(const float* __restrict__ minmax, int N, double* __restrict__ tracker,
@@ -268,13 +245,14 @@ __global__ __launch_bounds__(RT) void student_combine_bwd_kernel(const FrameArgs
     }
 }
 
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+using pd::aligned4;
+using pd::aligned8;
 
 }  // namespace
 
 // ============================================================================ C ABI
-extern "C" int pd_student_masks_rows(int N, int h, int w) { return mask_rows(N, h, w); }
+// workgroups per item of masks_kernel: one thread per quad, 4 h w quads per item
+extern "C" int pd_student_masks_rows(int N, int h, int w) { return h <= 0 || w <= 0 ? 1 : (int)pd::item_grid(N, 4L * h * w); }
 
 extern "C" int pd_student_masks(const void* lowest, const void* confidence, const void* mono_depth, const void* aug,
                                 int motion_masking, void* rmask, void* cmask, void* lowest_up, void* minmax, void* partial_ws,
@@ -288,7 +266,7 @@ extern "C" int pd_student_masks(const void* lowest, const void* confidence, cons
     PD_REQUIRE(pd::aligned16(mono_depth) && pd::aligned16(cmask) && pd::aligned16(lowest_up) && aligned4(rmask),
                "pd_student_masks: mono_depth, cmask and lowest_up must be 16-byte aligned, rmask 4-byte");
     if (N == 0) return PD_OK;
-    const int rows = mask_rows(N, h, w);
+    const int rows = pd_student_masks_rows(N, h, w);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(masks_kernel, dim3(rows, N), dim3(RT), 0, st, (const float*)lowest, (const float*)confidence,
                        (const float*)mono_depth, (const float*)aug, motion_masking, (unsigned char*)rmask, (float*)cmask,
@@ -311,22 +289,17 @@ extern "C" int pd_depth_bins_update(const void* minmax, int N, void* tracker, do
 
 extern "C" int pd_student_combine_rows(int N, int H, int W) {
     if (N <= 0 || H <= 0 || W <= 0) return 1;
-    return (int)rgrid((long)N * H * W / 4);
+    return (int)pd::flat_grid((long)N * H * W / 4);
 }
 
-static int student_combine_args(const char* who, int F, int N, int H, int W, int avg) {
-    PD_REQUIRE(F >= 1 && F <= MAX_FRAMES, "%s: 1 <= F <= %d frames, got %d", who, MAX_FRAMES, F);
-    PD_REQUIRE(N >= 0 && H > 0 && W > 0, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
-    PD_REQUIRE(H % 4 == 0 && W % 4 == 0, "%s: H and W must be multiples of 4 (the masks are 4x a quarter-resolution map), got %d x %d", who, H, W);
-    PD_REQUIRE((long)H * W <= (1L << 30), "%s: image too large (%d x %d)", who, H, W);
-    PD_REQUIRE(avg == 0 || avg == 1, "%s: avg must be 0 or 1, got %d", who, avg);
-    return PD_OK;
-}
+// a thread handles a quad, four pixels that are neighbours in x
+static const char* const kQuads = "%s: H and W must be multiples of 4 (the masks are 4x a quarter-resolution map), got %d x %d";
 
 extern "C" int pd_student_combine_fwd(const void* const* reproj, int F, const void* valid, const void* rmask,
                                       const void* multi_depth, const void* mono_depth, void* sel, void* partial_ws, void* sums,
                                       void* loss, int N, int H, int W, int avg, void* stream) {
-    if (int rc = student_combine_args("pd_student_combine_fwd", F, N, H, W, avg)) return rc;
+    if (int rc = pd_frames::combine_args("pd_student_combine_fwd", F, N, H, W, avg)) return rc;
+    PD_REQUIRE(H % 4 == 0 && W % 4 == 0, kQuads, "pd_student_combine_fwd", H, W);
     PD_REQUIRE(reproj && rmask && multi_depth && mono_depth && sel && partial_ws && sums && loss,
                "pd_student_combine_fwd: reproj, rmask, multi_depth, mono_depth, sel, partial_ws, sums and loss must not be null");
     PD_REQUIRE(aligned8(partial_ws) && aligned8(sums), "pd_student_combine_fwd: partial_ws and sums must be 8-byte aligned");
@@ -353,7 +326,8 @@ extern "C" int pd_student_combine_fwd(const void* const* reproj, int F, const vo
 extern "C" int pd_student_combine_bwd(const void* gloss, const void* sel, const void* sums, const void* valid,
                                       const void* multi_depth, const void* mono_depth, void* const* greproj, void* gmulti, int F,
                                       int N, int H, int W, int avg, void* stream) {
-    if (int rc = student_combine_args("pd_student_combine_bwd", F, N, H, W, avg)) return rc;
+    if (int rc = pd_frames::combine_args("pd_student_combine_bwd", F, N, H, W, avg)) return rc;
+    PD_REQUIRE(H % 4 == 0 && W % 4 == 0, kQuads, "pd_student_combine_bwd", H, W);
     PD_REQUIRE(gloss && sel && sums && multi_depth && mono_depth && greproj && gmulti,
                "pd_student_combine_bwd: gloss, sel, sums, multi_depth, mono_depth, greproj and gmulti must not be null");
     PD_REQUIRE(aligned8(sums), "pd_student_combine_bwd: sums must be 8-byte aligned");
@@ -367,7 +341,7 @@ extern "C" int pd_student_combine_bwd(const void* gloss, const void* sel, const 
     if (N == 0) return PD_OK;
     const int qper = H * W / 4;
     const long quads = (long)N * qper;
-    hipLaunchKernelGGL(student_combine_bwd_kernel, dim3(rgrid(quads)), dim3(RT), 0, (hipStream_t)stream, a, F,
+    hipLaunchKernelGGL(student_combine_bwd_kernel, dim3(pd::flat_grid(quads)), dim3(RT), 0, (hipStream_t)stream, a, F,
                        (const float*)gloss, (const unsigned char*)sel, (const double*)sums, (const float*)valid,
                        (const float*)multi_depth, (const float*)mono_depth, (float*)gmulti, quads, qper,
                        (double)N * (double)H * (double)W, avg);

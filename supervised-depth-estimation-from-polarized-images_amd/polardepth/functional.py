@@ -1170,6 +1170,26 @@ class DispDepthFn(torch.autograd.Function):
         return gdisp, None, None, None
 
 
+def _multiview_chain(who, cfg, disps, depths, target, sources, K, inv_K, poses, no_ssim):
+    """What ``photometric_loss`` and ``student_loss`` share: the frame / pose count check and the fp32 contiguous target and
+    sources, and the chain of one scale.  Returns (target, sources, scale); ``scale(i)`` is (d, views, maps): the depth map
+    of scale i on the tape (``DispDepthFn``), every source warped through it (``ops.view_synthesis``) and the reprojection
+    map of every warped frame against the target (``ops.reprojection_loss``)."""
+    sources, poses = list(sources), list(poses)
+    if len(sources) != len(poses) or not sources:
+        raise ValueError(f"{who}: one pose per source frame, at least one frame")
+    target = target.float().contiguous()
+    sources = [s.float().contiguous() for s in sources]
+
+    def scale(i):
+        d = depths[i]
+        if disps is not None and disps[i] is not None:
+            d = DispDepthFn.apply(disps[i], d, cfg.min_depth, cfg.max_depth)
+        views = [ops.view_synthesis(d, s, K, inv_K, T)[0] for s, T in zip(sources, poses)]
+        return d, views, [ops.reprojection_loss(v, target, no_ssim) for v in views]
+    return target, sources, scale
+
+
 def photometric_loss(cfg, disps, depths, target, sources, K, inv_K, poses, valid, noise=None, no_ssim=False, automask=True,
                      avg=False, details=False):
     """monodepth2's photometric reprojection term with known poses (trainer.py:983-1098, 1150-1236 for ``--pose_input``):
@@ -1185,22 +1205,14 @@ def photometric_loss(cfg, disps, depths, target, sources, K, inv_K, poses, valid
     noise    the automask tie-breaker added to the identity value: one [N,1,H,W] map for every scale or a list of one per
              scale (trainer.py:1193-1194 draws one per scale); ignored without automasking
     The identity maps do not depend on the scale: they are evaluated once.  ``details``: also the per-scale ``sel`` maps."""
-    sources, poses = list(sources), list(poses)
-    if len(sources) != len(poses) or not sources:
-        raise ValueError("photometric_loss: one pose per source frame, at least one frame")
-    target = target.float().contiguous()
-    sources = [s.float().contiguous() for s in sources]
+    target, sources, scale = _multiview_chain("photometric_loss", cfg, disps, depths, target, sources, K, inv_K, poses, no_ssim)
     identity = None
     if automask:
         with torch.no_grad():
             identity = [ops.reprojection_loss(s, target, no_ssim) for s in sources]
     losses, sels = [], []
-    for i, depth in enumerate(depths):
-        d = depth
-        if disps is not None and disps[i] is not None:
-            d = DispDepthFn.apply(disps[i], depth, cfg.min_depth, cfg.max_depth)
-        maps = [ops.reprojection_loss(ops.view_synthesis(d, s, K, inv_K, T)[0], target, no_ssim)
-                for s, T in zip(sources, poses)]
+    for i in range(len(depths)):
+        _, _, maps = scale(i)
         nz = None
         if automask and noise is not None:
             nz = noise[i] if isinstance(noise, (list, tuple)) else noise
@@ -1224,20 +1236,12 @@ def student_loss(cfg, disps, depths, mono_depths, target, sources, K, inv_K, pos
 
     No identity maps are evaluated and no tie-breaking noise is drawn: the reference computes both in this branch and then
     overwrites the automask with ones (trainer.py:1203), so neither reaches a value or a gradient."""
-    sources, poses = list(sources), list(poses)
-    if len(sources) != len(poses) or not sources:
-        raise ValueError("student_loss: one pose per source frame, at least one frame")
+    _, _, scale = _multiview_chain("student_loss", cfg, disps, depths, target, sources, K, inv_K, poses, no_ssim)
     if len(mono_depths) != len(depths):
         raise ValueError("student_loss: one teacher depth map per scale")
-    target = target.float().contiguous()
-    sources = [s.float().contiguous() for s in sources]
     losses, sels, warped = [], [], []
-    for i, depth in enumerate(depths):
-        d = depth
-        if disps is not None and disps[i] is not None:
-            d = DispDepthFn.apply(disps[i], depth, cfg.min_depth, cfg.max_depth)
-        views = [ops.view_synthesis(d, s, K, inv_K, T)[0] for s, T in zip(sources, poses)]
-        maps = [ops.reprojection_loss(v, target, no_ssim) for v in views]
+    for i in range(len(depths)):
+        d, views, maps = scale(i)
         reproj, consistency, sel, _ = ops.student_combine(maps, rmask, d, mono_depths[i], valid, avg, details=True)
         losses.append((reproj, consistency))
         sels.append(sel)

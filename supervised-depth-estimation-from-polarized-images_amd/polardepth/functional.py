@@ -181,10 +181,16 @@ def grad_buf(p):
     return p.grad
 
 
-def _ready(p):
-    hook = getattr(p, "_pd_grad_ready", None)
-    if hook is not None:
-        hook()
+def _grad_bufs(*params):
+    """grad_buf of every parameter that takes a gradient, None for the others."""
+    return tuple(grad_buf(p) if p is not None and p.requires_grad else None for p in params)
+
+
+def _ready(*params):
+    for p in params:
+        hook = getattr(p, "_pd_grad_ready", None)
+        if hook is not None:
+            hook()
 
 
 def nhwc_view(t):
@@ -230,7 +236,7 @@ class SkipGrad:
 
 class ActGrad:
     """Hand-over between the backward nodes around one ELU output y of the depth decoder (depth_decoder.py:60-71).
-    The node that produced y (ReflectConvActFn) needs dL/dz = dL/dy * ELU'(z); the consumers of y can deliver exactly
+    The node that produced y (ConvActFn) needs dL/dz = dL/dy * ELU'(z); the consumers of y can deliver exactly
     that from their own kernels instead of a separate pass over the tensor:
       * y has ONE consumer (upconv(i,0) -> upsample): pd_up_bwd_elu multiplies by ELU'(.) and sets `activated`;
       * y has two (upconv(i,1) -> disparity head and next level's first convolution): the convolution deposits its
@@ -266,6 +272,19 @@ def _check_deposits_after_backward():
         raise RuntimeError("ActGrad: a convolution handed its input gradient to the disparity head of the same tensor, but "
                            "that head did not run in this backward pass (loss over a subset of the decoder's scales on a "
                            "hand-built graph?); the gradients upstream of it are missing.  Set PD_ACT_FUSION=0.")
+
+
+def _deposit(mail, grad):
+    """Leave `grad` in the mailbox for the node that collects it later in this backward pass, and have the end of the pass
+    check that it was collected."""
+    global _deposit_check_queued
+    if mail.grad is not None:
+        raise RuntimeError("ActGrad: a data gradient was deposited twice")
+    mail.grad = grad
+    _DEPOSITS.append(mail)
+    if not _deposit_check_queued:
+        torch.autograd.Variable._execution_engine.queue_callback(_check_deposits_after_backward)
+        _deposit_check_queued = True
 
 
 def reset_backward_state():
@@ -440,8 +459,7 @@ class ConvBNChainFn(torch.autograd.Function):
                                           ctx.drop, cfg.seed, cfg.offset, step_state, int(cfg.relu_post), st),
                   "pd_chain_bwd_reduce")
             acc = _bn_acc(dev, Co)
-            dgamma = grad_buf(gamma) if gamma is not None and gamma.requires_grad else None
-            dbeta = grad_buf(beta) if beta is not None and beta.requires_grad else None
+            dgamma, dbeta = _grad_bufs(gamma, beta)
             check(lib.pd_bn_bwd_finalize(ptr(part), rows, Co, float(N * Hz * Wz), ptr(acc), acc.numel(), ptr(dgamma),
                                          ptr(dbeta), ptr(coef), 1, st), "pd_bn_bwd_finalize")
         dz = ops.empty_nhwc(N, Co, Hz, Wz, dev)
@@ -459,7 +477,7 @@ class ConvBNChainFn(torch.autograd.Function):
         db16, wb16 = ctx.conv_bf16
         if weight.requires_grad:
             # the bias feeds a BatchNorm: its gradient is identically zero (mean subtraction)
-            gw = grad_buf(weight)
+            gw, _ = _grad_bufs(weight, bias)
             if ctx.s2d:
                 def _stem_wgrad():
                     dw2 = ops.conv2d_wgrad(x, dz, (Co, x.shape[1], 4, 4), 1, 2, alg_k=49 * (x.shape[1] // 4), bf16=wb16)
@@ -468,8 +486,6 @@ class ConvBNChainFn(torch.autograd.Function):
             else:
                 _wgrad_async(x, dz, lambda: ops.conv2d_wgrad(x, dz, weight.shape, cfg.stride, cfg.pad,
                                                              affine=cfg.affine, dw=gw, accumulate=True, bf16=wb16))
-            if bias is not None and bias.requires_grad:
-                grad_buf(bias)
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.s2d:
@@ -482,9 +498,7 @@ class ConvBNChainFn(torch.autograd.Function):
             dx = ops.conv2d_dgrad(dz, weight, (x.shape[2], x.shape[3]), cfg.stride, cfg.pad, addend=skip, bf16=db16)
         elif cfg.skip_in is not None and cfg.skip_in.grad is not None:
             raise RuntimeError("SkipGrad: a skip gradient was deposited but the block input needs no gradient")
-        for p in (weight, bias, gamma, beta):
-            if p is not None:
-                _ready(p)
+        _ready(weight, bias, gamma, beta)
         return dx, None, None, None, None, dres, None
 
 
@@ -501,73 +515,81 @@ class _NoCtx:
     """Stand-in for the autograd context on the inference path (nothing is saved)."""
 
 
-# ------------------------------------------------------------------ decoder: reflect conv + activation
-class ReflectConvActFn(torch.autograd.Function):
-    """layers.Conv3x3 (ReflectionPad2d(1) + Conv2d(3)) followed by ELU (ConvBlock) or sigmoid (dispconv)."""
+# ------------------------------------------------------------------ convolution with bias and activation (no BatchNorm)
+class ConvActFn(torch.autograd.Function):
+    """act(conv(pad(x), w) + bias) with no normalisation layer behind it, the activation in the epilogue:
+      * zero padding, any stride: nn.Conv2d -- the 1x1 q/k/v/o projections, the DPT blocks, the pose decoder;
+      * reflection padding, stride 1, k = 2 pad + 1: layers.Conv3x3 (+ ELU in ConvBlock, sigmoid in dispconv), layers.Conv5x5.
+    Backward goes through the activation's OUTPUT (pd_act_bwd).  act_mail / dx_mail: ActGrad of this node's output / input."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act, act_mail=None, dx_mail=None):
+    def forward(ctx, x, weight, bias, stride, pad, mode, act, act_mail=None, dx_mail=None):
         x = ops.as_nhwc(x)
-        y = ops.conv2d_fwd(x, weight, bias, 1, 1, mode=ops.MODE_REFLECT, act=act)
+        y = ops.conv2d_fwd(x, weight, bias, stride, pad, mode=mode, act=act)
         ctx.conv_bf16 = ops.conv_bf16_mode()
-        ctx.act = act
-        ctx.mails = (act_mail, dx_mail)         # ActGrad of this node's output / of its input
+        ctx.geom = (stride, pad, mode, act)
+        ctx.mails = (act_mail, dx_mail)
         ctx.params = (weight, bias)
-        ctx.save_for_backward(x, y)
+        ctx.save_for_backward(x, y if act != ops.ACT_NONE else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y = ctx.saved_tensors
         weight, bias = ctx.params
-        N, Co, H, W = y.shape
-        dy = dy.contiguous(memory_format=CL) if not (dy.is_contiguous(memory_format=CL) or Co == 1) else dy
-        if Co == 1 and not dy.is_contiguous():
-            dy = dy.contiguous()
+        stride, pad, mode, act = ctx.geom
         act_mail, dx_mail = ctx.mails
-        pre_activated = act_mail is not None and act_mail.activated
-        if pre_activated:
+        N, Ci, H, W = x.shape
+        Co, _, KH, KW = weight.shape
+        db16, wb16 = ctx.conv_bf16
+        dz = dy = ops.as_nhwc(dy)
+        if act_mail is not None and act_mail.activated:
             act_mail.activated = False          # the consumer already multiplied by the activation derivative
-        if ctx.act != ops.ACT_NONE and not pre_activated:
-            dz = torch.empty_like(y)
-            check(lib.pd_act_bwd(ptr(dy), ptr(y), ptr(dz), y.numel(), ctx.act, stream_ptr()), "pd_act_bwd")
-        else:
-            dz = dy
+        elif act != ops.ACT_NONE:
+            dz = torch.empty_like(dy)
+            check(lib.pd_act_bwd(ptr(dy), ptr(y), ptr(dz), dy.numel(), act, stream_ptr()), "pd_act_bwd")
         if weight.requires_grad:
-            db = grad_buf(bias) if bias is not None and bias.requires_grad else None
-            gw = grad_buf(weight)
-            _wgrad_async(x, dz, lambda: ops.conv2d_wgrad(x, dz, weight.shape, 1, 1, mode=ops.MODE_REFLECT, dw=gw,
-                                                         dbias=db, accumulate=True, bf16=ctx.conv_bf16[1]))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            Ci = x.shape[1]
-            if USE_REFLECT_BORDER and 1 < Co < 128:
-                # (from 128 output channels on the fold pass over the small deep tensor is cheaper than the border kernel,
-                #  whose every target pixel re-streams its slice of a multi-megabyte filter)
-                # the interior of the padded-grid gradient IS the zero-padding (pad 1) data gradient: it goes straight
-                # into dx; the four folded border strips are added by a kernel that touches 2(H+W) pixels per image
-                dx = ops.conv2d_dgrad(dz, weight, (H, W), 1, 1, bf16=ctx.conv_bf16[0])
-                dzv, ld_dz = nhwc_view(dz)
-                check(lib.pd_reflect_dgrad_border(ptr(dzv), ld_dz, ptr(ops.weight_cl(weight)), ptr(dx), N, H, W, Co, Ci,
-                                                  stream_ptr()), "pd_reflect_dgrad_border")
-            else:
-                # gradient on the reflection-padded grid (a zero-pad transposed conv), then fold the border
-                dxp = ops.conv2d_dgrad(dz, weight, (H + 2, W + 2), 1, 0, bf16=ctx.conv_bf16[0])
-                dx = ops.empty_nhwc(N, Ci, H, W, dy.device)
-                check(lib.pd_reflect_fold(ptr(dxp), ptr(dx), N, H, W, Ci, stream_ptr()), "pd_reflect_fold")
-            if dx_mail is not None and not dx_mail.closed:
-                if dx_mail.grad is not None:
-                    raise RuntimeError("ActGrad: a data gradient was deposited twice")
-                dx_mail.grad, dx = dx, None     # the disparity head of the same tensor sums and activates it
-                global _deposit_check_queued
-                _DEPOSITS.append(dx_mail)
-                if not _deposit_check_queued:
-                    torch.autograd.Variable._execution_engine.queue_callback(_check_deposits_after_backward)
-                    _deposit_check_queued = True
-        for p in (weight, bias):
-            if p is not None:
-                _ready(p)
-        return dx, None, None, None, None, None
+            gw, db = _grad_bufs(weight, bias)
+            _wgrad_async(x, dz, lambda: ops.conv2d_wgrad(x, dz, weight.shape, stride, pad, mode=mode, dw=gw, dbias=db,
+                                                         accumulate=True, bf16=wb16))
+        if not ctx.needs_input_grad[0]:
+            dx = None
+        elif mode == ops.MODE_ZERO:
+            dx = ops.conv2d_dgrad(dz, weight, (H, W), stride, pad, bf16=db16)
+        elif USE_REFLECT_BORDER and 1 < Co < 128 and (KH, KW, stride, pad) == (3, 3, 1, 1):
+            # (from 128 output channels on the fold pass over the small deep tensor is cheaper than the border kernel,
+            #  whose every target pixel re-streams its slice of a multi-megabyte filter)
+            # the interior of the padded-grid gradient IS the zero-padding (pad 1) data gradient: it goes straight
+            # into dx; the four folded border strips are added by a kernel that touches 2(H+W) pixels per image
+            dx = ops.conv2d_dgrad(dz, weight, (H, W), 1, 1, bf16=db16)
+            dzv, ld_dz = nhwc_view(dz)
+            check(lib.pd_reflect_dgrad_border(ptr(dzv), ld_dz, ptr(ops.weight_cl(weight)), ptr(dx), N, H, W, Co, Ci,
+                                              stream_ptr()), "pd_reflect_dgrad_border")
+        else:
+            # gradient on the reflection-padded grid (a zero-pad transposed conv), then fold the border
+            dxp = ops.conv2d_dgrad(dz, weight, (H + 2 * pad, W + 2 * pad), 1, 0, bf16=db16)
+            dx = ops.empty_nhwc(N, Ci, H, W, dz.device)
+            check(lib.pd_reflect_fold_pad(ptr(dxp), ptr(dx), N, H, W, Ci, pad, stream_ptr()), "pd_reflect_fold_pad")
+        if dx is not None and dx_mail is not None and not dx_mail.closed:
+            _deposit(dx_mail, dx)               # the disparity head of the same tensor sums and activates it
+            dx = None
+        _ready(weight, bias)
+        return dx, None, None, None, None, None, None, None, None
+
+
+def conv_bias_act(x, conv, act=ops.ACT_NONE):
+    """nn.Conv2d (zero padding, bias) with the activation of the NEXT module in its epilogue (ReLU: the residual units of the
+    DPT fusion blocks, blocks.py:289-300)."""
+    return ConvActFn.apply(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0], ops.MODE_ZERO, int(act))
+
+
+def conv_bias(x, conv):
+    return conv_bias_act(x, conv)
+
+
+def padded_conv(x, conv, pad, reflect=True, act=ops.ACT_NONE):
+    """ReflectionPad2d(p) / ZeroPad2d(p) + Conv2d(k, bias) for any odd k = 2p + 1 (layers.Conv5x5; not on the training step)."""
+    return ConvActFn.apply(x, conv.weight, conv.bias, 1, int(pad), ops.MODE_REFLECT if reflect else ops.MODE_ZERO, int(act))
 
 
 class DispHeadFn(torch.autograd.Function):
@@ -595,8 +617,7 @@ class DispHeadFn(torch.autograd.Function):
         mail = ctx.mail
         if weight.requires_grad and USE_DISPHEAD_FUSED:
             # one pass: x read once, dx written once, dw / dbias from the same folded neighbour sums
-            db = grad_buf(bias) if bias is not None and bias.requires_grad else None
-            gw = grad_buf(weight)
+            gw, db = _grad_bufs(weight, bias)
             dx = ops.empty_nhwc(N, C, H, W, x.device) if ctx.needs_input_grad[0] else None
             add, elu = None, 0
             if mail is not None and dx is not None:
@@ -611,15 +632,12 @@ class DispHeadFn(torch.autograd.Function):
             ws = ops._workspace(lib.pd_disphead_workspace(C), x.device)
             check(lib.pd_disphead_bwd(ptr(dy), ptr(y), ptr(x), ptr(ops.weight_cl(weight)), ptr(add), elu, ptr(dx), ptr(gw),
                                       ptr(db), ptr(ws), ws.numel(), N, H, W, C, 1, stream_ptr()), "pd_disphead_bwd")
-            for p in (weight, bias):
-                if p is not None:
-                    _ready(p)
+            _ready(weight, bias)
             return dx, None, None, None
         if mail is not None:
             mail.closed = True                  # unfused kernels: plain route (a gradient already deposited is added below)
         if weight.requires_grad:
-            db = grad_buf(bias) if bias is not None and bias.requires_grad else None
-            gw = grad_buf(weight)
+            gw, db = _grad_bufs(weight, bias)
 
             def wgrad():
                 nbytes = lib.pd_disphead_workspace(C)
@@ -636,9 +654,7 @@ class DispHeadFn(torch.autograd.Function):
                 dx, mail.grad = dx + mail.grad, None
         elif mail is not None and mail.grad is not None:
             raise RuntimeError("ActGrad: a gradient was deposited but the head's input needs none")
-        for p in (weight, bias):
-            if p is not None:
-                _ready(p)
+        _ready(weight, bias)
         return dx, None, None, None
 
 
@@ -653,57 +669,7 @@ def reflect_conv_act(x, conv, act, act_mail=None, dx_mail=None, head_mail=None):
         return DispHeadFn.apply(x, w, conv.bias, head_mail)
     if head_mail is not None:
         head_mail.closed = True                 # no direct head kernel for this shape: plain route
-    return ReflectConvActFn.apply(x, w, conv.bias, act, act_mail, dx_mail)
-
-
-class PaddedConvFn(torch.autograd.Function):
-    """ReflectionPad2d(p) / ZeroPad2d(p) + Conv2d(k, bias) for any odd k = 2p + 1 (layers.Conv5x5; not on the training
-    step): general implicit-GEMM forward, data gradient on the padded grid + pd_reflect_fold_pad, general weight gradient."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, pad, reflect, act=ops.ACT_NONE):
-        x = ops.as_nhwc(x)
-        mode = ops.MODE_REFLECT if reflect else ops.MODE_ZERO
-        y = ops.conv2d_fwd(x, weight, bias, 1, pad, mode=mode, act=act)
-        ctx.conv_bf16 = ops.conv_bf16_mode()
-        ctx.geom = (pad, mode, act)
-        ctx.params = (weight, bias)
-        ctx.save_for_backward(x, y if act != ops.ACT_NONE else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, y = ctx.saved_tensors
-        weight, bias = ctx.params
-        pad, mode, act = ctx.geom
-        N, Ci, H, W = x.shape
-        Co = weight.shape[0]
-        dy = dy.contiguous(memory_format=CL) if Co > 1 else dy.contiguous()
-        if act != ops.ACT_NONE:                 # the epilogue's activation (sigmoid of the uncertainty heads), through its output
-            dz = torch.empty_like(dy)
-            check(lib.pd_act_bwd(ptr(dy), ptr(y), ptr(dz), dy.numel(), act, stream_ptr()), "pd_act_bwd")
-            dy = dz
-        if weight.requires_grad:
-            db = grad_buf(bias) if bias is not None and bias.requires_grad else None
-            gw = grad_buf(weight)
-            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, 1, pad, mode=mode, dw=gw, dbias=db, accumulate=True,
-                                                         bf16=ctx.conv_bf16[1]))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if mode == ops.MODE_ZERO:
-                dx = ops.conv2d_dgrad(dy, weight, (H, W), 1, pad, bf16=ctx.conv_bf16[0])
-            else:
-                dxp = ops.conv2d_dgrad(dy, weight, (H + 2 * pad, W + 2 * pad), 1, 0, bf16=ctx.conv_bf16[0])
-                dx = ops.empty_nhwc(N, Ci, H, W, dy.device)
-                check(lib.pd_reflect_fold_pad(ptr(dxp), ptr(dx), N, H, W, Ci, pad, stream_ptr()), "pd_reflect_fold_pad")
-        for p in (weight, bias):
-            if p is not None:
-                _ready(p)
-        return dx, None, None, None, None, None
-
-
-def padded_conv(x, conv, pad, reflect=True, act=ops.ACT_NONE):
-    return PaddedConvFn.apply(x, conv.weight, conv.bias, int(pad), bool(reflect), int(act))
+    return ConvActFn.apply(x, w, conv.bias, 1, 1, ops.MODE_REFLECT, act, act_mail, dx_mail)
 
 
 class UpCatFn(torch.autograd.Function):
@@ -740,12 +706,8 @@ class UpCatFn(torch.autograd.Function):
         smail = ctx.skip_mail
         if dskip is not None and smail is not None and USE_SKIP_FUSION and not smail.closed and smail.grad is None:
             # the skip tensor's other consumer (the ResNet max-pool) adds this gradient in its own backward kernel
-            global _deposit_check_queued
-            smail.grad, dskip = dskip, None
-            _DEPOSITS.append(smail)
-            if not _deposit_check_queued:
-                torch.autograd.Variable._execution_engine.queue_callback(_check_deposits_after_backward)
-                _deposit_check_queued = True
+            _deposit(smail, dskip)
+            dskip = None
         return da, dskip, None, None
 
 
@@ -795,43 +757,6 @@ class MaxPool3s2Fn(torch.autograd.Function):
 
 def maxpool3s2(x, mail=None):
     return MaxPool3s2Fn.apply(x, mail)
-
-
-# ------------------------------------------------------------------ plain convolution with bias (no BatchNorm)
-class ConvBiasFn(torch.autograd.Function):
-    """nn.Conv2d (zero padding, bias) without a normalisation layer behind it, e.g. the 1x1 q/k/v/o projections."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad):
-        x = ops.as_nhwc(x)
-        y = ops.conv2d_fwd(x, weight, bias, stride, pad)
-        ctx.conv_bf16 = ops.conv_bf16_mode()
-        ctx.geom = (stride, pad)
-        ctx.params = (weight, bias)
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        weight, bias = ctx.params
-        stride, pad = ctx.geom
-        dy = ops.as_nhwc(dy)
-        if weight.requires_grad:
-            db = grad_buf(bias) if bias is not None and bias.requires_grad else None
-            gw = grad_buf(weight)
-            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, stride, pad, dw=gw, dbias=db, accumulate=True,
-                                                         bf16=ctx.conv_bf16[1]))
-        dx = (ops.conv2d_dgrad(dy, weight, (x.shape[2], x.shape[3]), stride, pad, bf16=ctx.conv_bf16[0])
-              if ctx.needs_input_grad[0] else None)
-        for p in (weight, bias):
-            if p is not None:
-                _ready(p)
-        return dx, None, None, None, None
-
-
-def conv_bias(x, conv):
-    return ConvBiasFn.apply(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0])
 
 
 # ------------------------------------------------------------------ single-head self-attention (config 5 variant)
@@ -1291,48 +1216,7 @@ def smooth_loss(disp, img):
     return SmoothLossFn.apply(disp.float().contiguous(), img.float().contiguous())
 
 
-# ------------------------------------------------------------------ DPT decoder glue (manydepth/dpt/blocks.py; --train_dpt)
-class ConvBiasActFn(torch.autograd.Function):
-    """nn.Conv2d (zero padding, bias) with the activation of the NEXT module in its epilogue (ReLU: the residual units of
-    the DPT fusion blocks, blocks.py:289-300); backward through the activation output (pd_act_bwd)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, act):
-        x = ops.as_nhwc(x)
-        y = ops.conv2d_fwd(x, weight, bias, stride, pad, act=act)
-        ctx.conv_bf16 = ops.conv_bf16_mode()
-        ctx.geom = (stride, pad, act)
-        ctx.params = (weight, bias)
-        ctx.save_for_backward(x, y if act != ops.ACT_NONE else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, y = ctx.saved_tensors
-        weight, bias = ctx.params
-        stride, pad, act = ctx.geom
-        dy = ops.as_nhwc(dy)
-        if act != ops.ACT_NONE:
-            dz = torch.empty_like(dy)
-            check(lib.pd_act_bwd(ptr(dy), ptr(y), ptr(dz), dy.numel(), act, stream_ptr()), "pd_act_bwd")
-            dy = dz
-        if weight.requires_grad:
-            db = grad_buf(bias) if bias is not None and bias.requires_grad else None
-            gw = grad_buf(weight)
-            _wgrad_async(x, dy, lambda: ops.conv2d_wgrad(x, dy, weight.shape, stride, pad, dw=gw, dbias=db, accumulate=True,
-                                                         bf16=ctx.conv_bf16[1]))
-        dx = (ops.conv2d_dgrad(dy, weight, (x.shape[2], x.shape[3]), stride, pad, bf16=ctx.conv_bf16[0])
-              if ctx.needs_input_grad[0] else None)
-        for p in (weight, bias):
-            if p is not None:
-                _ready(p)
-        return dx, None, None, None, None, None
-
-
-def conv_bias_act(x, conv, act=ops.ACT_NONE):
-    return ConvBiasActFn.apply(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0], int(act))
-
-
+# ------------------------------------------------------------------ pose network tail (csrc/pose.hip)
 class PoseHeadFn(ops._PoseHeadFn):
     """ops.pose_head for a module's 1x1 convolution: the weight and bias gradients are added to the parameters' gradient
     buffers (grad_buf, like every convolution here), not returned to autograd."""
@@ -1343,8 +1227,7 @@ class PoseHeadFn(ops._PoseHeadFn):
         gw = grad_buf(weight) if weight.requires_grad else torch.zeros_like(weight)
         gb = grad_buf(bias) if bias.requires_grad else torch.zeros_like(bias)
         gx = ops.pose_head_bwd(ctx.saved_tensors, ctx.geom, (gaa, gtr, gT, gTi), gw, gb, accumulate=True)
-        for p in (weight, bias):
-            _ready(p)
+        _ready(weight, bias)
         return (gx if ctx.needs_input_grad[0] else None), None, None, None
 
 
@@ -1355,6 +1238,7 @@ def pose_head(x, conv, invert=False):
     return PoseHeadFn.apply(ops.as_nhwc(x.float()), conv.weight, conv.bias, bool(invert))
 
 
+# ------------------------------------------------------------------ DPT decoder glue (manydepth/dpt/blocks.py; --train_dpt)
 class ReluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -126,6 +126,17 @@ def conv_out_size(h, k, s, p):
     return (h + 2 * p - k) // s + 1
 
 
+def _quad_strides(t):
+    """Channel stride 1 and every other stride a whole quad: what the 16-byte gathers of the kernels need of an operand."""
+    sN, sC, sH, sW = t.stride()
+    return sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0
+
+
+def _conv16_shape(Co, C, KH, KW, stride):
+    """The layer shape of the halo-tile kernels of the 16-channel decoder tail (pd_conv16, pd_conv16_wgrad)."""
+    return USE_CONV16 and Co == 16 and C in (16, 32) and KH == 3 and KW == 3 and stride == 1
+
+
 def conv2d_fwd(x, w, bias=None, stride=1, pad=0, mode=MODE_ZERO, act=ACT_NONE, want_stats=False,
                affine=None, out=None, out_hw=None, out_scale=None, alg_k=None):
     """y = act(conv(x, w) [* out_scale] + bias).  x: [N,C,H,W] any strides; returns channels_last [N,Co,Ho,Wo].
@@ -162,20 +173,18 @@ def conv2d_fwd(x, w, bias=None, stride=1, pad=0, mode=MODE_ZERO, act=ACT_NONE, w
     sub, div = (affine if affine is not None else (0.0, 1.0))
     sN, sC, sH, sW = x.stride()
     vec = C % 4 == 0 and sC == 1 and affine is None
-    if (USE_CONV16 and mode == MODE_REFLECT and Co == 16 and C in (16, 32) and KH == 3 and KW == 3 and stride == 1 and pad == 1
-            and vec and not want_stats and out_scale is None and act in (ACT_NONE, ACT_ELU) and out_hw is None
-            and H >= 2 and W >= 2 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0):
+    shape = ("fwd", N, C, H, W, Co, KH, stride, mode)
+    if (_conv16_shape(Co, C, KH, KW, stride) and mode == MODE_REFLECT and pad == 1 and vec and _quad_strides(x)
+            and not want_stats and out_scale is None and act in (ACT_NONE, ACT_ELU) and out_hw is None and H >= 2 and W >= 2):
         # 16-channel decoder tail: halo-tile kernel (every input pixel staged once instead of once per tap)
         _profiled("conv16_halo_kernel", 2.0 * N * Ho * Wo * Co * C * 9,
                   lambda: check(lib.pd_conv16(ptr(x), ptr(w), ptr(bias), ptr(out), N, H, W, C, sN, sH, sW, Ho, Wo, Co, ldy,
-                                              0, act, stream_ptr()), "pd_conv16"),
-                  shape=("fwd", N, C, H, W, Co, KH, stride, mode))
+                                              0, act, stream_ptr()), "pd_conv16"), shape=shape)
         return out
     _profiled(_igemm_label(N * Ho * Wo, Co, vec, "fwd", C, KH, KW, stride, pad, mode, act, out_scale is not None, (Ho, Wo)), 2.0 * N * Ho * Wo * Co * (alg_k if alg_k is not None else C * KH * KW),
               lambda: check(lib.pd_conv2d(ptr(x), ptr(w), ptr(bias), ptr(out_scale), ptr(out), ptr(stats), N, H, W, C, sN, sH, sW, sC,
                                           Ho, Wo, Co, KH, KW, stride, pad, mode, act, int(affine is not None), sub,
-                                          div, ldy, CONV_FLAGS, stream_ptr()), "pd_conv2d"),
-              shape=("fwd", N, C, H, W, Co, KH, stride, mode))
+                                          div, ldy, CONV_FLAGS, stream_ptr()), "pd_conv2d"), shape=shape)
     return (out, stats) if want_stats else out
 
 
@@ -220,8 +229,10 @@ def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None, bf16=None)
         wt = weight_transposed(w)
     dx = empty_nhwc(N, Ci, H, W, dy.device)
     sN, sC, sH, sW = dy.stride()
+    # algorithmic flops of the data gradient = those of the forward conv it differentiates
+    flops, shape = 2.0 * N * Hy * Wy * Co * Ci * KH * KW, ("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED)
     if (USE_S2_PHASES and not (flags & CONV_GENERAL_KERNELS) and addend is None and stride == 2 and KH == 3 and KW == 3 and pad == 1 and H == 2 * Hy and W == 2 * Wy
-            and Co % 32 == 0 and Ci % 4 == 0 and Ci > 16 and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0):
+            and Co % 32 == 0 and Ci % 4 == 0 and Ci > 16 and _quad_strides(dy)):
         # stride-2 data gradient by output parity: four stride-1 2x2 sub-filter launches + one interleave
         def _phases():
             wsub = torch.empty(9 * Ci * Co, dtype=torch.float32, device=dy.device)     # class filters 1x1, 1x2, 2x1, 2x2
@@ -233,35 +244,29 @@ def conv2d_dgrad(dy, w, in_hw, stride=1, pad=0, wt=None, addend=None, bf16=None)
                                          sC, Hy, Wy, Ci, 1 + ph, 1 + pw, ph, pw, MODE_TRANSPOSED, Ci, flags, stream_ptr()),
                       "pd_conv2d_rect(dgrad s2 phase)")
             check(lib.pd_interleave4(ptr(sub), ptr(dx), N, Hy, Wy, Ci, stream_ptr()), "pd_interleave4")
-        _profiled("conv_dgrad_s2_phases", 2.0 * N * Hy * Wy * Co * Ci * KH * KW, _phases,
-                  shape=("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED))
+        _profiled("conv_dgrad_s2_phases", flops, _phases, shape=shape)
         return dx
     c16_mode = 1 if (pad == 0 and H == Hy + 2 and W == Wy + 2) else (2 if (pad == 1 and H == Hy and W == Wy) else 0)
-    if (USE_CONV16 and addend is None and Co == 16 and Ci in (16, 32) and KH == 3 and KW == 3 and stride == 1 and c16_mode
-            and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0 and Hy >= 2 and Wy >= 2):
+    if _conv16_shape(Co, Ci, KH, KW, stride) and addend is None and c16_mode and _quad_strides(dy) and Hy >= 2 and Wy >= 2:
         # data gradient of a 16-channel 3x3 conv (on the padded grid, or pad 1 on the same grid): halo-tile kernel
-        _profiled("conv16_halo_kernel", 2.0 * N * Hy * Wy * Co * Ci * 9,
+        _profiled("conv16_halo_kernel", flops,
                   lambda: check(lib.pd_conv16(ptr(dy), ptr(wt), None, ptr(dx), N, Hy, Wy, Co, sN, sH, sW, H, W, Ci, Ci, c16_mode,
-                                              0, stream_ptr()), "pd_conv16(dgrad)"),
-                  shape=("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED))
+                                              0, stream_ptr()), "pd_conv16(dgrad)"), shape=shape)
         return dx
+    label = _igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W), flags=flags)
     if addend is not None:
         assert addend.shape == dx.shape and addend.stride(1) == 1 and addend.is_cuda
         ld_add = addend.stride(3)
         assert addend.stride(2) == W * ld_add and addend.stride(0) == H * W * ld_add
-        _profiled(_igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W), flags=flags),
-                  2.0 * N * Hy * Wy * Co * Ci * KH * KW,
+        _profiled(label, flops,
                   lambda: check(lib.pd_conv2d_add(ptr(dy), ptr(wt), ptr(addend), ld_add, ptr(dx), N, Hy, Wy, Co, sN, sH, sW,
                                                   sC, H, W, Ci, KH, KW, stride, pad, MODE_TRANSPOSED, Ci, flags, stream_ptr()),
-                                "pd_conv2d_add(dgrad)"),
-                  shape=("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED))
-        return dx
-    # algorithmic flops of the data gradient = those of the forward conv it differentiates
-    _profiled(_igemm_label(N * H * W, Ci, True, "dgrad", Co, KH, KW, stride, pad, MODE_TRANSPOSED, out_hw=(H, W), flags=flags), 2.0 * N * Hy * Wy * Co * Ci * KH * KW,
-              lambda: check(lib.pd_conv2d(ptr(dy), ptr(wt), None, None, ptr(dx), None, N, Hy, Wy, Co, sN, sH, sW, sC,
-                                          H, W, Ci, KH, KW, stride, pad, MODE_TRANSPOSED, ACT_NONE, 0, 0.0, 1.0, Ci,
-                                          flags, stream_ptr()), "pd_conv2d(dgrad)"),
-              shape=("dgrad", N, Ci, H, W, Co, KH, stride, MODE_TRANSPOSED))
+                                "pd_conv2d_add(dgrad)"), shape=shape)
+    else:
+        _profiled(label, flops,
+                  lambda: check(lib.pd_conv2d(ptr(dy), ptr(wt), None, None, ptr(dx), None, N, Hy, Wy, Co, sN, sH, sW, sC,
+                                              H, W, Ci, KH, KW, stride, pad, MODE_TRANSPOSED, ACT_NONE, 0, 0.0, 1.0, Ci,
+                                              flags, stream_ptr()), "pd_conv2d(dgrad)"), shape=shape)
     return dx
 
 
@@ -303,29 +308,23 @@ def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, mode=MODE_ZERO, affine=None, d
         dbias = torch.empty(Co, dtype=torch.float32, device=x.device)
     M, K = N * Ho * Wo, KH * KW * C
     sN, sC, sH, sW = x.stride()
-    if (USE_CONV16 and mode == MODE_REFLECT and Co == 16 and C in (16, 32) and KH == 3 and KW == 3 and stride == 1 and pad == 1
-            and affine is None and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0 and H >= 2 and W >= 2
-            and dy.stride(3) % 4 == 0):
+    shape = ("wgrad", N, C, H, W, Co, KH, stride, mode)
+    fits = affine is None and _quad_strides(x) and dy.stride(3) % 4 == 0
+    if _conv16_shape(Co, C, KH, KW, stride) and mode == MODE_REFLECT and pad == 1 and fits and H >= 2 and W >= 2:
         ws = _workspace(lib.pd_conv16_wgrad_workspace(C), x.device)
         _profiled("conv16_wgrad_kernel", 2.0 * M * Co * K,
                   lambda: check(lib.pd_conv16_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), N, H, W, C,
                                                     sN, sH, sW, dy.stride(3), int(accumulate), stream_ptr()),
-                                "pd_conv16_wgrad"),
-                  shape=("wgrad", N, C, H, W, Co, KH, stride, mode))
+                                "pd_conv16_wgrad"), shape=shape)
         return (dw, dbias) if (want_bias or dbias is not None) else dw
-    nbytes = lib.pd_conv2d_wgrad_workspace(M, Co, K, flags)
-    ws = _workspace(nbytes, x.device)
+    ws = _workspace(lib.pd_conv2d_wgrad_workspace(M, Co, K, flags), x.device)
     sub, div = (affine if affine is not None else (0.0, 1.0))
-    sN, sC, sH, sW = x.stride()
-    fits = affine is None and sC == 1 and sN % 4 == 0 and sH % 4 == 0 and sW % 4 == 0 and dy.stride(3) % 4 == 0
     route = lib.pd_conv2d_wgrad_route(M, Co, C, KH, KW, stride, pad, mode, H, W, Ho, Wo, flags) if fits else 0
-    _profiled(_WGRAD_LABELS[route & 7],
-              2.0 * M * Co * (alg_k if alg_k is not None else K),
+    _profiled(_WGRAD_LABELS[route & 7], 2.0 * M * Co * (alg_k if alg_k is not None else K),
               lambda: check(lib.pd_conv2d_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), N, H, W, C,
                                                 sN, sH, sW, sC, Ho, Wo, Co, KH, KW, stride, pad, mode,
                                                 int(affine is not None), sub, div, dy.stride(3), int(accumulate),
-                                                flags, stream_ptr()), "pd_conv2d_wgrad"),
-              shape=("wgrad", N, C, H, W, Co, KH, stride, mode))
+                                                flags, stream_ptr()), "pd_conv2d_wgrad"), shape=shape)
     return (dw, dbias) if (want_bias or dbias is not None) else dw
 
 

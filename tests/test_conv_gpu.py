@@ -265,7 +265,7 @@ def test_rectangular_filter_with_separate_padding(geom):
                                   (1, 16, 64, 96), (1, 32, 3, 70)])
 def test_sixteen_channel_tail_halo_kernel(case):
     """pd_conv16: ReflectionPad2d(1) + Conv3x3 with 16 output channels (+ bias, ELU) from a halo tile in LDS, and its data
-    gradient on the padded grid (through ReflectConvActFn: pd_conv16 mode 1 + pd_reflect_fold), against autograd
+    gradient (through functional.ConvActFn: pd_conv16 mode 2 + pd_reflect_dgrad_border), against autograd
     through a PyTorch fp32 CPU reference; tiles that overhang the image, images smaller than a tile, 2x2."""
     from polardepth import functional as PF
     N, C, H, W = case

@@ -704,6 +704,55 @@ int pd_pose_head_bwd(const void* gT, const void* gT_inv, const void* gaxisangle,
                      const void* axisangle, const void* translation, const void* w, const void* mean, void* gx, void* gw,
                      void* gb, void* gpre_ws, int N, int h, int wd, int Cin, int Co, int invert, int accumulate, void* stream);
 
+/* Pose supervision and the records of the pose evaluator (csrc/pose_loss.hip): --supervise_pose of trainer.py:1267-1285, the
+ * predicted cam_T_cam against the ground-truth relative pose, rotations compared as rotation vectors.
+ *
+ * rv(M) for a 3x3 block M -- roma.rotmat_to_rotvec, i.e. roma.rotmat_to_unitquat followed by roma.unitquat_to_rotvec, which
+ * roma adapted from SciPy's Rotation.from_matrix / as_rotvec.  In fp64 from the fp32 values, every expression in its order, no
+ * fused multiply-add:
+ *   tr = (M00 + M11) + M22;  c = the index of the FIRST maximum of (M00, M11, M22, tr)
+ *   c < 3, i = c, j = (i + 1) % 3, k = (j + 1) % 3:
+ *     q[i] = (1 - tr) + 2 M[i][i];  q[j] = M[j][i] + M[i][j];  q[k] = M[k][i] + M[i][k];  q[3] = M[k][j] - M[j][k]
+ *   c == 3:  q = (M21 - M12, M02 - M20, M10 - M01, 1 + tr)
+ *   q = q / sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3)   (four divisions);  q = -q where q3 < 0
+ *   s = sqrt((q0 q0 + q1 q1) + q2 q2);  angle = 2 atan2(s, q3)
+ *   scale = (2 + angle^2 / 12) + 7 (angle^2 angle^2) / 2880 where angle <= 1e-3, else angle / sin(angle / 2)
+ *   rv = scale * (q0, q1, q2)
+ * Near angle = pi the sign of rv is discontinuous (q3 changes sign, or the branch c changes); so it is in the reference, and
+ * nothing here smooths it.  M need not be orthogonal; a non-finite entry propagates into rv.
+ *
+ * pd_pose_loss_fwd
+ *   T_pred, T_gt   host arrays of F device pointers (1 <= F <= PD_REPROJ_MAX_FRAMES, as pd_reproj_combine_fwd), each [N,4,4] fp32
+ *   frame_weight   F host floats
+ *   valid          [N,F] fp32, 0 = item n has no frame f and does not count, or NULL: all count
+ *   records        [F,N,10] doubles out (8-byte aligned) or NULL, written for invalid items too:
+ *                  rv(R_pred) (3), rv(R_gt) (3), |rv(D)| with D[i][j] = (R_pred[0][i] R_gt[0][j] + R_pred[1][i] R_gt[1][j]) +
+ *                  R_pred[2][i] R_gt[2][j] (the geodesic angle of R_pred^T R_gt, radians), |t_pred - t_gt|, |t_pred|, |t_gt|
+ *                  (norms: sqrt((x x + y y) + z z); t = T[:3,3])
+ *   vals           3 + 2 F floats out
+ * Per frame f, in fp64: cnt_f = the number of items with valid != 0 (N without valid);
+ *   e_r[n] = sum_k (rv(R_pred)[k] - rv(R_gt)[k])^2, e_t[n] = sum_k (t_pred[k] - t_gt[k])^2, k ascending
+ *   r_f = 0.1 * ((sum of e_r over the valid n) / (3 cnt_f)),  t_f = (sum of e_t over the valid n) / (3 cnt_f);  both 0 when cnt_f == 0
+ *   vals[0] = sum_f r_f, vals[1] = sum_f t_f, vals[2] = sum_f frame_weight[f] (r_f + t_f)  (f ascending),
+ *   vals[3 + 2f] = r_f, vals[4 + 2f] = t_f, each rounded once to fp32.
+ * One workgroup of 256 threads: thread t sums its items t, t + 256, ... ascending, the 64 lanes of a wavefront by xor shuffles
+ * (32, 16, ... 1), the four wavefronts ((w0 + w1) + w2) + w3.  Bit-reproducible, no atomics, no host synchronisation.
+ *
+ * pd_pose_loss_bwd -- gvals: 3 floats ON THE DEVICE, the gradients of vals[0..2] (vals[3..] carry none); gT: host array of
+ * F device pointers [N,4,4] fp32, written with "=".  One thread per (frame, item), in fp64, rounded once; with
+ * a_r = gvals[0] + frame_weight[f] gvals[2], a_t = gvals[1] + frame_weight[f] gvals[2]:
+ *   gT[:3,:3] = (a_r * 0.1 * 2 / (3 cnt_f)) * J^T (rv(R_pred) - rv(R_gt)),  gT[:3,3] = (a_t * 2 / (3 cnt_f)) * (t_pred - t_gt),
+ *   last row 0; an invalid item receives 16 zeros; the ground truth receives no gradient.
+ * J = d rv / d M of the expressions above as written: the branch c is fixed, the sign flip is a constant factor, the
+ * small-angle polynomial is differentiated in its own branch (angle / 6 + 7 angle^3 / 720), and d sqrt(x) / dx is taken as 0 at
+ * x == 0 (PyTorch's rule for norm, as in pd_pose_matrix_bwd), so that at the identity d rv / d M is (M21 - M12) / 2, ...
+ * Limits of both: 0 <= N <= 65535; N == 0 writes zeros into vals (forward) and touches nothing else (the matrix pointers may
+ * then be null).  Parity with roma itself is pinned through SciPy's identical algorithm (tests/test_pose_loss_ref.py). */
+int pd_pose_loss_fwd(const void* const* T_pred, const void* const* T_gt, int F, const float* frame_weight, const void* valid,
+                     void* records, void* vals, int N, void* stream);
+int pd_pose_loss_bwd(const void* gvals, const void* const* T_pred, const void* const* T_gt, int F, const float* frame_weight,
+                     const void* valid, void* const* gT, int N, void* stream);
+
 /* ------------------------------------------------------------------------- multi-frame cost volume (csrc/matching.hip)
  * pd_cost_volume -- ManyDepth's plane sweep from known poses: ResnetEncoderMatching.match_features, compute_confidence_mask
  * and the lowest-cost map (resnet_encoder.py:430-511, 534-541, 620-630), forward only (the reference runs it under no_grad).

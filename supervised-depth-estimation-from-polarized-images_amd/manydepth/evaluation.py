@@ -17,6 +17,7 @@ from polardepth import color as pdcolor
 from polardepth import normals_eval
 from polardepth import depth_eval
 from polardepth import pointcloud
+from polardepth import pose_eval
 from polardepth._lib import lib, check, ptr, stream_ptr
 
 _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, "teapot": 120, "cutlery": 140,
@@ -27,7 +28,7 @@ class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
-                 pol_calibration=None, normals_decoder=None):
+                 pol_calibration=None, normals_decoder=None, pose_network=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -45,7 +46,10 @@ class Evaluation:
         calibration (a ``polardepth.calibration.Calibration`` or the path of a saved one, or $PD_POL_CALIBRATION), applied to
         both kinds of sensor frame before their demosaic; its layout must be ``pol_layout``.  None = none.  ``normals_decoder``:
         build the `arch1++_separate_normals_dec` variant's NormalsDecoder behind the normals encoder (``predict_all``,
-        ``test_normals``); None reads $PD_NORMALS_DECODER == "1", as the Trainer does."""
+        ``test_normals``); None reads $PD_NORMALS_DECODER == "1", as the Trainer does.  ``pose_network``: also build the pose
+        network (``pose_encoder``, ``pose``) as the Trainer's ``opt.pose_network`` mode does, and a second loader that serves
+        the neighbouring frames -1 and 1 with their ground-truth poses (``test_pose``); None reads $PD_POSE_NETWORK == "1".
+        Without it the object is what it was: the same models, the same draws, the same loader."""
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -87,6 +91,11 @@ class Evaluation:
             if not augment_normals:
                 raise ValueError("the separate normals decoder sits behind the normals encoder: it needs augment_normals")
             self.models["normals_decoder"] = networks.NormalsDecoder(64)
+        self.pose_network = (os.environ.get("PD_POSE_NETWORK") == "1") if pose_network is None else bool(pose_network)
+        if self.pose_network:                     # as Trainer.__init__ builds them (trainer.py:222-236, "separate_resnet")
+            self.models["pose_encoder"] = networks.ResnetEncoder(18, False, num_input_images=2)
+            self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc, num_input_features=1,
+                                                       num_frames_to_predict_for=2)
         for m in self.models.values():
             m.to(self.device).eval()
         # evaluation.py:96 reads ../splits (cwd = manydepth/); the repository root works too
@@ -104,13 +113,20 @@ class Evaluation:
         if self.pol_calibration is not None:                  # a calibration of another frame size is refused here, not in predict
             pdcal.check_dataset(self.pol_calibration, ds, "the test loader")
         self.test_loader = DataLoader(ds, batch_size, False, num_workers=num_workers, drop_last=True)
+        self.pose_frame_ids = [-1, 1]
+        if self.pose_network:
+            # a pair is scored only where the neighbour's picture and both pose files exist (need_poses=True)
+            pose_ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0] + self.pose_frame_ids, 4, is_train=False,
+                                              supervised_depth_only=False, need_poses=True)
+            self.pose_loader = DataLoader(pose_ds, batch_size, False, num_workers=num_workers, drop_last=True)
 
     def load_mono_model(self):
         if self.load_weights_folder is None:
             return
         for n, m in self.models.items():
             path = os.path.join(self.load_weights_folder, f"{n}.pth")
-            if n == "normals_decoder" and not os.path.isfile(path):      # weights of a run without the variant: it keeps its initialisation
+            # weights of a run without the variant / without the pose network: the module keeps its initialisation
+            if n in ("normals_decoder", "pose_encoder", "pose") and not os.path.isfile(path):
                 continue
             sd = torch.load(path, map_location="cpu")
             m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()})
@@ -253,6 +269,46 @@ class Evaluation:
             if pooled[k][nm - 1] > 0:
                 print(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
                 print(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
+        return results
+
+    @torch.no_grad()
+    def predict_poses(self, inputs):
+        """{frame id: cam_T_cam [N,4,4]} for the neighbours of ``pose_frame_ids``: one pass of the pose network per
+        neighbour on the un-jittered frame pair in temporal order, as Trainer.predict_poses runs it."""
+        if not self.pose_network:
+            raise ValueError("predict_poses needs Evaluation(pose_network=True) (or PD_POSE_NETWORK=1)")
+        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        cur = inputs[("color", 0, 0)].float()
+        out = {}
+        for f_i in self.pose_frame_ids:
+            other = inputs[("color", f_i, 0)].float()
+            feats = self.models["pose_encoder"](torch.cat([other, cur] if f_i < 0 else [cur, other], 1))
+            out[f_i] = self.models["pose"].forward_with_matrices([feats], invert=f_i < 0)[2]
+        return out
+
+    @torch.no_grad()
+    def test_pose(self):
+        """Pose accuracy of the pose network (polardepth.pose_eval; the reference reports none): the predicted ``cam_T_cam``
+        of every neighbour against ``("poses", i)``, one pd_pose_loss_fwd call per batch for its per-pair records, which stay
+        on the device until the loop is over.  Prints, and returns {frame id: r, ..., "all": r} with r = {"pairs", "missing",
+        "bad", "rot_deg": {mean, median, rmse, max of the geodesic angle in degrees}, "trans_mm": {the same of
+        |t_pred - t_gt| in millimetres}, "scale_ratio_median": the median of |t_pred| / |t_gt| over the pairs with
+        |t_gt| >= 1 mm}.  Pairs whose ``frame_valid`` is 0 count as ``missing``, pairs with a non-finite record as ``bad``;
+        neither is averaged."""
+        if not self.pose_network:
+            raise ValueError("test_pose needs Evaluation(pose_network=True) (or PD_POSE_NETWORK=1)")
+        ids = self.pose_frame_ids
+        records, valids = [], []
+        for inputs in self.pose_loader:
+            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+            T = self.predict_poses(inputs)
+            valid = torch.stack([inputs[("frame_valid", i)] for i in ids], 1).float()
+            records.append(pose_eval.pair_records([T[i] for i in ids], [inputs[("poses", i)] for i in ids], valid))
+            valids.append(valid)
+        if not records:
+            return {}
+        results = pose_eval.metrics_from_records(torch.cat(records, 1), torch.cat(valids, 0), ids)
+        print(pose_eval.format_report(results))
         return results
 
     @torch.no_grad()

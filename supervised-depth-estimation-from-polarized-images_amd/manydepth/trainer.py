@@ -19,9 +19,17 @@ captured yet (``PD_STEP_GRAPH=1`` is refused with it).  With ``opt.pose_network 
 ``--depth_supervision True`` without ``--depth_supervision_only`` and without ``--pose_input``) the poses of that term are
 PREDICTED: ``pose_encoder`` (ResnetEncoder, two stacked frames) and ``pose`` (PoseDecoder) see the jittered frame pair of
 every neighbour in temporal order (trainer.py:222-236, 669-707), their output goes through transformation_from_parameters into
-the same warp, and the term trains depth and pose together; ``--supervise_pose``, ``--res_pose`` and the matching-pose half
+the same warp, and the term trains depth and pose together; ``--res_pose`` and the matching-pose half
 of predict_poses are not built, and ``PD_STEP_GRAPH=1`` / ``opt.bf16`` / ``torch.distributed`` are refused with it; its loaders
-take a neighbour's picture without asking for pose files (``HAMMER_Dataset(need_poses=False)``).  The cost-volume student's building
+take a neighbour's picture without asking for pose files (``HAMMER_Dataset(need_poses=False)``).  ``--supervise_pose`` (only
+with the pose network; trainer.py:1267-1285) adds the predicted ``cam_T_cam`` against the ground-truth relative pose,
+rotations compared as rotation vectors (``roma.rotmat_to_rotvec``, restated in csrc/pose_loss.hip: one launch forward, one
+backward, for all frames): ``r_loss`` / ``t_loss`` are the plain sums over the frames, and what joins ``loss`` (after the
+division by the number of scales) weights frame f of F with F - f, because the reference adds its RUNNING sums inside the loop
+over the frames -- with ``frame_ids 0 -1 1`` the first neighbour counts twice, the second once.  The loaders are then built
+with ``need_poses=True``, and -- a deliberate difference from the reference, which has no mask here and supervises a missing
+neighbour towards whatever its loader substituted -- items whose ``frame_valid`` is 0 are left out, the mean being taken over
+the present ones, as in the photometric term.  The cost-volume student's building
 blocks exist -- the plane sweep (``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training
 branch (``--train_student``: matching augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it,
 ``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
@@ -121,7 +129,9 @@ class Trainer:
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: the HIP hot path cannot run and there is no CPU fallback")
         for flag in ("train_stereo_only", "train_dpt", "train_student", "use_stereo", "res_pose", "supervise_pose"):
-            if getattr(self.opt, flag, False):
+            # --supervise_pose supervises the PREDICTED poses: with the pose network it is built (below), without it there
+            # is nothing to supervise
+            if getattr(self.opt, flag, False) and not (flag == "supervise_pose" and getattr(self.opt, "pose_network", False)):
                 raise NotImplementedError(f"--{flag}: outside the supervised hot path of this build")
         # the one further configuration: the supervised terms plus the photometric reprojection term from the neighbouring
         # frames, warped with the ground-truth relative poses (no pose network, no cost volume)
@@ -142,6 +152,9 @@ class Trainer:
             if torch.distributed.is_available() and torch.distributed.is_initialized():
                 raise NotImplementedError("torch.distributed with opt.pose_network: the gradient reducer expects one "
                                           "backward pass per module and step; run this mode on one GPU")
+        # --supervise_pose (trainer.py:1267-1285): the predicted cam_T_cam against the ground-truth relative pose of
+        # ``_pose/%06d.txt``, one launch for all frames (polardepth.ops.pose_supervision, csrc/pose_loss.hip)
+        self.supervise_pose = bool(self.pose_network and getattr(self.opt, "supervise_pose", False))
         self.photometric = bool(self.opt.depth_supervision and (self.opt.pose_input or self.pose_network)
                                 and not self.opt.depth_supervision_only and not getattr(self.opt, "v1_multiscale", False))
         if not (self.opt.depth_supervision_only and self.opt.depth_supervision) and not self.photometric:
@@ -266,7 +279,7 @@ class Trainer:
                                                   img_ext='.png', offset=self.opt.offset, modality=self.opt.modality,
                                                   supervised_depth=True, supervised_depth_only=not self.photometric,
                                                   depth_modality=self.opt.depth_modality, lookup_aug=self.pose_network,
-                                                  need_poses=not self.pose_network)
+                                                  need_poses=not self.pose_network or self.supervise_pose)
         train_dataset, val_dataset, test_dataset = mk(self.data_path, train_files, True), \
             mk(self.data_path, val_files, False), mk(self.data_path_val, test_files, False)
         if self.pol_calibration is not None:
@@ -529,6 +542,18 @@ class Trainer:
                                       self.opt.max_depth)
             losses["normals_decoder_loss"] = nl
             losses["loss"] = losses["loss"] + self.opt.normals_loss_weight * nl
+        if self.supervise_pose and not is_multi:
+            # trainer.py:1267-1285, added after the division by the number of scales.  ``total`` carries the reference's
+            # cumulative frame weights [F .. 1] (it adds the running sums inside its loop over the frames); r_loss / t_loss
+            # are the plain sums it logs.  Unlike the reference, a neighbour the loader flags as missing is left out and
+            # the mean is taken over the present items (ops.pose_supervision).  Under --freeze_teacher_and_pose the
+            # matrices carry no tape, and neither do these terms.
+            ids = self.frame_ids[1:]
+            r_loss, t_loss, total = ops.pose_supervision(
+                [outputs[("cam_T_cam", 0, i)] for i in ids], [inputs[("poses", i)] for i in ids],
+                valid=torch.stack([inputs[("frame_valid", i)] for i in ids], 1).float())
+            losses["r_loss"], losses["t_loss"] = r_loss, t_loss
+            losses["loss"] = losses["loss"] + total
         return losses
 
     def compute_supervised_normals_losses(self, depth_gt, depth_pred, intrinsics, mask=None):

@@ -591,6 +591,81 @@ def pose_head(x, weight, bias, invert=False):
                              bool(invert))
 
 
+# ------------------------------------------------------------------ pose supervision (csrc/pose_loss.hip)
+def _frame_weights(w):
+    import ctypes
+    return (ctypes.c_float * len(w))(*w)
+
+
+class _PoseSupervisionFn(torch.autograd.Function):
+    """pd_pose_loss_fwd / _bwd: returns (vals[:3], records | None); differentiable in the F predicted matrices."""
+
+    @staticmethod
+    def forward(ctx, T_gt, valid, weights, want_records, *T_pred):
+        F = len(T_pred)
+        N = T_pred[0].shape[0]
+        dev = T_pred[0].device
+        vals = torch.empty(3 + 2 * F, dtype=torch.float32, device=dev)
+        records = torch.empty((F, N, 10), dtype=torch.float64, device=dev) if want_records else None
+        check(lib.pd_pose_loss_fwd(_dev_ptrs(T_pred), _dev_ptrs(T_gt), F, _frame_weights(weights), ptr(valid), ptr(records),
+                                   ptr(vals), N, stream_ptr()), "pd_pose_loss_fwd")
+        ctx.geom = (F, N, tuple(weights))
+        ctx.save_for_backward(valid, *T_gt, *T_pred)
+        if records is not None:
+            ctx.mark_non_differentiable(records)
+        return vals[:3], records
+
+    @staticmethod
+    def backward(ctx, gvals, _grecords):
+        F, N, weights = ctx.geom
+        valid, T_gt, T_pred = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + F], ctx.saved_tensors[1 + F:]
+        grads = [torch.empty((N, 4, 4), dtype=torch.float32, device=gvals.device) for _ in range(F)]
+        check(lib.pd_pose_loss_bwd(ptr(gvals.float().contiguous()), _dev_ptrs(T_pred), _dev_ptrs(T_gt), F,
+                                   _frame_weights(weights), ptr(valid), _dev_ptrs(grads), N, stream_ptr()), "pd_pose_loss_bwd")
+        return (None, None, None, None, *grads)
+
+
+def pose_supervision(T_pred, T_gt, valid=None, frame_weight=None, details=False):
+    """``--supervise_pose`` of trainer.py:1267-1285 in one launch (pd_pose_loss_fwd; include/polardepth.h states the
+    arithmetic): ``T_pred`` and ``T_gt`` are lists of F [N,4,4] matrices, the predicted ``cam_T_cam`` of every neighbouring
+    frame and its ground-truth relative pose.  Per frame ``r_f = 0.1 * mean((rv(R_pred) - rv(R_gt))^2)`` with ``rv`` =
+    ``roma.rotmat_to_rotvec`` and ``t_f = mean((t_pred - t_gt)^2)``.  Returns ``(r_loss, t_loss, total)``: the plain sums
+    over the frames, which the reference logs, and ``total = sum_f frame_weight[f] (r_f + t_f)``, which it adds to the loss.
+
+    ``frame_weight`` defaults to ``[F, F-1, ..., 1]``: the reference adds the RUNNING sums ``r_loss + t_loss`` to the total
+    inside its loop over the frames, so with ``frame_ids 0 -1 1`` the first neighbour counts twice and the second once.
+    ``valid`` [N,F] marks with 0 the items whose frame f does not exist: they are left out and the mean is taken over the
+    present ones (the reference has no mask and supervises towards whatever its loader substituted -- a deliberate
+    difference, the rule of the photometric term).  ``details``: also ``records`` [F,N,10] float64 per item, invalid ones
+    included (rv_pred, rv_gt, the geodesic angle of R_pred^T R_gt in radians, |t_pred - t_gt|, |t_pred|, |t_gt|).
+    Differentiable in the ``T_pred`` tensors; the ground truth receives no gradient."""
+    T_pred, T_gt = list(T_pred), list(T_gt)
+    F = len(T_pred)
+    if not 1 <= F <= REPROJ_MAX_FRAMES:
+        raise ValueError(f"pose_supervision: 1 .. {REPROJ_MAX_FRAMES} frames, got {F}")
+    if len(T_gt) != F:
+        raise ValueError(f"pose_supervision: as many ground-truth as predicted poses, got {len(T_gt)} / {F}")
+    shape = tuple(T_pred[0].shape)
+    if len(shape) != 3 or shape[1:] != (4, 4):
+        raise ValueError(f"pose_supervision: poses must be [N,4,4], got {shape}")
+    if shape[0] > 65535:
+        raise ValueError(f"pose_supervision: at most 65535 items, got {shape[0]}")
+    for t in (*T_pred, *T_gt):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"pose_supervision: every pose must be {shape}, got {tuple(t.shape)}")
+    if valid is not None and tuple(valid.shape) != (shape[0], F):
+        raise ValueError(f"pose_supervision: valid must be [{shape[0]},{F}], got {tuple(valid.shape)}")
+    weights = [float(F - f) for f in range(F)] if frame_weight is None else [float(w) for w in frame_weight]
+    if len(weights) != F:
+        raise ValueError(f"pose_supervision: {F} frame weights expected, got {len(weights)}")
+    _require_cuda(*T_pred, *T_gt, valid)
+    f32 = lambda t: t.float().contiguous()
+    head, records = _PoseSupervisionFn.apply([f32(t).detach() for t in T_gt], None if valid is None else f32(valid).detach(),
+                                             weights, bool(details), *[f32(t) for t in T_pred])
+    r_loss, t_loss, total = head.unbind(0)
+    return (r_loss, t_loss, total, records) if details else (r_loss, t_loss, total)
+
+
 # ------------------------------------------------------------------ multi-frame cost volume (csrc/matching.hip)
 COST_VOLUME_MAX_BINS = 128
 

@@ -15,7 +15,9 @@ tail and the training steps are host-bound and are timed per call (one event pai
     matrices, and the backward of all that -- with its kernel count from the same profiler;
   * with ``--step`` one training step of a Trainer in the pose-network mode next to one in the known-pose mode (synthetic
     items).
-One JSON line per size, printed and written to ``--out`` (default: profiles/pose.log)."""
+One JSON line per size, printed and written to ``--out`` (default: profiles/pose.log).  ``--loss`` times the pose supervision
+instead (time_loss: pd_pose_loss_fwd / _bwd at N = 12 and 16, F = 2, next to the same loss with torch ops; default log
+profiles/pose_loss.log)."""
 import argparse
 import json
 import os
@@ -136,16 +138,72 @@ def time_head(N, H, W, iters):
         torch.cuda.synchronize()
         out[name] = timer(call, iters)[0]
 
-    def kernels_of(call):
-        from torch.profiler import profile, ProfilerActivity
-        with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
-            call()
-            torch.cuda.synchronize()
-        return sum(e.count for e in prof.key_averages() if getattr(e, "device_type", None) is not None
-                   and "cuda" in str(e.device_type).lower())
     return {"head_plane": [h, w], "pose_head_fwd_ms": round(out["fwd"], 4), "pose_head_bwd_ms": round(out["bwd"], 4),
-            "pose_head_kernels": kernels_of(lambda: (fwd(), bwd())), "torch_tail_fwd_bwd_ms": round(out["torch"], 4),
-            "torch_tail_kernels": kernels_of(torch_tail), "torch_ratio": round(out["torch"] / (out["fwd"] + out["bwd"]), 1)}
+            "pose_head_kernels": _kernels_of(lambda: (fwd(), bwd())), "torch_tail_fwd_bwd_ms": round(out["torch"], 4),
+            "torch_tail_kernels": _kernels_of(torch_tail), "torch_ratio": round(out["torch"] / (out["fwd"] + out["bwd"]), 1)}
+
+
+def _kernels_of(call):
+    import torch
+    from torch.profiler import profile, ProfilerActivity
+    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+        call()
+        torch.cuda.synchronize()
+    return sum(e.count for e in prof.key_averages() if getattr(e, "device_type", None) is not None
+               and "cuda" in str(e.device_type).lower())
+
+
+def time_loss(N, F, iters):
+    """pd_pose_loss_fwd + pd_pose_loss_bwd (csrc/pose_loss.hip) for F frames of N poses next to the same loss written with
+    torch ops on the device under autograd (tests/pose_loss_ref.py: torch_rotvec / torch_pose_loss, float32 there), with the
+    number of kernels torch's profiler counts for one forward + backward of each.  The two kernels are timed in windows of 20
+    queued calls, the host-bound torch chain per call."""
+    import ctypes
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pose_loss_ref
+    from polardepth import ops
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    mats = lambda: [ops.pose_matrix(1.5 * (torch.rand((N, 3), generator=gen, device="cuda") - 0.5),
+                                    0.1 * torch.randn((N, 3), generator=gen, device="cuda"), invert=bool(f & 1))
+                    for f in range(F)]
+    Tp, Tg = mats(), mats()
+    valid = torch.ones((N, F), device="cuda")
+    vals = torch.empty(3 + 2 * F, device="cuda")
+    gvals = torch.ones(3, device="cuda")
+    gT = [torch.empty_like(t) for t in Tp]
+    arr = lambda ts: (ctypes.c_void_p * F)(*[t.data_ptr() for t in ts])
+    pp, pg, pgT = arr(Tp), arr(Tg), arr(gT)
+    w = (ctypes.c_float * F)(*[float(F - f) for f in range(F)])
+
+    def fwd():
+        check(lib.pd_pose_loss_fwd(pp, pg, F, w, ptr(valid), None, ptr(vals), N, stream_ptr()), "pd_pose_loss_fwd")
+
+    def bwd():
+        check(lib.pd_pose_loss_bwd(ptr(gvals), pp, pg, F, w, ptr(valid), pgT, N, stream_ptr()), "pd_pose_loss_bwd")
+    leaves = [t.detach().clone().requires_grad_(True) for t in Tp]
+
+    def op():
+        ops.pose_supervision(leaves, Tg, valid=valid)[2].backward()
+        for t in leaves:
+            t.grad = None
+
+    def torch_chain():
+        pose_loss_ref.torch_pose_loss(leaves, Tg)[2].backward()
+        for t in leaves:
+            t.grad = None
+    out = {}
+    for name, call, timer in (("fwd", fwd, _queued_ms), ("bwd", bwd, _queued_ms), ("op", op, _median_ms),
+                              ("torch", torch_chain, _median_ms)):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        out[name] = timer(call, iters)[0]
+    return {"op": "pose_loss", "N": N, "F": F, "pose_loss_fwd_ms": round(out["fwd"], 4), "pose_loss_bwd_ms": round(out["bwd"], 4),
+            "pose_loss_kernels": _kernels_of(lambda: (fwd(), bwd())), "pose_supervision_fwd_bwd_ms": round(out["op"], 4),
+            "pose_supervision_kernels": _kernels_of(op), "torch_loss_fwd_bwd_ms": round(out["torch"], 4),
+            "torch_loss_kernels": _kernels_of(torch_chain), "torch_ratio": round(out["torch"] / (out["fwd"] + out["bwd"]), 1)}
 
 
 def _step_ms(N, H, W, iters, pose_network):
@@ -181,13 +239,24 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=12)
     ap.add_argument("--step", action="store_true", help="also time one step of the pose-network and of the known-pose mode")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose.log"), help="the log; '' = print only")
+    ap.add_argument("--loss", action="store_true", help="time the pose supervision (pd_pose_loss_fwd / _bwd) instead: N = 12 "
+                    "and 16, F = 2, next to the same loss with torch ops; the default log is then profiles/pose_loss.log")
+    ap.add_argument("--out", default=None, help="the log (default profiles/pose.log, with --loss profiles/pose_loss.log); "
+                    "'' = print only")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pose_loss.log" if args.loss else "pose.log")
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("bench_pose needs the GPU; there is no CPU fallback")
     log = open(args.out, "w") if args.out else None
-    for N, H, W in SIZES:
+    for N, _, _ in SIZES if args.loss else ():
+        line = json.dumps(time_loss(N, 2, args.iters))
+        print(line, flush=True)
+        if log:
+            log.write(line + "\n")
+            log.flush()
+    for N, H, W in () if args.loss else SIZES:
         row = {"op": "pose_network_kernels", "N": N, "H": H, "W": W}
         row.update(time_warp(N, H, W, args.iters))
         row.update(time_head(N, H, W, args.iters))

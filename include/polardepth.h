@@ -704,6 +704,31 @@ int pd_pose_head_bwd(const void* gT, const void* gT_inv, const void* gaxisangle,
                      const void* axisangle, const void* translation, const void* w, const void* mean, void* gx, void* gw,
                      void* gb, void* gpre_ws, int N, int h, int wd, int Cin, int Co, int invert, int accumulate, void* stream);
 
+/* pd_pose_chain -- the matching-pose half of predict_poses (trainer.py:708-746): the poses 0 -> fi of a chain of L
+ * consecutive frames in ONE launch, forward only (the reference runs it under no_grad).
+ *   axisangle, translation  [L,N,3] fp32: link k is the pose network's slot-0 output for the pair (frame s (k+1), frame s k)
+ *                           stacked in temporal order, s = direction (-1: the past frames -1, -2, ...; +1: the future ones)
+ *   present                 [L,N] fp32, or NULL = all present: 0 means frame s (k+1) of item n does not exist
+ *   init                    [N,4,4] fp32, or NULL: the pose 0 -> frame 0 of the chain to continue from (streaming use)
+ *   rel, rel_inv            [L,N,4,4] fp32 out ("=")
+ * Per item n, k ascending:
+ *   M_k    = pd_pose_matrix_fwd(axisangle[k], translation[k], invert = (s < 0)), rounded to fp32 exactly as there
+ *            (trainer.py:718-719, 731-732);  Minv_k the same with invert flipped (:720-721, 733-734)
+ *   A_k    = M_k A_{k-1} (:725, 738), A_{-1} = init; without init A_0 = M_0.  Each entry is
+ *            ((m_i0 a_0c + m_i1 a_1c) + m_i2 a_2c) + m_i3 a_3c in fp64 from the fp32 values of M_k and of the STORED A_{k-1}
+ *            (what rel[k-1] holds, or init), no fused multiply-add, rounded once
+ *   rel[k] = A_k where present[k][n] != 0, else sixteen 0.0f -- and the next link multiplies those zeros: the reference
+ *            stores the zeroed pose and reads it back (:725, 741-745).  A zero therefore travels down the chain by
+ *            arithmetic alone; a NaN pose stays NaN, in its own item only.
+ *   rel_inv[k] = Minv_k: the link's OWN inverse, neither chained nor zeroed.  This is what the reference stores in
+ *            ("relative_pose_inv", fi) (:720-721, 746) -- a quirk kept on purpose; it is not the inverse of rel[k] for k > 0.
+ * One thread per item walks the links (64-thread groups); no atomics, no host synchronisation, capturable.
+ * Limits: 1 <= L <= PD_POSE_CHAIN_MAX_LINKS, N >= 1, direction -1 or 1; anything else, or a NULL among axisangle,
+ * translation, rel, rel_inv, is PD_EINVAL before any launch. */
+#define PD_POSE_CHAIN_MAX_LINKS 8
+int pd_pose_chain(const void* axisangle, const void* translation, const void* present, const void* init, void* rel,
+                  void* rel_inv, int L, int N, int direction, void* stream);
+
 /* Pose supervision and the records of the pose evaluator (csrc/pose_loss.hip): --supervise_pose of trainer.py:1267-1285, the
  * predicted cam_T_cam against the ground-truth relative pose, rotations compared as rotation vectors.
  *

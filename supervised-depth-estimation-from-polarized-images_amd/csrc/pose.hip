@@ -117,6 +117,56 @@ __global__ __launch_bounds__(64) void pose_matrix_bwd_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------ matching poses: all links of a chain, one thread per item
+// The second half of predict_poses (trainer.py:708-746): rel[k] = M_k A_{k-1} with A_{-1} = init (or A_0 = M_0), each entry
+// ((m_i0 a_0c + m_i1 a_1c) + m_i2 a_2c) + m_i3 a_3c in fp64 from the fp32 values of M_k and of the STORED A_{k-1}, rounded
+// once; an absent frame stores sixteen zeros, which the next link multiplies.  rel_inv[k] is the link's own inverse.  The
+// stored matrix stays in registers between the links: what is multiplied is what was written.
+__global__ __launch_bounds__(64) void pose_chain_kernel(const float* __restrict__ aa, const float* __restrict__ tr,
+                                                        const float* __restrict__ present, const float* __restrict__ init,
+                                                        float* __restrict__ rel, float* __restrict__ rel_inv, int L, int N,
+                                                        int invert) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;
+    float A[16], M[16], Mi[16];
+    bool have = init != nullptr;
+    if (have) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) A[e] = init[16L * n + e];
+    }
+    for (int k = 0; k < L; ++k) {
+        const long i = (long)k * N + n;
+        const double a[3] = {(double)aa[3 * i], (double)aa[3 * i + 1], (double)aa[3 * i + 2]};
+        const double t[3] = {(double)tr[3 * i], (double)tr[3 * i + 1], (double)tr[3 * i + 2]};
+        pose_matrix(a, t, invert, M);
+        pose_matrix(a, t, !invert, Mi);
+        if (have) {
+            float P[16];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    P[4 * r + c] = (float)((((double)M[4 * r] * (double)A[c] + (double)M[4 * r + 1] * (double)A[4 + c]) +
+                                            (double)M[4 * r + 2] * (double)A[8 + c]) + (double)M[4 * r + 3] * (double)A[12 + c]);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) A[e] = P[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) A[e] = M[e];
+            have = true;
+        }
+        if (present && present[i] == 0.f) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) A[e] = 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            rel[16 * i + e] = A[e];
+            rel_inv[16 * i + e] = Mi[e];
+        }
+    }
+}
+
 // ------------------------------------------------------------------ decoder tail, one workgroup per item
 using pd_wave::wave_sum;
 
@@ -252,6 +302,19 @@ extern "C" int pd_pose_matrix_bwd(const void* gT, const void* axisangle, const v
     hipLaunchKernelGGL(pose_matrix_bwd_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)gT,
                        (const float*)axisangle, (const float*)translation, (float*)gaxisangle, (float*)gtranslation, N, invert);
     return pd::check_launch("pd_pose_matrix_bwd");
+}
+
+extern "C" int pd_pose_chain(const void* axisangle, const void* translation, const void* present, const void* init, void* rel,
+                             void* rel_inv, int L, int N, int direction, void* stream) {
+    PD_REQUIRE(axisangle && translation && rel && rel_inv,
+               "pd_pose_chain: axisangle, translation, rel and rel_inv must not be null");
+    PD_REQUIRE(L >= 1 && L <= PD_POSE_CHAIN_MAX_LINKS, "pd_pose_chain: 1 .. %d links, got L=%d", PD_POSE_CHAIN_MAX_LINKS, L);
+    PD_REQUIRE(N >= 1, "pd_pose_chain: bad item count N=%d", N);
+    PD_REQUIRE(direction == -1 || direction == 1, "pd_pose_chain: direction must be -1 or 1, got %d", direction);
+    hipLaunchKernelGGL(pose_chain_kernel, dim3((N - 1) / 64 + 1), dim3(64), 0, (hipStream_t)stream, (const float*)axisangle,
+                       (const float*)translation, (const float*)present, (const float*)init, (float*)rel, (float*)rel_inv, L, N,
+                       direction < 0 ? 1 : 0);
+    return pd::check_launch("pd_pose_chain");
 }
 
 static int pose_head_args(const char* who, int N, int h, int w, int Cin, int Co, int invert) {

@@ -18,6 +18,7 @@ from polardepth import normals_eval
 from polardepth import depth_eval
 from polardepth import pointcloud
 from polardepth import pose_eval
+from polardepth import matching as pdmatching
 from polardepth._lib import lib, check, ptr, stream_ptr
 
 _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, "teapot": 120, "cutlery": 140,
@@ -28,7 +29,8 @@ class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
-                 pol_calibration=None, normals_decoder=None, pose_network=None):
+                 pol_calibration=None, normals_decoder=None, pose_network=None, multi_frame=False, matching_ids=(0, -1),
+                 multi_poses="files", num_depth_bins=96, depth_binning="linear"):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -49,7 +51,26 @@ class Evaluation:
         ``test_normals``); None reads $PD_NORMALS_DECODER == "1", as the Trainer does.  ``pose_network``: also build the pose
         network (``pose_encoder``, ``pose``) as the Trainer's ``opt.pose_network`` mode does, and a second loader that serves
         the neighbouring frames -1 and 1 with their ground-truth poses (``test_pose``); None reads $PD_POSE_NETWORK == "1".
-        Without it the object is what it was: the same models, the same draws, the same loader."""
+        Without it the object is what it was: the same models, the same draws, the same loader.
+
+        ``multi_frame=True``: multi-frame depth inference, e.g. from a student checkpoint the reference trained
+        (``encoder.pth``, ``depth.pth``, ``pose_encoder.pth``, ``pose.pth``).  Two more models, constructed AFTER every
+        existing one (which therefore draw what they drew): ``encoder`` = ResnetEncoderMatching(18, False, height, width,
+        adaptive_bins=True, ``num_depth_bins``, ``depth_binning``) with the bins of ``min_depth`` / ``max_depth`` until a
+        checkpoint says otherwise, and ``depth`` = DepthDecoder.  ``matching_ids``: 0 and the lookup frames, as the
+        reference's ``matching_ids`` (-1 .. -Ln, 1 .. Lp without gaps).  ``multi_poses``: where the sweep's poses come from --
+        "files": the loader's ground-truth ``("poses", i)``; "network": the pose network's, composed link by link
+        (``polardepth.matching.matching_poses``), which implies ``pose_network=True``.  A third loader
+        (``multi_loader``) serves frame 0 and the lookup frames, with ``need_poses`` only for "files".  See
+        ``predict_multi``, ``test_depth(source="multi")``; ``test_pose_chain`` needs the pose network only."""
+        if multi_poses not in ("files", "network"):
+            raise ValueError(f'multi_poses must be "files" or "network", got {multi_poses!r}')
+        self.multi_frame, self.multi_poses = bool(multi_frame), multi_poses
+        self.matching_ids = [int(i) for i in matching_ids]
+        if self.multi_frame:
+            pdmatching.chain_pairs(self.matching_ids)
+            if multi_poses == "network":
+                pose_network = True
         data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
         load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
         if data_path is None:
@@ -96,6 +117,12 @@ class Evaluation:
             self.models["pose_encoder"] = networks.ResnetEncoder(18, False, num_input_images=2)
             self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc, num_input_features=1,
                                                        num_frames_to_predict_for=2)
+        if self.multi_frame:                      # last: the models above draw what they drew without them
+            self.models["encoder"] = networks.ResnetEncoderMatching(18, False, height, width, min_depth_bin=self.min_depth,
+                                                                    max_depth_bin=self.max_depth,
+                                                                    num_depth_bins=num_depth_bins, adaptive_bins=True,
+                                                                    depth_binning=depth_binning)
+            self.models["depth"] = networks.DepthDecoder(self.models["encoder"].num_ch_enc, self.scales)
         for m in self.models.values():
             m.to(self.device).eval()
         # evaluation.py:96 reads ../splits (cwd = manydepth/); the repository root works too
@@ -119,16 +146,35 @@ class Evaluation:
             pose_ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0] + self.pose_frame_ids, 4, is_train=False,
                                               supervised_depth_only=False, need_poses=True)
             self.pose_loader = DataLoader(pose_ds, batch_size, False, num_workers=num_workers, drop_last=True)
+        self._loader_args = (data_path, files, num_workers)
+        self._chain_loaders = {}
+        if self.multi_frame:
+            # an absent lookup frame arrives as a zero picture with frame_valid 0 (and the identity as its pose: predict_multi
+            # hands the sweep an all-zero pose instead); with "files" a frame counts only with both pose files
+            multi_ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0] + self.matching_ids[1:], 4, is_train=False,
+                                               supervised_depth_only=False, need_poses=(multi_poses == "files"))
+            self.multi_loader = DataLoader(multi_ds, batch_size, False, num_workers=num_workers, drop_last=True)
 
     def load_mono_model(self):
         if self.load_weights_folder is None:
             return
         for n, m in self.models.items():
             path = os.path.join(self.load_weights_folder, f"{n}.pth")
-            # weights of a run without the variant / without the pose network: the module keeps its initialisation
-            if n in ("normals_decoder", "pose_encoder", "pose") and not os.path.isfile(path):
+            # weights of a run without the variant / without the pose network / without the multi-frame student: the module
+            # keeps its initialisation
+            if n in ("normals_decoder", "pose_encoder", "pose", "encoder", "depth") and not os.path.isfile(path):
                 continue
             sd = torch.load(path, map_location="cpu")
+            if n == "encoder":
+                # what the reference's save_model adds to encoder.pth (trainer.py:1607-1613), handled as its load_model
+                # does (:1665-1675): the tracked depth range recomputes the bins, the size must be ours, and none of the four
+                # reaches load_state_dict
+                extra = {k: sd.pop(k) for k in ("height", "width", "min_depth_bin", "max_depth_bin") if k in sd}
+                for k, own in (("height", self.height), ("width", self.width)):
+                    if k in extra and int(extra[k]) != own:
+                        raise ValueError(f"encoder.pth was trained at {k} {int(extra[k])}, this Evaluation runs at {own}")
+                if extra.get("min_depth_bin") is not None and extra.get("max_depth_bin") is not None:
+                    m.compute_depth_bins(float(extra["min_depth_bin"]), float(extra["max_depth_bin"]))
             m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()})
 
     @torch.no_grad()
@@ -161,6 +207,38 @@ class Evaluation:
         if with_normals_pred and "normals_decoder" in self.models:
             out["normals_pred"] = self.models["normals_decoder"](nf)
         return out
+
+    @torch.no_grad()
+    def predict_multi(self, inputs):
+        """Multi-frame depth (``multi_frame=True``): {"depth" [N,1,H,W], "lowest_cost" [N,H/4,W/4] (the disparity of the
+        cheapest bin), "confidence" [N,H/4,W/4] (0/1)}.  The current frame is ("color_aug", 0, 0), the lookup frames the
+        stacked ("color", i, 0) of ``matching_ids[1:]``, the intrinsics ("K", 2) / ("inv_K", 2) (the cost volume's quarter
+        resolution).  The poses are ("poses", i) times ("frame_valid", i) with ``multi_poses="files"``, or the pose network's
+        chain (``matching_poses`` on the ("color", i, 0) frames, the loader's ``frame_valid`` as ``present``) with
+        "network": either way an absent frame reaches the sweep as an ALL-ZERO pose, which it skips -- the loader's identity
+        pose would have its black picture matched.  Then the matching encoder, the decoder, and pd_disp_to_depth and the
+        clamp as ``predict`` ends."""
+        if not self.multi_frame:
+            raise ValueError("predict_multi needs Evaluation(multi_frame=True)")
+        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        ids = self.matching_ids
+        lookups = torch.stack([inputs[("color", i, 0)].float() for i in ids[1:]], 1)
+        if self.multi_poses == "network":
+            rel, _ = pdmatching.matching_poses(self.models["pose_encoder"], self.models["pose"],
+                                               {i: inputs[("color", i, 0)] for i in ids}, ids,
+                                               {i: inputs[("frame_valid", i)] for i in ids[1:]})
+            poses = torch.stack([rel[i] for i in ids[1:]], 1)
+        else:
+            poses = torch.stack([inputs[("poses", i)].float() * inputs[("frame_valid", i)].float().view(-1, 1, 1)
+                                 for i in ids[1:]], 1)
+        feats, lowest_cost, confidence = self.models["encoder"](inputs[("color_aug", 0, 0)].float(), lookups, poses,
+                                                                inputs[("K", 2)].float(), inputs[("inv_K", 2)].float())
+        disp = self.models["depth"](feats)[("disp", 0)].contiguous()
+        N = disp.shape[0]
+        depth = torch.empty((N, 1, self.height, self.width), device=disp.device)
+        check(lib.pd_disp_to_depth(ptr(disp), ptr(depth), None, N, disp.shape[2], disp.shape[3], self.height, self.width,
+                                   self.min_depth, self.max_depth, stream_ptr()), "pd_disp_to_depth")
+        return {"depth": depth.clamp(self.min_depth, self.max_depth), "lowest_cost": lowest_cost, "confidence": confidence}
 
     def test(self):
         """evaluation.py:120-288: mean over images of the 7 masked depth metrics, for the whole frame and per material
@@ -232,7 +310,7 @@ class Evaluation:
         return results
 
     @torch.no_grad()
-    def test_depth(self, median_scaling=None):
+    def test_depth(self, median_scaling=None, source="mono"):
         """Depth accuracy per class in one pass (polardepth.depth_eval): what ``test`` reports -- and the pooled figures, the
         distribution of the absolute error and the count of unusable predictions -- for the whole frame, all objects and each
         material, one pd_depth_stats call per batch.  ``median_scaling``: None, or "numpy" / "torch" to rescale the prediction
@@ -241,11 +319,16 @@ class Evaluation:
         rmse_log, a1, a2, a3, the mean and the median of |d| in millimetres, the shares of |d| below 5 / 10 / 20 mm and the
         pixel count: "per_image" is the mean over images of the per-image figures (the reference's and ``test``'s convention;
         images without a pixel of the class do not count), "pooled" takes all pixels of all images as one set.  The records
-        stay on the device until the loop is over."""
+        stay on the device until the loop is over.  ``source``: "mono" scores ``predict`` over the test loader, "multi"
+        (``multi_frame=True``) ``predict_multi`` over the loader that also serves the lookup frames -- the same scoring."""
+        if source not in ("mono", "multi"):
+            raise ValueError(f'source must be "mono" or "multi", got {source!r}')
+        if source == "multi" and not self.multi_frame:
+            raise ValueError('source="multi" needs Evaluation(multi_frame=True)')
         total, sums, counts = None, None, None
-        for inputs in self.test_loader:
+        for inputs in (self.multi_loader if source == "multi" else self.test_loader):
             inputs = {k: v.to(self.device) for k, v in inputs.items()}
-            depth = self.predict(inputs)
+            depth = self.predict_multi(inputs)["depth"] if source == "multi" else self.predict(inputs)
             st = depth_eval.depth_stats(depth, inputs["depth_gt"], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
                                         max_depth=self.max_depth, median_scaling=median_scaling)
             m = st.metrics()
@@ -308,6 +391,38 @@ class Evaluation:
         if not records:
             return {}
         results = pose_eval.metrics_from_records(torch.cat(records, 1), torch.cat(valids, 0), ids)
+        print(pose_eval.format_report(results))
+        return results
+
+    @torch.no_grad()
+    def test_pose_chain(self, num_links=3):
+        """The drift of the composition: the pose network's chained poses 0 -> -1, .., 0 -> -num_links
+        (``polardepth.matching.matching_poses`` on the un-jittered frames) against the ground-truth ``("poses", fi)``, scored
+        per frame id exactly as ``test_pose`` scores single pairs (the same records and figures; its return value with the
+        chain's frame ids as keys).  The loader (frames 0, -1, .., -num_links, ``need_poses=True``) is built on first use.  A
+        chain counts down to its first missing frame: from there on its poses are all zero and its pairs ``missing``."""
+        if not self.pose_network:
+            raise ValueError("test_pose_chain needs Evaluation(pose_network=True) (or PD_POSE_NETWORK=1)")
+        ids = [0] + list(range(-1, -1 - int(num_links), -1))
+        pdmatching.chain_pairs(ids)
+        if num_links not in self._chain_loaders:
+            data_path, files, num_workers = self._loader_args
+            ds = datasets.HAMMER_Dataset(data_path, files, self.height, self.width, ids, 4, is_train=False,
+                                         supervised_depth_only=False, need_poses=True)
+            self._chain_loaders[num_links] = DataLoader(ds, self.batch_size, False, num_workers=num_workers, drop_last=True)
+        records, valids = [], []
+        for inputs in self._chain_loaders[num_links]:
+            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+            pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+            present = {i: inputs[("frame_valid", i)].float() for i in ids[1:]}
+            rel, _ = pdmatching.matching_poses(self.models["pose_encoder"], self.models["pose"],
+                                               {i: inputs[("color", i, 0)] for i in ids}, ids, present)
+            valid = torch.cumprod(torch.stack([present[i] for i in ids[1:]], 1), 1)
+            records.append(pose_eval.pair_records([rel[i] for i in ids[1:]], [inputs[("poses", i)] for i in ids[1:]], valid))
+            valids.append(valid)
+        if not records:
+            return {}
+        results = pose_eval.metrics_from_records(torch.cat(records, 1), torch.cat(valids, 0), ids[1:])
         print(pose_eval.format_report(results))
         return results
 

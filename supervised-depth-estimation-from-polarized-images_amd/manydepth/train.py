@@ -51,6 +51,10 @@ def options_from_environment(opts, env=os.environ):
     # flag that could select it here, since --pose_input False alone keeps its present meaning
     if env.get("PD_POSE_NETWORK") == "1":
         opts.pose_network = True
+    # PD_MATCHING_POSES=1: with the pose network, also the matching-pose half of predict_poses -- the poses 0 -> fi of the
+    # lookup frames of --num_matching_frames / --use_future_frame into inputs[("relative_pose", fi)] (opt.matching_poses)
+    if env.get("PD_MATCHING_POSES") == "1":
+        opts.matching_poses = True
     return opts
 
 

@@ -19,9 +19,17 @@ captured yet (``PD_STEP_GRAPH=1`` is refused with it).  With ``opt.pose_network 
 ``--depth_supervision True`` without ``--depth_supervision_only`` and without ``--pose_input``) the poses of that term are
 PREDICTED: ``pose_encoder`` (ResnetEncoder, two stacked frames) and ``pose`` (PoseDecoder) see the jittered frame pair of
 every neighbour in temporal order (trainer.py:222-236, 669-707), their output goes through transformation_from_parameters into
-the same warp, and the term trains depth and pose together; ``--res_pose`` and the matching-pose half
-of predict_poses are not built, and ``PD_STEP_GRAPH=1`` / ``opt.bf16`` / ``torch.distributed`` are refused with it; its loaders
-take a neighbour's picture without asking for pose files (``HAMMER_Dataset(need_poses=False)``).  ``--supervise_pose`` (only
+the same warp, and the term trains depth and pose together; ``--res_pose`` is not built, and ``PD_STEP_GRAPH=1`` /
+``opt.bf16`` / ``torch.distributed`` are refused with it; its loaders
+take a neighbour's picture without asking for pose files (``HAMMER_Dataset(need_poses=False)``).  ``opt.matching_poses = True``
+(``PD_MATCHING_POSES=1``; only with the pose network, else ValueError) adds the matching-pose half of predict_poses
+(trainer.py:708-746): ``matching_ids`` from ``--num_matching_frames`` / ``--use_future_frame`` as trainer.py:131-137 forms them,
+loaders that serve ``frame_ids`` plus the matching ids not among them (appended at the end), and after every ``predict_poses``
+``inputs[("relative_pose", fi)]`` -- the pose 0 -> fi composed link by link from the jittered frames, all zeros from a missing
+frame on -- and ``inputs[("relative_pose_inv", fi)]`` -- the link's own inverse, as the reference stores it -- without a tape
+(``polardepth.matching.matching_poses``: one pose-network pass per id, one pd_pose_chain launch per direction).  Nothing in a
+training step consumes them yet; ``frame_ids`` keeps its meaning for the photometric term and the pose supervision, and
+without the option nothing changes in a bit.  ``--supervise_pose`` (only
 with the pose network; trainer.py:1267-1285) adds the predicted ``cam_T_cam`` against the ground-truth relative pose,
 rotations compared as rotation vectors (``roma.rotmat_to_rotvec``, restated in csrc/pose_loss.hip: one launch forward, one
 backward, for all frames): ``r_loss`` / ``t_loss`` are the plain sums over the frames, and what joins ``loss`` (after the
@@ -60,6 +68,7 @@ from polardepth import cdofp as pdcdofp
 from polardepth import calibration as pdcal
 from polardepth import color as pdcolor
 from polardepth import ops
+from polardepth import matching as pdmatching
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -152,6 +161,12 @@ class Trainer:
             if torch.distributed.is_available() and torch.distributed.is_initialized():
                 raise NotImplementedError("torch.distributed with opt.pose_network: the gradient reducer expects one "
                                           "backward pass per module and step; run this mode on one GPU")
+        # the matching-pose half of predict_poses (trainer.py:708-746): the pose network's poses 0 -> fi of the cost volume's
+        # lookup frames, composed link by link (polardepth.matching.matching_poses, csrc/pose.hip: one launch per
+        # direction).  Not a reference CLI flag: ``opt.matching_poses = True`` (manydepth/train.py maps PD_MATCHING_POSES=1)
+        self.matching_poses = bool(getattr(self.opt, "matching_poses", False))
+        if self.matching_poses and not self.pose_network:
+            raise ValueError("opt.matching_poses: the matching poses are the pose network's; it needs opt.pose_network")
         # --supervise_pose (trainer.py:1267-1285): the predicted cam_T_cam against the ground-truth relative pose of
         # ``_pose/%06d.txt``, one launch for all frames (polardepth.ops.pose_supervision, csrc/pose_loss.hip)
         self.supervise_pose = bool(self.pose_network and getattr(self.opt, "supervise_pose", False))
@@ -167,6 +182,15 @@ class Trainer:
         if self.photometric and (self.frame_ids[0] != 0 or len(self.frame_ids) < 2 or 0 in self.frame_ids[1:]
                                  or len(self.frame_ids) - 1 > ops.REPROJ_MAX_FRAMES):
             raise ValueError(f"--frame_ids {self.frame_ids}: 0 first, then 1 .. {ops.REPROJ_MAX_FRAMES} neighbouring frames")
+        # trainer.py:128-137: the frames the loaders serve are frame_ids plus the matching ids not among them, appended at
+        # the end (a synthetic item draws its neighbours in this order: the existing ones keep their draws).  frame_ids keeps
+        # its meaning for the photometric term and for pose supervision
+        self.frames_to_load = list(self.frame_ids)
+        if self.matching_poses:
+            self.matching_ids = [0] + ([1] if self.opt.use_future_frame else []) + \
+                list(range(-1, -1 - int(self.opt.num_matching_frames), -1))
+            pdmatching.chain_pairs(self.matching_ids)          # ValueError for what the chain cannot take (no frame, too many)
+            self.frames_to_load += [i for i in self.matching_ids if i not in self.frames_to_load]
         local_rank = int(os.environ.get("LOCAL_RANK", 0))
         self.device = torch.device("cuda", local_rank)
         torch.cuda.set_device(self.device)
@@ -275,7 +299,7 @@ class Trainer:
         train_files = [self.opt.overfit_scene] if self.opt.overfit else _split(self.opt.split, "train", self.data_path)
         val_files = [self.opt.overfit_scene] if self.opt.overfit else _split(self.opt.split, "val", self.data_path)
         test_files = _split(self.opt.eval_split, "test", self.data_path_val)
-        mk = lambda path, files, tr: self.dataset(path, files, self.opt.height, self.opt.width, self.frame_ids, 4, is_train=tr,
+        mk = lambda path, files, tr: self.dataset(path, files, self.opt.height, self.opt.width, self.frames_to_load, 4, is_train=tr,
                                                   img_ext='.png', offset=self.opt.offset, modality=self.opt.modality,
                                                   supervised_depth=True, supervised_depth_only=not self.photometric,
                                                   depth_modality=self.opt.depth_modality, lookup_aug=self.pose_network,
@@ -501,6 +525,17 @@ class Trainer:
             axisangle, translation, T, T_inv = self.models["pose"].forward_with_matrices([feats], invert=f_i < 0)
             outputs[("axisangle", 0, f_i)], outputs[("translation", 0, f_i)] = axisangle, translation
             outputs[("cam_T_cam", 0, f_i)], outputs[("cam_T_cam_inv", 0, f_i)] = T, T_inv
+        if self.matching_poses:
+            # the second half (trainer.py:708-746), without a tape: inputs[("relative_pose", fi)] = the pose 0 -> fi of every
+            # matching frame, all zeros from a missing frame on, and ("relative_pose_inv", fi) = the LINK's inverse, as the
+            # reference stores it.  The jittered frames, as there; the loader's frame_valid stands for its feat.sum() == 0.
+            # Nothing in a training step consumes them yet (the cost-volume student's branch is not built)
+            ids = self.matching_ids
+            rel, rel_inv = pdmatching.matching_poses(self.models["pose_encoder"], self.models["pose"],
+                                                     {i: inputs[("color_aug", i, 0)] for i in ids}, ids,
+                                                     {i: inputs[("frame_valid", i)] for i in ids[1:]})
+            for i in ids[1:]:
+                inputs[("relative_pose", i)], inputs[("relative_pose_inv", i)] = rel[i], rel_inv[i]
         return outputs
 
     def compute_losses(self, inputs, outputs, is_multi=False):

@@ -138,6 +138,7 @@ SIGNATURES = {
     "pd_pose_matrix_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "pd_pose_head_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pd_pose_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "pd_pose_chain": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pd_pose_loss_fwd": (_i, [_vpp, _vpp, _i, _c.POINTER(_f), _vp, _vp, _vp, _i, _vp]),
     "pd_pose_loss_bwd": (_i, [_vp, _vpp, _vpp, _i, _c.POINTER(_f), _vp, _vpp, _i, _vp]),
     "pd_depth_to_updisp_bwd": (_i, [_vp, _vp, _vp, _l, _f, _f, _vp]),

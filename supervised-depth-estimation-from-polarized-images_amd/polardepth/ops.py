@@ -591,6 +591,43 @@ def pose_head(x, weight, bias, invert=False):
                              bool(invert))
 
 
+POSE_CHAIN_MAX_LINKS = 8      # PD_POSE_CHAIN_MAX_LINKS
+
+
+def pose_chain(axisangle, translation, present=None, init=None, direction=-1):
+    """The matching-pose half of predict_poses (trainer.py:708-746) for one direction in one launch (pd_pose_chain;
+    include/polardepth.h states the arithmetic).  ``axisangle`` / ``translation`` [L,N,3] (or [L,N,1,3]): link k is the pose
+    network's slot-0 output for the frames ``direction * (k+1)`` and ``direction * k`` stacked in temporal order;
+    ``present`` [L,N]: 0 where frame ``direction * (k+1)`` of an item does not exist; ``init`` [N,4,4]: the pose to continue
+    from.  Returns ``(rel, rel_inv)`` [L,N,4,4]: ``rel[k]`` is the pose 0 -> frame ``direction * (k+1)`` -- all zeros from an
+    absent frame on --, ``rel_inv[k]`` the link's OWN inverse, neither chained nor zeroed (the reference's
+    ``relative_pose_inv``).  Forward only: the results carry no tape.  CPU tensors and wrong shapes are a ValueError."""
+    for t in (axisangle, translation, present, init):
+        if t is not None and not t.is_cuda:
+            raise ValueError("pose_chain: polardepth ops need CUDA(HIP) tensors; there is no CPU fallback")
+    if direction not in (-1, 1):
+        raise ValueError(f"pose_chain: direction must be -1 or 1, got {direction!r}")
+    if axisangle.dim() < 3 or axisangle.shape[0] < 1 or axisangle.shape[1] < 1:
+        raise ValueError(f"pose_chain: axisangle must be [L,N,3] or [L,N,1,3], got {tuple(axisangle.shape)}")
+    L, N = axisangle.shape[:2]
+    if L > POSE_CHAIN_MAX_LINKS:
+        raise ValueError(f"pose_chain: 1 .. {POSE_CHAIN_MAX_LINKS} links, got {L}")
+    for name, t in (("axisangle", axisangle), ("translation", translation)):
+        if tuple(t.shape) not in ((L, N, 3), (L, N, 1, 3)):
+            raise ValueError(f"pose_chain: {name} must be [{L},{N},3] or [{L},{N},1,3], got {tuple(t.shape)}")
+    if present is not None and tuple(present.shape) != (L, N):
+        raise ValueError(f"pose_chain: present must be [{L},{N}], got {tuple(present.shape)}")
+    if init is not None and tuple(init.shape) != (N, 4, 4):
+        raise ValueError(f"pose_chain: init must be [{N},4,4], got {tuple(init.shape)}")
+    f = lambda t: None if t is None else t.detach().float().contiguous()
+    aa, tr, present, init = f(axisangle), f(translation), f(present), f(init)
+    rel = torch.empty((L, N, 4, 4), dtype=torch.float32, device=aa.device)
+    rel_inv = torch.empty_like(rel)
+    check(lib.pd_pose_chain(ptr(aa), ptr(tr), ptr(present), ptr(init), ptr(rel), ptr(rel_inv), L, N, int(direction),
+                            stream_ptr()), "pd_pose_chain")
+    return rel, rel_inv
+
+
 # ------------------------------------------------------------------ pose supervision (csrc/pose_loss.hip)
 def _frame_weights(w):
     import ctypes

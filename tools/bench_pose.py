@@ -17,7 +17,8 @@ tail and the training steps are host-bound and are timed per call (one event pai
     items).
 One JSON line per size, printed and written to ``--out`` (default: profiles/pose.log).  ``--loss`` times the pose supervision
 instead (time_loss: pd_pose_loss_fwd / _bwd at N = 12 and 16, F = 2, next to the same loss with torch ops; default log
-profiles/pose_loss.log)."""
+profiles/pose_loss.log).  ``--chain`` times the matching-pose chain instead (time_chain: pd_pose_chain at N = 12 and 16, L = 1
+and 3, next to the reference's chain with torch ops and its host synchronisations; default log profiles/pose_chain.log)."""
 import argparse
 import json
 import os
@@ -206,6 +207,53 @@ def time_loss(N, F, iters):
             "torch_loss_kernels": _kernels_of(torch_chain), "torch_ratio": round(out["torch"] / (out["fwd"] + out["bwd"]), 1)}
 
 
+def time_chain(N, H, W, L, iters):
+    """pd_pose_chain (csrc/pose.hip) for a chain of L past frames of N items next to the reference's chain restated with
+    torch ops (trainer.py:713-746): per link both transformation_from_parameters, the matmul with the stored pose, and the
+    Python loop over the batch with ``feat.sum() == 0`` per item -- one host synchronisation each, over pictures of the
+    training size.  The kernel is timed in windows of 20 queued calls, the host-bound torch chain per call; the kernel counts
+    are torch's profiler's for one call of each."""
+    import torch
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    aa = 0.3 * (torch.rand((L, N, 3), generator=gen, device="cuda") - 0.5)
+    tr = 0.1 * torch.randn((L, N, 3), generator=gen, device="cuda")
+    pics = torch.rand((L, N, 3, H, W), generator=gen, device="cuda")
+    pics[L - 1, N // 2] = 0                                          # one missing frame
+    present = (pics.reshape(L, N, -1).sum(2) != 0).float()
+    rel, rel_inv = torch.empty((L, N, 4, 4), device="cuda"), torch.empty((L, N, 4, 4), device="cuda")
+
+    def kernel():
+        check(lib.pd_pose_chain(ptr(aa), ptr(tr), ptr(present), None, ptr(rel), ptr(rel_inv), L, N, -1, stream_ptr()),
+              "pd_pose_chain")
+    state = {}
+
+    def torch_chain():
+        prev = None
+        for k in range(L):
+            pose = _torch_matrix(aa[k][:, None], tr[k][:, None], True)
+            state["inv"] = _torch_matrix(aa[k][:, None], tr[k][:, None], False)
+            if prev is not None:
+                pose = torch.matmul(pose, prev)
+            for b, feat in enumerate(pics[k]):
+                if feat.sum() == 0:
+                    pose[b] *= 0
+            prev = pose
+        state["rel"] = prev
+    out = {}
+    for name, call, timer in (("kernel", kernel, _queued_ms), ("torch", torch_chain, _median_ms)):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        out[name] = timer(call, iters)
+    err = float((state["rel"] - rel[L - 1]).abs().max())
+    return {"op": "pose_chain", "N": N, "L": L, "H": H, "W": W, "pose_chain_ms": round(out["kernel"][0], 4),
+            "pose_chain_min_max": [round(v, 4) for v in out["kernel"][1:]], "pose_chain_kernels": _kernels_of(kernel),
+            "torch_chain_ms": round(out["torch"][0], 4), "torch_chain_kernels": _kernels_of(torch_chain),
+            "torch_chain_host_syncs": L * N, "torch_ratio": round(out["torch"][0] / out["kernel"][0], 1),
+            "max_abs_diff_last_link": err}
+
+
 def _step_ms(N, H, W, iters, pose_network):
     import torch
     from manydepth.options import MonodepthOptions
@@ -241,22 +289,33 @@ if __name__ == "__main__":
     ap.add_argument("--step", action="store_true", help="also time one step of the pose-network and of the known-pose mode")
     ap.add_argument("--loss", action="store_true", help="time the pose supervision (pd_pose_loss_fwd / _bwd) instead: N = 12 "
                     "and 16, F = 2, next to the same loss with torch ops; the default log is then profiles/pose_loss.log")
-    ap.add_argument("--out", default=None, help="the log (default profiles/pose.log, with --loss profiles/pose_loss.log); "
-                    "'' = print only")
+    ap.add_argument("--chain", action="store_true", help="time the matching-pose chain (pd_pose_chain) instead: N = 12 and 16, "
+                    "L = 1 and 3, next to the reference's chain with torch ops; the default log is then profiles/pose_chain.log")
+    ap.add_argument("--out", default=None, help="the log (default profiles/pose.log, with --loss profiles/pose_loss.log, with "
+                    "--chain profiles/pose_chain.log); '' = print only")
     args = ap.parse_args()
+    if args.loss and args.chain:
+        ap.error("--loss and --chain are two runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "pose_loss.log" if args.loss else "pose.log")
+        args.out = os.path.join(ROOT, "profiles", "pose_loss.log" if args.loss else "pose_chain.log" if args.chain else "pose.log")
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("bench_pose needs the GPU; there is no CPU fallback")
     log = open(args.out, "w") if args.out else None
+    for N, H, W in SIZES if args.chain else ():
+        for L in (1, 3):
+            line = json.dumps(time_chain(N, H, W, L, args.iters))
+            print(line, flush=True)
+            if log:
+                log.write(line + "\n")
+                log.flush()
     for N, _, _ in SIZES if args.loss else ():
         line = json.dumps(time_loss(N, 2, args.iters))
         print(line, flush=True)
         if log:
             log.write(line + "\n")
             log.flush()
-    for N, H, W in () if args.loss else SIZES:
+    for N, H, W in () if args.loss or args.chain else SIZES:
         row = {"op": "pose_network_kernels", "N": N, "H": H, "W": W}
         row.update(time_warp(N, H, W, args.iters))
         row.update(time_head(N, H, W, args.iters))

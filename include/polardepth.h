@@ -1113,6 +1113,90 @@ int pd_depth_stats(const void* gt, const void* pred, const void* mask, const int
                    const void* edges, void* err, void* stats, void* workspace, size_t ws_bytes, int N, int H, int W,
                    float min_depth, float max_depth, void* stream);
 
+/* Multi-view depth consistency per pixel class (csrc/consistency.hip): do the depth maps of neighbouring frames describe
+ * the same surface once the camera motion between them is taken into account?  The forward-backward reprojection check of
+ * MVSNet's geometric filter (Yao et al., ECCV 2018, sec. 4.2), scored per class of the instance mask in one read of the batch.
+ * It needs no ground-truth depth.  tests/consistency_ref.py states the definition in NumPy, in the order written here.
+ *
+ * depth0       fp32 [N,H,W]     depth of the current view
+ * depths       fp32 [N,F,H,W]   depth of each source view, 1 <= F <= PD_REPROJ_MAX_FRAMES
+ * T            fp32 [N,F,4,4]   rigid motion from view 0 to view f (a point X of camera 0 is R X + t in camera f)
+ * K, inv_K     fp32 [N,4,4]
+ * frame_valid  fp32 [N,F] or NULL (every view present)
+ * visible      uint8 [N,F,H,W] or NULL: a 0 takes the (pixel, view) pair out of the comparison
+ * mask         int32 [N,H,W] or NULL; classes HOST int[n_classes][2] as in pd_normals_stats (lo > hi = every pixel; a ranged
+ *              class needs a mask); 1 <= n_classes <= PD_DSTAT_MAX_CLASSES
+ * tau_px, tau_rel   HOST double[3], loose -> tight: positive, finite, non-increasing.  The defaults of the Python layer are
+ *              (4, 0.04), (2, 0.02), (1, 0.01); the tightest pair is MVSNet's filter.
+ * fuse_level   2, 3 or 4: the level a view must reach to enter n_cons and fused
+ *
+ * Every step is fp64 unless fp32 is stated; the file is built with -ffp-contract=off; the camera pieces are those of
+ * csrc/view_geom.hpp (cam_P, cam_iK, ray, project_ray, axis_of, Bilinear), whose comments give their order of operations.
+ * With in(d) = (d >= min_depth && d <= max_depth) in fp32 (NaN fails), pixel (x, y) of item n and view f get exactly ONE
+ * outcome, tested in this order:
+ *   1 invalid    !in(d0), d0 = depth0[n][y][x]
+ *   2 absent     frame_valid[n][f] == 0
+ *   3 filtered   visible given and visible[n][f][y][x] == 0
+ *   4 outside    (forward leg)  P = cam_P(K_n, T_nf), r = ray(inv_K_n, x, y), project_ray(P, r, (double)d0) -> (u, v, hz);
+ *                uf = (float)u, vf = (float)v, rounded ONCE.  Outside unless hz > 1e-3 && 0 <= uf <= W-1 && 0 <= vf <= H-1
+ *                (the last four in fp32; NaN fails).
+ *   5 hole       ax = axis_of(uf, W), ay = axis_of(vf, H); the taps v00 = D[ay.i0][ax.i0], v10 = D[ay.i0][ax.i1],
+ *                v01 = D[ay.i1][ax.i0], v11 = D[ay.i1][ax.i1] of D = depths[n][f].  A hole unless in() holds for all four;
+ *                otherwise d1 = Bilinear(ax.w1, ay.w1).blend(v00, v10, v01, v11) in fp32.
+ *   6 outside    (return leg)  R = T[:3,:3], t = T[:3,3] widened to fp64; Ti = [R^T | -(R^T t)] with
+ *                (R^T t)[i] = (R[0][i] t0 + R[1][i] t1) + R[2][i] t2 and the last row (0, 0, 0, 1);
+ *                P'[i][j] = ((K[i][0] Ti[0][j] + K[i][1] Ti[1][j]) + K[i][2] Ti[2][j]) + K[i][3] Ti[3][j] (cam_P's order on
+ *                doubles); r' = ray(inv_K_n, (double)uf, (double)vf): the ray of the FRACTIONAL pixel;
+ *                project_ray(P', r', (double)d1) -> (u2, v2, hz2).  Outside unless hz2 > 1e-3.
+ *   7 compared   du = u2 - x, dv = v2 - y; e2 = du du + dv dv; e_px = sqrt(e2); e_rel = |hz2 - d0| / d0.  hz2 carries
+ *                project_ray's + 1e-7, as every depth that function returns.  Level j (0 loose, 1 mid, 2 tight) is met when
+ *                e2 < tau_px[j] tau_px[j] && e_rel < tau_rel[j]; no square root takes part in a decision.
+ *
+ * stats: [N][n_classes] records pooled over the F views, written whole by every call; byte offsets:
+ *      0  int64   n           the compared pairs (the sum of the bins)
+ *      8  int64   loose       compared pairs that meet level 0  (the levels are nested: loose >= mid >= tight)
+ *     16  int64   mid         ... level 1
+ *     24  int64   tight       ... level 2
+ *     32  int64   invalid
+ *     40  int64   absent
+ *     48  int64   filtered
+ *     56  int64   outside     either leg
+ *     64  int64   hole
+ *     72  double  sum e_px
+ *     80  double  sum e_rel
+ *     88  double  sum e2      (e_px squared, before the root)
+ *     96  double  sum e_rel e_rel
+ *    104  8 bytes of zero
+ *    112  uint32  hist[256]   bin = min((int)floor(e_rel * 1024), 255): width 1/1024, the last bin open
+ * n + invalid + absent + filtered + outside + hole = (pixels of the class) * F.  The integer fields are exact.  The sums are
+ * bit-reproducible: a lane adds the terms of one pixel over f ascending (from 0), adds that to the pixel's classes, and
+ * takes its pixels in increasing order; lanes, waves and workgroups follow in the fixed order of csrc/class_records.hpp.
+ *
+ * Per-pixel outputs, each NULL or:
+ *   level   uint8 [N,F,H,W]   0 = not compared; 1 = compared, no level met; 2, 3, 4 = the tightest level met (loose, mid, tight)
+ *   n_cons  uint8 [N,H,W]     the number of views with level >= fuse_level
+ *   fused   fp32  [N,H,W]     (float)((d0 + sum hz2_f) / (1 + n_cons)) over those views, summed in fp64 with f ascending
+ *                             starting from d0, rounded once; on an invalid pixel n_cons = 0 and fused = 0
+ * A work item is a pixel, its lane loops over the views: the outputs are written with plain stores by the lane that owns
+ * the pixel.  A workgroup belongs to one image and holds P, P' and inv_K of its F views in LDS.  Three launches per 2^20
+ * images; the call neither synchronises, allocates nor reads the environment and can be captured into a graph.
+ * workspace: >= pd_depth_consistency_workspace(N, H, W, n_classes) bytes (never 0, a multiple of 16, monotone), 16-byte
+ * aligned.  N == 0 returns PD_OK after the checks.  Every refusal is PD_EINVAL with a message, decided before the device is
+ * touched: those of pd_depth_stats (null pointers, bad shape, n_classes outside 1 .. 16, a ranged class with mask == NULL,
+ * !(min_depth > 0), !(max_depth > min_depth), stats / workspace not 16-byte aligned, a too-small workspace, a frame beyond
+ * 2^30 pixels), F outside 1 .. PD_REPROJ_MAX_FRAMES, thresholds that are not positive and finite or not nested, fuse_level
+ * outside 2 .. 4. */
+#define PD_CONS_BINS         256      /* bins of e_rel, 1/1024 wide, the last one open-ended */
+#define PD_CONS_COUNTERS     8        /* loose, mid, tight, invalid, absent, filtered, outside, hole */
+#define PD_CONS_SUMS         4
+#define PD_CONS_RECORD_BYTES 1136     /* 112 + 4 * 256 */
+size_t pd_depth_consistency_workspace(int N, int H, int W, int K);
+int pd_depth_consistency(const void* depth0, const void* depths, const void* T, const void* K, const void* inv_K,
+                         const void* frame_valid, const void* visible, const void* mask, const int* classes, int n_classes,
+                         float min_depth, float max_depth, const double* tau_px, const double* tau_rel, int fuse_level,
+                         void* level, void* n_cons, void* fused, void* stats, void* workspace, size_t ws_bytes, int N, int F,
+                         int H, int W, void* stream);
+
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward
  * dp[r][:] <- scale * p * (dp - sum(dp * p)).  The score GEMMs (Q K^T, P V and their gradients) are pd_conv2d /

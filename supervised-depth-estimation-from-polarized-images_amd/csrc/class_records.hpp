@@ -1,5 +1,5 @@
-// Per-image, per-class records: what pd_normals_stats (normals_stats.hip), pd_cloud_stats (pointcloud.hip) and pd_depth_stats
-// (depth_stats.hip) share.
+// Per-image, per-class records: what pd_normals_stats (normals_stats.hip), pd_cloud_stats (pointcloud.hip), pd_depth_stats
+// (depth_stats.hip) and pd_depth_consistency (consistency.hip) share.
 //
 // A record is: int64 n, `Counters` further int64 counters, `Sums` fp64 sums (two unless the evaluator asks for more), padding
 // to 16 bytes, a uint32 histogram of `Bins` bins (Layout).  An evaluator fills its [N][K] records in three launches (run_records):

@@ -1,9 +1,10 @@
-// The camera geometry of the multi-view kernels (csrc/reproj.hip, csrc/matching.hip): a pixel of the current view at a
-// depth to its coordinates (u, v) in a source view, and the bilinear taps there.  Each expression is written here once, its
-// order of operations in the comment above it; the files are built with -ffp-contract=off, so no product is fused into a
-// sum and two kernels that call the same piece produce the same bits.  (u, v) are source PIXEL coordinates
-// (align_corners=True).  What becomes of a tap outside the image is the caller's rule: clamped (axis_of: grid_sample's
-// "border") or the sample dropped (matching.hip: "zeros" plus the edge mask).
+// The camera geometry of the multi-view kernels (csrc/reproj.hip, csrc/matching.hip, csrc/consistency.hip): a pixel of the
+// current view at a depth to its coordinates (u, v) in a source view, and the bilinear taps there.  Each expression is
+// written here once, its order of operations in the comment above it; the files are built with -ffp-contract=off, so no
+// product is fused into a sum and two kernels that call the same piece produce the same bits.  (u, v) are source PIXEL
+// coordinates (align_corners=True).  What becomes of a tap outside the image is the caller's rule: clamped (axis_of:
+// grid_sample's "border"), the sample dropped (matching.hip: "zeros" plus the edge mask) or the pair not compared
+// (consistency.hip).
 // Camera operands are references to arrays: called on __shared__ arrays they stay LDS reads after inlining.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +25,11 @@ __device__ __forceinline__ double cam_iK(const float* iK, long n, int q) { retur
 // r[i] = (iK[i][0] x + iK[i][1] y) + iK[i][2]
 __device__ __forceinline__ void ray(const double (&iK)[9], int x, int y, double (&r)[3]) {
     const double xd = (double)x, yd = (double)y;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] = (iK[3 * i] * xd + iK[3 * i + 1] * yd) + iK[3 * i + 2];
+}
+// the same at a FRACTIONAL pixel (csrc/consistency.hip: the return leg starts where the forward leg landed)
+__device__ __forceinline__ void ray(const double (&iK)[9], double xd, double yd, double (&r)[3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) r[i] = (iK[3 * i] * xd + iK[3 * i + 1] * yd) + iK[3 * i + 2];
 }

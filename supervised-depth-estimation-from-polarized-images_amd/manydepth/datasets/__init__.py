@@ -55,6 +55,14 @@ jittered, when it is blank or when it is missing); synthetic items get the same 
 ``need_poses=False`` (opt-in; the Trainer's pose-network mode, where the poses are predicted): a neighbour is present as
 soon as its picture exists, whether or not the tree has ``_pose/``; ``("poses", i)`` is then the identity unless both pose
 files exist.
+``neighbour_items=True`` (opt-in; ``Evaluation.test_consistency``, which runs the network on the neighbours too): every
+neighbour ``i`` also arrives as ``inputs[("neighbour", i)]``, the complete single-frame item dict of the frame ``idx + i *
+offset`` -- what a ``frame_idxs=[0]`` dataset with the same options returns for it (evaluation items draw nothing; a training
+item's neighbours draw their own augmentation after frame 0's).  Where that frame is not one of the dataset's complete frames,
+or ``("frame_valid", i)`` is 0, it is a zero item with the same keys, shapes and dtypes, and ``("frame_valid", i)`` is 0.
+Default collation stacks the nested dicts.  Synthetic items get the same keys: the same scene as the camera moved by
+``("poses", i)`` sees it (its depth maps are consistent with frame 0's under that pose), drawn after every other draw of the
+item.  Without the switch an item is what it was, key for key and bit for bit.
 """
 import glob
 import os
@@ -98,8 +106,11 @@ class HAMMER_Dataset(Dataset):
     def __init__(self, data_path, filenames, height, width, frame_idxs, num_scales, is_train=False, img_ext='.png',
                  offset=10, modality="polarization", supervised_depth=True, supervised_depth_only=True,
                  depth_modality="_gt", items_per_scene=8, raw_pol=None, raw_color=None, pol_native=None,
-                 pol_dofp=None, pol_cdofp=None, lookup_aug=False, need_poses=True):
+                 pol_dofp=None, pol_cdofp=None, lookup_aug=False, need_poses=True, neighbour_items=False):
         super().__init__()
+        # neighbour_items: every neighbour also arrives as ("neighbour", i), its complete single-frame item (module docstring).
+        # Off: an item is what it was, bit for bit.
+        self.neighbour_items = bool(neighbour_items)
         # need_poses: a neighbouring frame counts as present only with both ``_pose/%06d.txt`` files (the known-pose mode).
         # False (the Trainer's pose-network mode, which predicts the poses): the picture alone decides ("frame_valid", i),
         # so sequences that ship no pose files train.  Default: an item is what it was, bit for bit.
@@ -154,6 +165,7 @@ class HAMMER_Dataset(Dataset):
                                         f"{depth_modality}) under "
                                         f"{data_path!r} for scenes {self.filenames[:3]}...")
             self.items = len(self.frames)
+        self._complete = set(self.frames)
 
     # ---- real HAMMER tree -------------------------------------------------------------------------------
     def _discover(self, scenes):
@@ -170,8 +182,9 @@ class HAMMER_Dataset(Dataset):
                     frames.append((folder, idx))
         return frames
 
-    def _load_item(self, folder, idx):
+    def _load_item(self, folder, idx, neighbours=None):
         from PIL import Image
+        neighbours = self.neighbours if neighbours is None else neighbours
         H, W = self.height, self.width
         name = "{:06d}{}".format(idx, self.img_ext)
         to_t = lambda im: torch.from_numpy(np.asarray(im, dtype=np.float32).transpose(2, 0, 1) / 255.0)
@@ -237,8 +250,17 @@ class HAMMER_Dataset(Dataset):
             inputs[("inv_K", s)] = torch.from_numpy(np.linalg.pinv(K))
         inputs["stereo_T"] = torch.eye(4)
         inputs["stereo_T"][0, 3] = -0.0498921
-        for i in self.neighbours:                 # indoor_dataset.py:311-366: a missing neighbour is a dummy, not an error
+        single = list(inputs) if self.neighbour_items else None      # the keys of a single-frame item
+        for i in neighbours:                      # indoor_dataset.py:311-366: a missing neighbour is a dummy, not an error
             inputs.update(self._neighbour(folder, idx, i, jitter))
+        if self.neighbour_items:
+            for i in neighbours:
+                other = idx + i * self.offset
+                if float(inputs[("frame_valid", i)]) != 0.0 and (folder, other) in self._complete:
+                    inputs[("neighbour", i)] = self._load_item(folder, other, neighbours=())
+                else:
+                    inputs[("neighbour", i)] = {k: torch.zeros_like(inputs[k]) for k in single}
+                    inputs[("frame_valid", i)] = torch.tensor(0.0, dtype=torch.float32)
         return inputs
 
     @staticmethod
@@ -319,6 +341,39 @@ class HAMMER_Dataset(Dataset):
     # ---- synthetic items --------------------------------------------------------------------------------
     def _synthetic_item(self, index):
         rng = np.random.default_rng(index)
+        inputs = self._synthetic_frame(rng, index)
+        self._synthetic_neighbours(rng, inputs)
+        if self.neighbour_items:                  # after every other draw: the item above is what it is without them
+            for i in self.neighbours:
+                inputs[("neighbour", i)] = self._synthetic_frame(rng, index, inputs[("poses", i)].numpy().astype(np.float64))
+        return inputs
+
+    def _synthetic_surface_from(self, index, T):
+        """The depth surface of item ``index`` (frame 0's formula, without its holes) as the camera moved by ``T`` sees it,
+        [H,W] float64: per pixel the depth d at which the point d r, taken back to frame 0, lies on the surface -- Newton
+        steps on g(d) = z0(d) - surface(x0(d), y0(d)) with a difference quotient (g' stays within (0.2, 1.8) for the small
+        motions drawn here)."""
+        H, W = self.height, self.width
+        K = np.eye(3)
+        K[0, 0] = K[1, 1] = 0.65 * W; K[0, 2] = W / 2; K[1, 2] = H / 2
+        yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+        r = np.einsum("ij,jhw->ihw", np.linalg.inv(K), np.stack([xx, yy, np.ones_like(xx)]))
+        Ti = np.linalg.inv(T)
+
+        def g(d):
+            X0 = np.einsum("ij,jhw->ihw", Ti[:3, :3], d * r) + Ti[:3, 3, None, None]
+            x, y = K[0, 0] * X0[0] / X0[2] + K[0, 2], K[1, 1] * X0[1] / X0[2] + K[1, 2]
+            return X0[2] - (1.05 + 0.7 * np.sin(x / (W / 7.0) + index) * np.cos(y / (H / 5.0)))
+        d = np.full((H, W), 1.05)
+        for _ in range(10):
+            g0 = g(d)
+            d = d - g0 * 1e-4 / (g(d + 1e-4) - g0)
+        return d
+
+    def _synthetic_frame(self, rng, index, pose=None):
+        """One single-frame item from ``rng``'s next draws.  ``pose`` None: frame 0 of item ``index``; else the same scene
+        from the camera moved by ``pose`` ([4,4] float64): its own pictures, mask and holes, and the depth of frame 0's
+        surface as that camera sees it, so that the two depth maps are consistent under the pose."""
         H, W = self.height, self.width
         inputs = {}
         color = rng.random((3, H, W), dtype=np.float32)
@@ -331,7 +386,10 @@ class HAMMER_Dataset(Dataset):
             inputs[("K", s)] = torch.from_numpy(K)
             inputs[("inv_K", s)] = torch.from_numpy(np.linalg.pinv(K))
         yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
-        depth = 1.05 + 0.7 * np.sin(xx / (W / 7.0) + index) * np.cos(yy / (H / 5.0))
+        if pose is None:
+            depth = 1.05 + 0.7 * np.sin(xx / (W / 7.0) + index) * np.cos(yy / (H / 5.0))
+        else:
+            depth = self._synthetic_surface_from(index, pose)
         depth[rng.random((H, W)) < 0.1] = 0
         inputs["depth"] = torch.from_numpy(depth[None].astype(np.float32))
         inputs["depth_gt"] = inputs["depth"].clone()
@@ -343,8 +401,13 @@ class HAMMER_Dataset(Dataset):
         pol = np.clip(np.rint(pol + rng.normal(0, 1.5, pol.shape)), 0, 255).astype(np.uint8)
         inputs[("pol", 0, 0)] = torch.from_numpy(pol)
         inputs["stereo_T"] = torch.eye(4)
+        return inputs
+
+    def _synthetic_neighbours(self, rng, inputs):
         # neighbouring frames (drawn after every draw above, so frame 0 is what it is without them): a small rigid motion and a
         # smooth colour picture -- frame 0's colour is white noise, so the term measures nothing here; it has to run and be finite
+        H, W = self.height, self.width
+        yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
         for i in self.neighbours:
             rot, t = rng.uniform(-0.01, 0.01, 3), np.array([0.03 * i, 0.0, 0.0]) + rng.uniform(-0.01, 0.01, 3)
             cx, sx = np.cos(rot[0]), np.sin(rot[0]); cy, sy = np.cos(rot[1]), np.sin(rot[1]); cz, sz = np.cos(rot[2]), np.sin(rot[2])

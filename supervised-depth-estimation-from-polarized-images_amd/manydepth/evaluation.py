@@ -18,6 +18,7 @@ from polardepth import normals_eval
 from polardepth import depth_eval
 from polardepth import pointcloud
 from polardepth import pose_eval
+from polardepth import consistency_eval
 from polardepth import matching as pdmatching
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -148,6 +149,7 @@ class Evaluation:
             self.pose_loader = DataLoader(pose_ds, batch_size, False, num_workers=num_workers, drop_last=True)
         self._loader_args = (data_path, files, num_workers)
         self._chain_loaders = {}
+        self._consistency_loaders = {}
         if self.multi_frame:
             # an absent lookup frame arrives as a zero picture with frame_valid 0 (and the identity as its pose: predict_multi
             # hands the sweep an all-zero pose instead); with "files" a frame counts only with both pose files
@@ -424,6 +426,79 @@ class Evaluation:
             return {}
         results = pose_eval.metrics_from_records(torch.cat(records, 1), torch.cat(valids, 0), ids[1:])
         print(pose_eval.format_report(results))
+        return results
+
+    @torch.no_grad()
+    def test_consistency(self, ids=(-1, 1), visible="auto", per_view=False):
+        """Multi-view consistency of the predicted depth per class (polardepth.consistency_eval; the reference reports none):
+        ``predict`` runs on frame 0 and on every neighbour of ``ids``, and one pd_depth_consistency call per batch asks
+        whether the depth maps describe the same surface under the loader's ``("poses", i)``.  The figure needs no
+        ground-truth depth.  ``visible``: "auto" limits the score to the pairs the ground-truth depths of both frames say
+        are mutually visible (``consistency_eval.visibility``), so that a true occlusion does not count as an inconsistency;
+        None scores every pair -- occlusions then count, and the medians are the robust figures.  The loader (frames 0 and
+        ``ids``, ``need_poses=True``, ``neighbour_items=True``) is built on first use; a neighbour that is missing arrives
+        with ``frame_valid`` 0 and its pairs are ``absent``.  Prints the table for the whole frame, all objects and each
+        material, and returns {class: {"pooled": [14] (consistency_eval.METRIC_NAMES), "n": int, "counters": int64 [8],
+        "sums": float64 [4], "hist": int64 [256]}} over all pairs of the test set; with ``per_view`` also one table per
+        id, from F = 1 calls, under "views": {id: {class: ...}}.  The records stay on the device until the loop is over."""
+        if visible not in ("auto", None):
+            raise ValueError(f'visible must be "auto" or None, got {visible!r}')
+        ids = tuple(int(i) for i in ids)
+        if not ids or 0 in ids or len(ids) > consistency_eval.MAX_FRAMES:
+            raise ValueError(f"ids must name 1 .. {consistency_eval.MAX_FRAMES} neighbouring frames, got {ids!r}")
+        if ids not in self._consistency_loaders:
+            data_path, files, num_workers = self._loader_args
+            ds = datasets.HAMMER_Dataset(data_path, files, self.height, self.width, [0] + list(ids), 4, is_train=False,
+                                         supervised_depth_only=False, need_poses=True, neighbour_items=True)
+            self._consistency_loaders[ids] = DataLoader(ds, self.batch_size, False, num_workers=num_workers, drop_last=True)
+        to_dev = lambda d: {k: to_dev(v) if isinstance(v, dict) else v.to(self.device) for k, v in d.items()}
+        total, views = None, {i: None for i in ids}
+        for inputs in self._consistency_loaders[ids]:
+            inputs = to_dev(inputs)
+            depth0 = self.predict(inputs)
+            depths = torch.cat([self.predict(inputs[("neighbour", i)]) for i in ids], 1)
+            T = torch.stack([inputs[("poses", i)] for i in ids], 1)
+            valid = torch.stack([inputs[("frame_valid", i)] for i in ids], 1).float()
+            K, inv_K = inputs[("K", 0)], inputs[("inv_K", 0)]
+            kw = dict(mask=inputs[("mask", 0, 0)], min_depth=self.min_depth, max_depth=self.max_depth)
+            vis = None
+            if visible == "auto":
+                gts = torch.cat([inputs[("neighbour", i)]["depth_gt"] for i in ids], 1)
+                vis = consistency_eval.visibility(inputs["depth_gt"], gts, T, K, inv_K, frame_valid=valid,
+                                                  min_depth=self.min_depth, max_depth=self.max_depth)
+            st = consistency_eval.consistency(depth0, depths, T, K, inv_K, frame_valid=valid, visible=vis, want=(), **kw)
+            if total is None:
+                total = st
+            else:
+                total += st
+            if per_view:
+                for f, i in enumerate(ids):
+                    sv = consistency_eval.consistency(depth0, depths[:, f:f + 1], T[:, f:f + 1], K, inv_K,
+                                                      frame_valid=valid[:, f:f + 1],
+                                                      visible=None if vis is None else vis[:, f:f + 1], want=(), **kw)
+                    if views[i] is None:
+                        views[i] = sv
+                    else:
+                        views[i] += sv
+        if total is None:
+            return {}
+
+        def table(pool, title):
+            n, counters, sums, hist = (t.cpu().numpy() for t in pool._totals())
+            pooled = pool.pooled().cpu().numpy()
+            nm = len(consistency_eval.METRIC_NAMES)
+            print(f"consistency ({title}) " + ("{:>11} " * nm).format(*consistency_eval.METRIC_NAMES))
+            out = {}
+            for k, name in enumerate(pool.names):
+                out[name] = {"pooled": pooled[k], "n": int(n[k]), "counters": counters[k], "sums": sums[k], "hist": hist[k]}
+                if n[k] > 0:
+                    print(f"{name:>8} pooled    " + ("&{: 11.4f} " * nm).format(*pooled[k].tolist()))
+            return out
+
+        how = "mutually visible pairs" if visible == "auto" else "all pairs"
+        results = table(total, f"views {list(ids)}, {how}")
+        if per_view:
+            results["views"] = {i: table(views[i], f"view {i}, {how}") for i in ids}
         return results
 
     @torch.no_grad()

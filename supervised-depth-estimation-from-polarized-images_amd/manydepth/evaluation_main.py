@@ -1,7 +1,8 @@
 """reference manydepth/evaluation_main.py:7-10; PD_EVAL_NORMALS=1 adds the surface-normal report (Evaluation.test_normals),
 PD_EVAL_POINTCLOUD=1 the point-cloud report (Evaluation.test_pointcloud), PD_EVAL_DEPTH=1 the one-pass depth report
 (Evaluation.test_depth), median-scaled with PD_EVAL_MEDIAN_SCALING=numpy or torch, PD_EVAL_POSE=1 the pose report of the
-pose network (Evaluation.test_pose; needs PD_POSE_NETWORK=1, which makes Evaluation build and load the pose network)."""
+pose network (Evaluation.test_pose; needs PD_POSE_NETWORK=1, which makes Evaluation build and load the pose network),
+PD_EVAL_CONSISTENCY=1 the multi-view consistency report of the predicted depth (Evaluation.test_consistency)."""
 import os
 
 from manydepth.evaluation import Evaluation
@@ -19,6 +20,8 @@ def main():
         ev.test_depth(median_scaling=os.environ.get("PD_EVAL_MEDIAN_SCALING") or None)
     if os.environ.get("PD_EVAL_POSE") == "1":
         ev.test_pose()
+    if os.environ.get("PD_EVAL_CONSISTENCY") == "1":
+        ev.test_consistency()
 
 
 if __name__ == "__main__":

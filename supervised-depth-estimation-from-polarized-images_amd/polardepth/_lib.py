@@ -162,6 +162,9 @@ SIGNATURES = {
     "pd_depth_medians": (_i, [_vp, _vp, _vp, _ip, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
     "pd_depth_stats_workspace": (_sz, [_i, _i, _i, _i]),
     "pd_depth_stats": (_i, [_vp, _vp, _vp, _ip, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
+    "pd_depth_consistency_workspace": (_sz, [_i, _i, _i, _i]),
+    "pd_depth_consistency": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _i, _f, _f, _dp, _dp, _i, _vp, _vp, _vp, _vp,
+                                  _vp, _sz, _i, _i, _i, _i, _vp]),
 }
 
 

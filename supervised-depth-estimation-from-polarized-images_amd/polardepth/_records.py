@@ -1,4 +1,5 @@
-"""What the wrappers of the per-class record evaluators (normals_eval, pointcloud; csrc/class_records.hpp) share: the cached
+"""What the wrappers of the per-class record evaluators (normals_eval, pointcloud, depth_eval, consistency_eval;
+csrc/class_records.hpp) share: the cached
 bin-edge table of a device, the input checks, the histogram median and the device-side pool."""
 import torch
 

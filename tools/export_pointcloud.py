@@ -4,7 +4,10 @@ truth), binary little-endian PLY coloured by ("color", 0, 0), y and z negated as
 
     python tools/export_pointcloud.py --data_path /data/HAMMER --weights /runs/x/models/weights_19 --index 0 --out clouds/
 
-``--data_path synthetic`` serves a seeded synthetic item; without ``--weights`` the networks keep their initialisation."""
+``--data_path synthetic`` serves a seeded synthetic item; without ``--weights`` the networks keep their initialisation.
+``--consistent M`` writes only the predicted points that at least M of the neighbouring frames -1 and 1 confirm (their
+predicted depth maps agree with this one at MVSNet's thresholds under the loader's poses: ``n_cons >= M`` of
+``polardepth.consistency_eval.consistency``), at the depth fused over the confirming views instead of the single prediction."""
 import argparse
 import os
 import sys
@@ -13,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarized-images_amd"))
 
 
-def export(data_path, weights, index, out, height=320, width=480, flip=True):
+def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None):
     import torch
     from torch.utils.data.dataloader import default_collate
     from manydepth.evaluation import Evaluation
@@ -27,7 +30,11 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True):
     colour = inputs[("color", 0, 0)][0].float()                        # [3,H,W] in 0 .. 1, before predict expands the batch
     depth = ev.predict(inputs)
     gt, K = inputs["depth_gt"], inputs[("K", 0)]
-    clouds = {"pred": pc.backproject(depth, K, gate=gt, min_depth=ev.min_depth, max_depth=ev.max_depth),
+    if consistent is not None:
+        depth, gt_gate = consistent_depth(ev, index, depth, gt, int(consistent))
+    else:
+        gt_gate = gt
+    clouds = {"pred": pc.backproject(depth, K, gate=gt_gate, min_depth=ev.min_depth, max_depth=ev.max_depth),
               "gt": pc.backproject(gt, K, min_depth=ev.min_depth, max_depth=ev.max_depth)}
     rgb = (colour.permute(1, 2, 0).reshape(-1, 3) * 255).round().clamp(0, 255).to(torch.uint8).cpu()
     os.makedirs(out, exist_ok=True)
@@ -40,6 +47,27 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True):
     return written
 
 
+def consistent_depth(ev, index, depth, gt, M, ids=(-1, 1)):
+    """(the fused depth [1,1,H,W], the ground-truth gate with the pixels of n_cons < M emptied) for test item ``index``."""
+    import torch
+    from torch.utils.data.dataloader import default_collate
+    from manydepth import datasets
+    from polardepth import consistency_eval as ce
+    if not 1 <= M <= len(ids):
+        raise ValueError(f"--consistent {M}: there are {len(ids)} neighbouring frames")
+    data_path, files, _ = ev._loader_args
+    ds = datasets.HAMMER_Dataset(data_path, files, ev.height, ev.width, [0] + list(ids), 4, is_train=False,
+                                 supervised_depth_only=False, need_poses=True, neighbour_items=True)
+    to_dev = lambda d: {k: to_dev(v) if isinstance(v, dict) else v.to(ev.device) for k, v in d.items()}
+    item = to_dev(default_collate([ds[index]]))
+    depths = torch.cat([ev.predict(item[("neighbour", i)]) for i in ids], 1)
+    st = ce.consistency(depth, depths, torch.stack([item[("poses", i)] for i in ids], 1), item[("K", 0)], item[("inv_K", 0)],
+                        frame_valid=torch.stack([item[("frame_valid", i)] for i in ids], 1), classes=(("all", None),),
+                        min_depth=ev.min_depth, max_depth=ev.max_depth, fuse_level=4, want=("n_cons", "fused"))
+    keep = (st.n_cons >= M)[:, None]
+    return st.fused[:, None], torch.where(keep, gt, torch.zeros_like(gt))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_path", required=True)
@@ -49,6 +77,9 @@ if __name__ == "__main__":
     ap.add_argument("--height", type=int, default=320)
     ap.add_argument("--width", type=int, default=480)
     ap.add_argument("--no_flip", action="store_true", help="keep the camera frame (y down, z forward)")
+    ap.add_argument("--consistent", type=int, default=None, metavar="M",
+                    help="keep the predicted points that M neighbouring frames confirm, at the fused depth")
     args = ap.parse_args()
-    for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip).items():
+    for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip,
+                          args.consistent).items():
         print(f"{path}: {n} points")

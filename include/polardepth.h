@@ -1197,6 +1197,99 @@ int pd_depth_consistency(const void* depth0, const void* depths, const void* T, 
                          void* level, void* n_cons, void* fused, void* stats, void* workspace, size_t ws_bytes, int N, int F,
                          int H, int W, void* stream);
 
+/* Polarimetric normals evaluation per pixel class (csrc/polar_normals_stats.hip): does a predicted surface agree with the
+ * polarisation that was measured?  K1 turns every pixel's DoLP / AoLP into three physical normal candidates (N_diff, N_spec1,
+ * N_spec2: manydepth/normals_vec.py:53-60); this call scores predicted normals against them, per class of the instance mask,
+ * in one evaluator launch.  It needs one frame, no ground truth and no pose, so it reports on glass and metal, where the depth
+ * sensors have holes; and a wrong polarizer layout, angle set or AoLP handedness turns its azimuth residual from a few
+ * degrees into tens.  The prediction in turn resolves the pi ambiguity and the diffuse / specular ambiguity of the
+ * polarisation normal: the chosen candidate per pixel is a disambiguated normal map.  tests/polar_normals_ref.py states the
+ * definition in NumPy.
+ * NOT BUILT: the residual uses the orthographic convention of calc_normals (the camera looks along -z at every pixel); there
+ * is no per-pixel viewing-ray frame.  There is no training loss on the residual.
+ *
+ * pred         fp32 device, pixel-major, pixel stride ld >= 3 floats, as for pd_normals_stats (ld = 3: a channels-last
+ *              [N,3,H,W] tensor read in place; ld = 4: what pd_gt_normals writes, read with 16-byte loads when aligned)
+ * pol_normals  fp32 planar [N,9,H,ldp], what pd_polar_fwd / pd_polar_general_fwd / pd_polar_normals_from_xolp write:
+ *              channels 0-2 N_diff, 3-5 N_spec1, 6-8 N_spec2
+ * xolp         fp32 [N,2,H,ldp]; only channel 0 (DoLP, rho) is read
+ * ldp          row pitch of both, ldp >= W; the padding columns are never read
+ * mask         int32 [N,H,W] or NULL; classes HOST int[K][2] exactly as in pd_normals_stats (lo > hi = every pixel; a ranged
+ *              class needs a mask; a pixel may be in several classes); 1 <= K <= PD_PNSTAT_MAX_CLASSES
+ * valid        uint8 [N,H,W] or NULL; a 0 takes the pixel out altogether: it is in no counter and its maps read "not counted"
+ * cos_edges    the same DEVICE double[719] table pd_normals_stats takes; the azimuth set uses its first 359 entries
+ * rho_min, rho_max   the DoLP range in which a pixel is scored; tilt2_min = sin^2 of the smallest tilt of the prediction at
+ *              which its azimuth is defined; aolp_sign = +1 or -1 multiplies the y component of every candidate
+ *
+ * Per pixel, every fp32 value converted to fp64 first (all products are then exact), no contraction, in this order.
+ * GATES, in this order; a pixel that fails one adds 1 to that counter in each of its classes, in BOTH record sets, and to
+ * nothing else:
+ *   1 dolp_out   rho is not finite, or rho < rho_min, or rho > rho_max
+ *   2 bad        a2 = (px px + py py) + pz pz is not finite or not > 0; or any of the nine candidate components is not finite;
+ *                or no candidate has b2 > 0 (b2 below)
+ * ORIENTATION: if pz < 0, p is negated (exact).  For every candidate cy' = aolp_sign * cy (exact).
+ * NORMAL SET (PD_PNSTAT_NORMAL_BINS = 720 bins of 0.25 degrees over [0, 180]).  Six candidates in the fixed order (diff,+),
+ * (diff,-), (spec1,+), (spec1,-), (spec2,+), (spec2,-); the "-" candidate is (-cx, -cy', cz), the pi flip of the azimuth.
+ * With m = (px cx) + (py cy'), q = pz cz, b2 = (cx cx + cy' cy') + cz cz:
+ *     c+ = (m + q) / (sqrt(a2) sqrt(b2)),   c- = (-m + q) / (sqrt(a2) sqrt(b2)).
+ * The first strict maximum in that order wins; candidates with b2 == 0 or a non-finite c are skipped (after the gates no c
+ * of fp32 inputs is non-finite; were all skipped, the pixel would count as `bad` in this set).  c is clamped to [-1, 1], its
+ * bin is #{ j in 1..719 : c <= cos_edges[j-1] }, deg = acos(c) * 57.29577951308232.  `spec`: the winner is a specular
+ * candidate; `flipped`: it is a "-" candidate.
+ * AZIMUTH SET (PD_PNSTAT_AZIMUTH_BINS = 360 bins of 0.25 degrees over [0, 90]).  t2 = px px + py py.  Branch d uses the xy of
+ * N_diff, branch s the xy of N_spec1 (N_spec2 shares its azimuth); u2 = cx cx + cy' cy'; a branch is usable when u2 > 0.  The
+ * pixel adds to `frontal`, and to nothing else of this set, when t2 <= tilt2_min * a2 or no branch is usable.  Otherwise
+ *     c_b = |(px cx) + (py cy')| / (sqrt(t2) sqrt(u2)) clamped to [0, 1]  (-1 for a branch that is not usable),
+ * c = max(c_d, c_s), `spec` when c_s > c_d strictly, bin = #{ j in 1..359 : c <= cos_edges[j-1] } (exactly 90 degrees lands
+ * in bin 359), deg = acos(c) * 57.29577951308232.
+ * No trigonometric function takes part in any decision: bins and choices are made on cosines in fp64.
+ * SUMS, in both sets, per class of a pixel that counts: deg, deg * deg, rho * deg, rho -- the last two give the
+ * DoLP-weighted mean.  They are bit-reproducible from run to run (the fixed lane, wave and workgroup order of
+ * csrc/class_records.hpp, partial sums through `workspace`); the integer fields are exact.
+ *
+ * Records, [N][K] each, written whole by every call; either pointer may be NULL, not both.  Byte offsets:
+ *   stats_normal                               stats_azimuth
+ *      0  int64   n  (the sum of the bins)        0  int64   n
+ *      8  int64   bad                             8  int64   bad
+ *     16  int64   dolp_out                       16  int64   dolp_out
+ *     24  int64   spec                           24  int64   frontal
+ *     32  int64   flipped                        32  int64   spec
+ *     40  double  sum deg                        40  double  sum deg
+ *     48  double  sum deg deg                    48  double  sum deg deg
+ *     56  double  sum rho deg                    56  double  sum rho deg
+ *     64  double  sum rho                        64  double  sum rho
+ *     72  8 bytes of zero                        72  8 bytes of zero
+ *     80  uint32  hist[720]                      80  uint32  hist[360]
+ * Per class: n + bad + dolp_out = the pixels of the class with valid != 0 (normal set), n + bad + dolp_out + frontal =
+ * the same (azimuth set).
+ * Per-pixel maps, each NULL or:
+ *   az_deg      fp32  [N,H,W]    the azimuth residual; NaN where the pixel does not count in the azimuth set, whatever its class
+ *   n_deg       fp32  [N,H,W]    the angle to the winner; NaN where the pixel does not count in the normal set
+ *   choice      uint8 [N,H,W]    0 = not counted in the normal set, else 1 + the winner's index in the order above
+ *   pol_normal  fp32  [N,H,W,4]  the winning candidate (+-cx, +-cy', cz, 0), negated when p was negated so that it lies on
+ *                                p's side; zeros where not counted
+ * One evaluator launch between the zero and finalize launches of csrc/class_records.hpp (one of each per record set) per 2^20
+ * images: blockIdx.y picks the record set a workgroup fills.  No allocation, copy or synchronisation: the call can be
+ * captured into a graph.  workspace: >= pd_polar_normals_stats_workspace(N, H, W, K) bytes (monotone in each argument,
+ * never 0, a multiple of 16).  N == 0 returns PD_OK after the checks.  Every refusal is PD_EINVAL with a message, decided
+ * before the device is touched: a null pred / pol_normals / xolp / classes / cos_edges / workspace, both record sets NULL,
+ * ws_bytes too small, K outside 1 .. 16, a ranged class with mask == NULL, ld < 3, ldp < W, aolp_sign not +-1, a non-finite
+ * or inverted rho_min / rho_max, tilt2_min outside [0, 1), pol_normals / records / pol_normal / workspace not 16-byte
+ * aligned, a frame beyond 2^30 pixels ("too large"), bad shape. */
+#define PD_PNSTAT_NORMAL_BINS          720      /* 0.25 degree bins over [0, 180] */
+#define PD_PNSTAT_AZIMUTH_BINS         360      /* 0.25 degree bins over [0, 90] */
+#define PD_PNSTAT_MAX_CLASSES          16
+#define PD_PNSTAT_COUNTERS             4        /* bad, dolp_out, then spec, flipped (normal) or frontal, spec (azimuth) */
+#define PD_PNSTAT_SUMS                 4
+#define PD_PNSTAT_NORMAL_RECORD_BYTES  2960     /* 80 + 4 * 720 */
+#define PD_PNSTAT_AZIMUTH_RECORD_BYTES 1520     /* 80 + 4 * 360 */
+size_t pd_polar_normals_stats_workspace(int N, int H, int W, int K);
+int pd_polar_normals_stats(const void* pred, long ld, const void* pol_normals, const void* xolp, long ldp, const void* mask,
+                           const int* classes, int K, const void* valid, const void* cos_edges, float rho_min, float rho_max,
+                           double tilt2_min, int aolp_sign, void* stats_normal, void* stats_azimuth, void* az_deg,
+                           void* n_deg, void* choice, void* pol_normal, void* workspace, size_t ws_bytes, int N, int H, int W,
+                           void* stream);
+
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward
  * dp[r][:] <- scale * p * (dp - sum(dp * p)).  The score GEMMs (Q K^T, P V and their gradients) are pd_conv2d /

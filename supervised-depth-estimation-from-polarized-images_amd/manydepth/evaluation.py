@@ -19,6 +19,7 @@ from polardepth import depth_eval
 from polardepth import pointcloud
 from polardepth import pose_eval
 from polardepth import consistency_eval
+from polardepth import polar_normals_eval
 from polardepth import matching as pdmatching
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -31,7 +32,7 @@ class Evaluation:
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
                  pol_calibration=None, normals_decoder=None, pose_network=None, multi_frame=False, matching_ids=(0, -1),
-                 multi_poses="files", num_depth_bins=96, depth_binning="linear"):
+                 multi_poses="files", num_depth_bins=96, depth_binning="linear", aolp_sign=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -63,7 +64,14 @@ class Evaluation:
         "files": the loader's ground-truth ``("poses", i)``; "network": the pose network's, composed link by link
         (``polardepth.matching.matching_poses``), which implies ``pose_network=True``.  A third loader
         (``multi_loader``) serves frame 0 and the lookup frames, with ``need_poses`` only for "files".  See
-        ``predict_multi``, ``test_depth(source="multi")``; ``test_pose_chain`` needs the pose network only."""
+        ``predict_multi``, ``test_depth(source="multi")``; ``test_pose_chain`` needs the pose network only.
+
+        ``aolp_sign``: +1 or -1, the handedness of the sensor's AoLP as ``test_polar_normals`` takes it (or
+        $PD_POL_AOLP_SIGN); None = +1.  Nothing else reads it."""
+        aolp_sign = aolp_sign if aolp_sign is not None else os.environ.get("PD_POL_AOLP_SIGN")
+        self.aolp_sign = 1 if aolp_sign is None else int(aolp_sign)
+        if self.aolp_sign not in (1, -1):
+            raise ValueError(f"aolp_sign must be +1 or -1, got {aolp_sign!r}")
         if multi_poses not in ("files", "network"):
             raise ValueError(f'multi_poses must be "files" or "network", got {multi_poses!r}')
         self.multi_frame, self.multi_poses = bool(multi_frame), multi_poses
@@ -309,6 +317,76 @@ class Evaluation:
             if pooled[k][6] > 0:
                 print(f"{name:>8} per-image " + ("&{: 9.4f} " * 7).format(*per_image[k].tolist()))
                 print(f"{name:>8} pooled    " + ("&{: 9.4f} " * 7).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
+        return results
+
+    @torch.no_grad()
+    def test_polar_normals(self, source="auto", rho_min=0.05, rho_max=1.0, tilt_min_deg=5.0):
+        """Does the surface agree with the polarisation that was measured (polardepth.polar_normals_eval)?  Per class -- the
+        whole frame, all objects, each material -- and per batch ONE pd_polar_normals_stats call scores normals against the
+        three physical candidates K1 derives from DoLP / AoLP, in two sets: "normal", the angle to the best of the six
+        candidates (each and its pi flip), and "azimuth", the azimuth residual modulo pi.  It needs no ground truth and no
+        pose.  ``source``: "depth" scores the normals of the predicted depth, "decoder" the NormalsDecoder's output, "auto" the
+        decoder where it exists, else depth; "gt" scores the normals of the GROUND-TRUTH depth, on the pixels whose 3x3
+        window is inside the depth range -- how well measurement and true geometry agree per material, the ceiling for any
+        prediction.  ``xolp`` and the nine-channel normals come from ``polar_inputs`` whatever ``augment_normals`` says; the
+        handedness is ``Evaluation(aolp_sign=)``.  ``rho_min`` and ``tilt_min_deg`` are conventions, not measurements
+        (``polar_normals_stats``).
+
+        Prints, and returns {class: {"normal": r, "azimuth": r}} with r = {"per_image": [8], "pooled": [8], and the set's
+        four counters by name (ints)}: mean, median, rmse (degrees), the shares within 11.25 / 22.5 / 30 degrees, the pixel
+        count and the DoLP-weighted mean; "per_image" and "pooled" as in ``test_normals``.  The records stay on the device
+        until the loop is over."""
+        if source not in ("auto", "depth", "decoder", "gt"):
+            raise ValueError(f'source must be "auto", "depth", "decoder" or "gt", got {source!r}')
+        if source == "auto":
+            source = "decoder" if "normals_decoder" in self.models else "depth"
+        if source == "decoder" and "normals_decoder" not in self.models:
+            raise ValueError('source="decoder" needs Evaluation(normals_decoder=True) (or PD_NORMALS_DECODER=1)')
+        sets = ("normal", "azimuth")
+        total, sums, counts = None, {}, {}
+        for inputs in self.test_loader:
+            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+            valid = None
+            if source == "gt":
+                pred = inputs["depth_gt"].float()
+                hole = ((pred < self.min_depth) | (pred > self.max_depth) | pred.isnan()).float()
+                valid = torch.nn.functional.max_pool2d(torch.nn.functional.pad(hole, (1, 1, 1, 1), mode="replicate"), 3, 1) == 0
+            else:
+                out = self._forward(inputs, source == "decoder")
+                pred = out["normals_pred" if source == "decoder" else "depth"]
+            pol = pdpolar.polar_inputs(inputs, (self.height, self.width), ("xolp", "normals"), self.pol_angles,
+                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+            st = polar_normals_eval.polar_normals_stats(pred, pol, inputs["xolp", 0, 0], K=inputs[("K", 0)],
+                                                        mask=inputs[("mask", 0, 0)], valid=valid, rho_min=rho_min,
+                                                        rho_max=rho_max, tilt_min_deg=tilt_min_deg, aolp_sign=self.aolp_sign)
+            for name in sets:
+                rs = getattr(st, name)
+                m = rs.metrics()
+                ok = rs.n > 0
+                s = torch.where(ok[..., None], m, torch.zeros_like(m)).sum(0)
+                sums[name] = s if total is None else sums[name] + s
+                counts[name] = ok.sum(0) if total is None else counts[name] + ok.sum(0)
+            if total is None:
+                total = st
+            else:
+                total += st
+        if total is None:
+            return {}
+        results = {name: {} for name in total.names}
+        nm = len(polar_normals_eval.METRIC_NAMES)
+        for sname in sets:
+            rs = getattr(total, sname)
+            per_image = (sums[sname] / counts[sname][:, None].double()).cpu().numpy()
+            pooled, counters = rs.pooled().cpu().numpy(), rs.pooled_counters().cpu().numpy()
+            print(f"polar {sname} ({source}) " + ("{:>9} " * nm).format(*polar_normals_eval.METRIC_NAMES))
+            for k, name in enumerate(total.names):
+                r = {"per_image": per_image[k], "pooled": pooled[k]}
+                r.update({c: int(counters[k][j]) for j, c in enumerate(rs.counter_names)})
+                results[name][sname] = r
+                if pooled[k][6] > 0:
+                    print(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
+                    print(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) +
+                          "".join(f" {c} {int(counters[k][j])}" for j, c in enumerate(rs.counter_names)))
         return results
 
     @torch.no_grad()

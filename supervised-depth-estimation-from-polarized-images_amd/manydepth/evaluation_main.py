@@ -2,7 +2,9 @@
 PD_EVAL_POINTCLOUD=1 the point-cloud report (Evaluation.test_pointcloud), PD_EVAL_DEPTH=1 the one-pass depth report
 (Evaluation.test_depth), median-scaled with PD_EVAL_MEDIAN_SCALING=numpy or torch, PD_EVAL_POSE=1 the pose report of the
 pose network (Evaluation.test_pose; needs PD_POSE_NETWORK=1, which makes Evaluation build and load the pose network),
-PD_EVAL_CONSISTENCY=1 the multi-view consistency report of the predicted depth (Evaluation.test_consistency)."""
+PD_EVAL_CONSISTENCY=1 the multi-view consistency report of the predicted depth (Evaluation.test_consistency),
+PD_EVAL_POLAR_NORMALS=1 the polarimetric normals report (Evaluation.test_polar_normals; PD_POL_AOLP_SIGN=-1 for a sensor of
+the other AoLP handedness)."""
 import os
 
 from manydepth.evaluation import Evaluation
@@ -22,6 +24,8 @@ def main():
         ev.test_pose()
     if os.environ.get("PD_EVAL_CONSISTENCY") == "1":
         ev.test_consistency()
+    if os.environ.get("PD_EVAL_POLAR_NORMALS") == "1":
+        ev.test_polar_normals()
 
 
 if __name__ == "__main__":

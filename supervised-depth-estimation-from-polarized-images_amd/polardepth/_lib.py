@@ -165,6 +165,9 @@ SIGNATURES = {
     "pd_depth_consistency_workspace": (_sz, [_i, _i, _i, _i]),
     "pd_depth_consistency": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _i, _f, _f, _dp, _dp, _i, _vp, _vp, _vp, _vp,
                                   _vp, _sz, _i, _i, _i, _i, _vp]),
+    "pd_polar_normals_stats_workspace": (_sz, [_i, _i, _i, _i]),
+    "pd_polar_normals_stats": (_i, [_vp, _l, _vp, _vp, _l, _vp, _ip, _i, _vp, _vp, _f, _f, _dbl, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 

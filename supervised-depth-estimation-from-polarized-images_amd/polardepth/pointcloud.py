@@ -239,10 +239,11 @@ def cloud_stats(pred_depth, gt_depth, K, mask=None, classes=DEFAULT_CLASSES, min
     return CloudStats(acc, comp, names, dist_acc, dist_comp)
 
 
-def write_ply(path, xyz, rgb=None, flip=True):
+def write_ply(path, xyz, rgb=None, flip=True, normals=None):
     """Host code: a binary little-endian PLY of the points ``xyz`` [n,3] or [n,4] (then only the rows with w == 1), with
     ``rgb`` [n,3] uint8 colours (rows as in xyz) if given.  ``flip`` negates y and z, as the reference's viewer transform
-    does (eval_pointcloud.py:288)."""
+    does (eval_pointcloud.py:288).  ``normals`` [n,3] (rows as in xyz), if given, become the properties nx ny nz behind
+    x y z, flipped with the points."""
     xyz = np.asarray(xyz.detach().cpu() if isinstance(xyz, torch.Tensor) else xyz, dtype=np.float32)
     if rgb is not None:
         rgb = np.asarray(rgb.detach().cpu() if isinstance(rgb, torch.Tensor) else rgb)
@@ -251,19 +252,30 @@ def write_ply(path, xyz, rgb=None, flip=True):
         rgb = rgb.astype(np.uint8)
     if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
         raise ValueError(f"xyz must be [n,3] or [n,4], got {xyz.shape}")
+    if normals is not None:
+        normals = np.asarray(normals.detach().cpu() if isinstance(normals, torch.Tensor) else normals, dtype=np.float32)
+        if normals.shape != (xyz.shape[0], 3):
+            raise ValueError(f"normals must be [{xyz.shape[0]},3], got {normals.shape}")
     if xyz.shape[1] == 4:
         keep = xyz[:, 3] == 1
         xyz, rgb = xyz[keep, :3], (rgb[keep] if rgb is not None else None)
+        normals = normals[keep] if normals is not None else None
     if flip:
         xyz = xyz * np.array([1, -1, -1], np.float32)
+        normals = normals * np.array([1, -1, -1], np.float32) if normals is not None else None
     n = xyz.shape[0]
-    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if rgb is not None else [])
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if normals is not None else [])
+    fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")] if rgb is not None else []
     rows = np.empty(n, dtype=fields)
     rows["x"], rows["y"], rows["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        rows["nx"], rows["ny"], rows["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     if rgb is not None:
         rows["red"], rows["green"], rows["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {n}"]
     header += [f"property float {c}" for c in "xyz"]
+    if normals is not None:
+        header += [f"property float {c}" for c in ("nx", "ny", "nz")]
     if rgb is not None:
         header += [f"property uchar {c}" for c in ("red", "green", "blue")]
     header.append("end_header")

@@ -1,0 +1,197 @@
+"""pd_polar_normals_stats (csrc/polar_normals_stats.hip) at the evaluation's sizes: B = 12 at 320x480 and B = 16 at 512x640,
+the twelve default classes, both record sets, no maps.
+
+ms per call with HIP events, warm: one event pair per call, median of ``--iters`` calls, every call on another of ``--sets``
+rotating input sets (sized past the 256 MB Infinity Cache; the records, the workspace and the cosine table are allocated
+once).  GB/s from the algorithm's own byte count -- 60 bytes per pixel: pred 16 (ld = 4), nine candidate planes 36, DoLP 4,
+mask 4; the second record set's workgroups re-read the same pixels and that is NOT counted -- next to the rate of a device
+copy that moves the SAME number of bytes (half read, half written; rotating buffers, the same timing) and the ratio of the
+two.  Then, in the same run and on the same inputs, the same figures (n, the counters, the four sums and the histogram of
+both sets, for the twelve classes) written with torch ops in fp64, and how far its pooled means are from the kernel's.  One
+JSON line per measurement, printed and written to ``--out`` (default: profiles/polar_normals.log)."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarized-images_amd"))
+
+SIZES = ((12, 320, 480), (16, 512, 640))
+BYTES_PER_PIXEL = 60
+TILT2 = math.sin(math.radians(5.0)) ** 2
+DEG = 57.29577951308232
+
+
+def _median_ms(call, iters):
+    import torch
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for i, (e0, e1) in enumerate(evs):
+        e0.record()
+        call(i)
+        e1.record()
+    torch.cuda.synchronize()
+    ts = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+    return ts[iters // 2], ts[0], ts[-1]
+
+
+def _copy_rate(moved, sets, iters):
+    """GB/s of a device copy that moves ``moved`` bytes, half read and half written, over rotating buffers"""
+    import torch
+    half = moved // 2
+    src = [torch.empty(half, dtype=torch.uint8, device="cuda").fill_(s + 1) for s in range(sets)]
+    dst = [torch.empty(half, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    copy = lambda i: dst[i % sets].copy_(src[i % sets])
+    for i in range(sets):
+        copy(i)
+    torch.cuda.synchronize()
+    ms, _, _ = _median_ms(copy, iters)
+    return ms, 2 * half / (ms * 1e-3) / 1e9
+
+
+def make_set(N, H, W, seed):
+    """One input set on the device: a smooth DoLP / AoLP field with a few unpolarised pixels, K1's own nine normals for it,
+    the instance mask in 32x32 blocks of the eleven grey values, and a pixel-major prediction (ld = 4) around the diffuse
+    candidate, a third of it pi-flipped."""
+    import torch
+    from polardepth import polar as pdpolar
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    rho = np.stack([0.3 + 0.25 * np.sin(xx / 37.0 + rng.uniform(0, 6)) * np.cos(yy / 29.0 + rng.uniform(0, 6))
+                    for _ in range(N)]).astype(np.float32)
+    rho[rng.random((N, H, W)) < 0.02] = 0.01
+    phi = np.stack([1.5 * np.sin(xx / 53.0 + rng.uniform(0, 6)) * np.sin(yy / 41.0 + rng.uniform(0, 6)) for _ in range(N)])
+    xolp = torch.from_numpy(np.stack([rho, phi.astype(np.float32)], 1)).cuda()
+    pol = pdpolar.normals_from_xolp(xolp)
+    blocks = rng.integers(0, 11, (N, -(-H // 32), -(-W // 32))) * 20
+    mask = torch.from_numpy(np.repeat(np.repeat(blocks, 32, axis=1), 32, axis=2)[:, :H, :W].astype(np.int32)).cuda()
+    pred = torch.zeros((N, H, W, 4), dtype=torch.float32, device="cuda")
+    pred[..., :3] = pol[:, :3].permute(0, 2, 3, 1) + 0.1 * torch.from_numpy(rng.normal(size=(N, H, W, 3)).astype(np.float32)).cuda()
+    flip = torch.from_numpy(rng.random((N, H, W)) < 0.33).cuda()
+    pred[..., :2] = torch.where(flip[..., None], -pred[..., :2], pred[..., :2])
+    return pred, pol, xolp, mask
+
+
+def torch_figures(pred, pol, xolp, mask, classes, edges, rho_min=0.05, rho_max=1.0, tilt2=TILT2):
+    """The records' figures with torch ops, fp64: per set (n [N,K], counters [N,K,4], sums [N,K,4], hist [N,K,bins])."""
+    import torch
+    N, H, W = mask.shape
+    rho = xolp[:, 0].double()
+    p = pred[..., :3].double()
+    px, py, pz = p[..., 0], p[..., 1], p[..., 2]
+    C = pol.double()
+    cx, cy, cz = C[:, 0::3], C[:, 1::3], C[:, 2::3]
+    dolp_out = ~torch.isfinite(rho) | (rho < rho_min) | (rho > rho_max)
+    a2 = (px * px + py * py) + pz * pz
+    b2 = (cx * cx + cy * cy) + cz * cz
+    good = torch.isfinite(a2) & (a2 > 0) & torch.isfinite(C).all(1) & (b2 > 0).any(1)
+    bad, ok = ~dolp_out & ~good, ~dolp_out & good
+    s = torch.where(pz < 0, -1.0, 1.0)
+    px, py, pz = px * s, py * s, pz * s
+    m = px[:, None] * cx + py[:, None] * cy
+    q = pz[:, None] * cz
+    den = a2.sqrt()[:, None] * b2.sqrt()
+    c6 = torch.stack([(m + q) / den, (-m + q) / den], 2).reshape(N, 6, H, W)
+    c6 = torch.where(torch.isfinite(c6) & (b2 > 0).repeat_interleave(2, 1), c6, torch.full_like(c6, -float("inf")))
+    best, win = c6.max(1)
+    cn = best.clamp(-1, 1)
+    t2 = px * px + py * py
+    u2 = cx[:, :2] * cx[:, :2] + cy[:, :2] * cy[:, :2]
+    frontal = ok & ((t2 <= tilt2 * a2) | ~(u2 > 0).any(1))
+    cb = ((px[:, None] * cx[:, :2] + py[:, None] * cy[:, :2]).abs() / (t2.sqrt()[:, None] * u2.sqrt())).clamp(max=1.0)
+    cb = torch.where(u2 > 0, cb, torch.full_like(cb, -1.0))
+    ca = cb.max(1).values
+    neg_edges = -edges
+    out = []
+    for c, counts, bins, flags in (
+            (cn, ok, 720, (bad, dolp_out, ok & (win >= 2), ok & (win % 2 == 1))),
+            (ca, ok & ~frontal, 360, (bad, dolp_out, frontal, ok & ~frontal & (cb[:, 1] > cb[:, 0])))):
+        c = torch.where(counts, c, torch.ones_like(c))
+        b = torch.bucketize(-c, neg_edges[:bins - 1], right=True)
+        deg = torch.acos(c) * DEG
+        terms = torch.stack([deg, deg * deg, rho * deg, rho], -1)
+        ns, cs, ss, hs = [], [], [], []
+        for lo, hi in classes:
+            sel = torch.ones_like(counts) if lo > hi else (mask >= lo) & (mask <= hi)
+            v = sel & counts
+            ns.append(v.sum((1, 2)))
+            cs.append(torch.stack([(sel & f).sum((1, 2)) for f in flags], -1))
+            ss.append((terms * v[..., None]).sum((1, 2)))
+            img = torch.arange(N, device=b.device)[:, None, None].expand_as(b)
+            hs.append(torch.bincount((img * bins + b)[v], minlength=N * bins).view(N, bins))
+        out.append((torch.stack(ns, 1), torch.stack(cs, 1), torch.stack(ss, 1), torch.stack(hs, 1)))
+    return out
+
+
+def time_stats(N, H, W, iters=24, sets=None, torch_iters=5):
+    import torch
+    from polardepth import normals_eval as ne
+    from polardepth import polar_normals_eval as pe
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    if not torch.cuda.is_available():
+        raise RuntimeError("bench_polar_normals needs the GPU; there is no CPU fallback")
+    moved = N * H * W * BYTES_PER_PIXEL
+    sets = sets if sets is not None else max(2, min(12, -(-int(2.5 * 256e6) // moved)))
+    data = [make_set(N, H, W, s) for s in range(sets)]
+    names, table = ne.class_table(ne.DEFAULT_CLASSES)
+    K = len(names)
+    edges = ne.cos_edges("cuda")
+    rec_n = torch.empty((N, K, pe.NORMAL_RECORD_BYTES), dtype=torch.uint8, device="cuda")
+    rec_a = torch.empty((N, K, pe.AZIMUTH_RECORD_BYTES), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(int(lib.pd_polar_normals_stats_workspace(N, H, W, K)), dtype=torch.uint8, device="cuda")
+
+    def call(i):
+        pred, pol, xolp, mask = data[i % sets]
+        check(lib.pd_polar_normals_stats(ptr(pred), 4, ptr(pol), ptr(xolp), W, ptr(mask), table, K, None, ptr(edges), 0.05, 1.0,
+                                         TILT2, 1, ptr(rec_n), ptr(rec_a), None, None, None, None, ptr(ws), ws.numel(), N, H, W,
+                                         stream_ptr()), "pd_polar_normals_stats")
+
+    for i in range(sets):
+        call(i)
+    torch.cuda.synchronize()
+    ms, ms_min, ms_max = _median_ms(call, iters)
+    call(0)
+    st_n, st_a = pe.RecordSet(rec_n, names, pe.NORMAL_COUNTERS, 720), pe.RecordSet(rec_a, names, pe.AZIMUTH_COUNTERS, 360)
+    pooled_n, pooled_a = st_n.pooled().cpu().numpy(), st_a.pooled().cpu().numpy()
+    copy_ms, copy_gbps = _copy_rate(moved, sets, iters)
+    gbps = moved / (ms * 1e-3) / 1e9
+    out = {"op": "polar_normals_stats", "N": N, "H": H, "W": W, "K": K, "sets": sets, "bytes": moved, "ms": round(ms, 4),
+           "ms_min": round(ms_min, 4), "ms_max": round(ms_max, 4), "GBps": round(gbps, 1), "copy_ms": round(copy_ms, 4),
+           "copy_GBps": round(copy_gbps, 1), "fraction_of_copy": round(gbps / copy_gbps, 3),
+           "time_over_copy": round(ms / copy_ms, 2),
+           "normal_mean_deg_all": round(float(pooled_n[0, 0]), 4), "azimuth_mean_deg_all": round(float(pooled_a[0, 0]), 4),
+           "normal_pixels_all": int(pooled_n[0, 6]), "azimuth_pixels_all": int(pooled_a[0, 6])}
+
+    lohi = [(1, 0) if r is None else r for _, r in ne.DEFAULT_CLASSES]
+    figures = lambda i: torch_figures(*data[i % sets], lohi, edges)
+    (tn, tcn, tsn, thn), (ta, tca, tsa, tha) = figures(0)
+    torch.cuda.synchronize()
+    t_ms, t_min, _ = _median_ms(figures, torch_iters)
+    same = bool(torch.equal(tn, st_n.n) and torch.equal(ta, st_a.n) and torch.equal(tcn, st_n.counters) and
+                torch.equal(tca, st_a.counters))
+    rel = max(float(((tsn - st_n.sums).abs() / st_n.sums.abs().clamp(min=1e-300)).max()),
+              float(((tsa - st_a.sums).abs() / st_a.sums.abs().clamp(min=1e-300)).max()))
+    out.update({"torch_ms": round(t_ms, 3), "torch_ms_min": round(t_min, 3), "torch_over_call": round(t_ms / ms, 1),
+                "torch_counts_equal": same, "torch_sums_max_rel_diff": rel,
+                "torch_hist_equal": bool(torch.equal(thn, st_n.hist.long()) and torch.equal(tha, st_a.hist.long()))})
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=24)
+    ap.add_argument("--sets", type=int, default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "polar_normals.log"), help="the log; '' = print only")
+    args = ap.parse_args()
+    log = open(args.out, "w") if args.out else None
+    for N, H, W in SIZES:
+        line = json.dumps(time_stats(N, H, W, args.iters, args.sets))
+        print(line, flush=True)
+        if log:
+            log.write(line + "\n")
+            log.flush()
+    if log:
+        log.close()

@@ -7,7 +7,11 @@ truth), binary little-endian PLY coloured by ("color", 0, 0), y and z negated as
 ``--data_path synthetic`` serves a seeded synthetic item; without ``--weights`` the networks keep their initialisation.
 ``--consistent M`` writes only the predicted points that at least M of the neighbouring frames -1 and 1 confirm (their
 predicted depth maps agree with this one at MVSNet's thresholds under the loader's poses: ``n_cons >= M`` of
-``polardepth.consistency_eval.consistency``), at the depth fused over the confirming views instead of the single prediction."""
+``polardepth.consistency_eval.consistency``), at the depth fused over the confirming views instead of the single prediction.
+``--normals depth`` adds the properties nx ny nz to ``pred.ply``: the normals of the depth map that is exported
+(pd_gt_normals).  ``--normals polar`` writes the polarisation normal instead wherever the measurement gives one: of the three
+physical candidates of K1 and their pi flips, the one closest to the depth normal (``pol_normal`` where ``choice != 0`` of
+``polardepth.polar_normals_eval.polar_normals_stats``), the depth normal elsewhere.  ``gt.ply`` is unchanged."""
 import argparse
 import os
 import sys
@@ -16,12 +20,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarized-images_amd"))
 
 
-def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None):
+def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None, normals=None, aolp_sign=None):
     import torch
     from torch.utils.data.dataloader import default_collate
     from manydepth.evaluation import Evaluation
     from polardepth import pointcloud as pc
-    ev = Evaluation(load_weights_folder=weights, data_path=data_path, height=height, width=width, batch_size=1)
+    if normals not in (None, "polar", "depth"):
+        raise ValueError(f'--normals takes "polar" or "depth", got {normals!r}')
+    ev = Evaluation(load_weights_folder=weights, data_path=data_path, height=height, width=width, batch_size=1,
+                    aolp_sign=aolp_sign)
     ev.load_mono_model()
     ds = ev.test_loader.dataset
     if not 0 <= index < len(ds):
@@ -43,8 +50,32 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True, con
         pix = torch.from_numpy(cloud.slot_pixels())
         cols = rgb[pix.clamp(min=0)]                                   # slots outside the image hold no point: any colour
         path = os.path.join(out, f"{name}.ply")
-        written[path] = pc.write_ply(path, cloud.points[0], cols, flip=flip)
+        nrm = pixel_normals(ev, inputs, depth, normals)[pix.clamp(min=0)] if normals is not None and name == "pred" else None
+        written[path] = pc.write_ply(path, cloud.points[0], cols, flip=flip, normals=nrm)
     return written
+
+
+def pixel_normals(ev, inputs, depth, kind):
+    """[H * W, 3] on the host: per pixel the normal of ``depth`` (pd_gt_normals without a range), or with kind "polar" the
+    disambiguated polarisation normal where the measurement gives one."""
+    import numpy as np
+    import torch
+    from polardepth import polar as pdpolar
+    from polardepth import polar_normals_eval as pe
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    N, _, H, W = depth.shape
+    big = float(np.finfo(np.float32).max)
+    depth, K = depth.float().contiguous(), inputs[("K", 0)].float().contiguous()
+    dn = torch.empty((N, H, W, 4), dtype=torch.float32, device=depth.device)
+    check(lib.pd_gt_normals(ptr(depth), ptr(K), ptr(dn), N, H, W, -big, big, stream_ptr()), "pd_gt_normals")
+    out = dn[0, ..., :3]
+    if kind == "polar":
+        pol = pdpolar.polar_inputs(inputs, (ev.height, ev.width), ("xolp", "normals"), ev.pol_angles, dofp=ev.pol_dofp,
+                                   cdofp=ev.pol_cdofp, calibration=ev.pol_calibration)
+        st = pe.polar_normals_stats(dn.permute(0, 3, 1, 2)[:, :3], pol, inputs["xolp", 0, 0], classes=(("all", None),),
+                                    aolp_sign=ev.aolp_sign, maps=True)
+        out = torch.where((st.choice[0] != 0)[..., None], st.pol_normal[0, ..., :3], out)
+    return out.reshape(H * W, 3).cpu()
 
 
 def consistent_depth(ev, index, depth, gt, M, ids=(-1, 1)):
@@ -79,7 +110,10 @@ if __name__ == "__main__":
     ap.add_argument("--no_flip", action="store_true", help="keep the camera frame (y down, z forward)")
     ap.add_argument("--consistent", type=int, default=None, metavar="M",
                     help="keep the predicted points that M neighbouring frames confirm, at the fused depth")
+    ap.add_argument("--normals", choices=("polar", "depth"), default=None,
+                    help="add nx ny nz to pred.ply: the depth map's normals, or the polarisation normal where there is one")
+    ap.add_argument("--aolp_sign", type=int, choices=(1, -1), default=None, help="the AoLP handedness for --normals polar")
     args = ap.parse_args()
     for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip,
-                          args.consistent).items():
+                          args.consistent, args.normals, args.aolp_sign).items():
         print(f"{path}: {n} points")

@@ -1206,7 +1206,7 @@ int pd_depth_consistency(const void* depth0, const void* depths, const void* T, 
  * polarisation normal: the chosen candidate per pixel is a disambiguated normal map.  tests/polar_normals_ref.py states the
  * definition in NumPy.
  * NOT BUILT: the residual uses the orthographic convention of calc_normals (the camera looks along -z at every pixel); there
- * is no per-pixel viewing-ray frame.  There is no training loss on the residual.
+ * is no per-pixel viewing-ray frame.  (The training loss on the same decisions is pd_polar_loss_fwd / _bwd, below.)
  *
  * pred         fp32 device, pixel-major, pixel stride ld >= 3 floats, as for pd_normals_stats (ld = 3: a channels-last
  *              [N,3,H,W] tensor read in place; ld = 4: what pd_gt_normals writes, read with 16-byte loads when aligned)
@@ -1289,6 +1289,81 @@ int pd_polar_normals_stats(const void* pred, long ld, const void* pol_normals, c
                            double tilt2_min, int aolp_sign, void* stats_normal, void* stats_azimuth, void* az_deg,
                            void* n_deg, void* choice, void* pol_normal, void* workspace, size_t ws_bytes, int N, int H, int W,
                            void* stream);
+
+/* The polarimetric normals loss (csrc/polar_loss.hip): the two figures of pd_polar_normals_stats as a training term on a depth
+ * map, so that Evaluation.test_polar_normals reports what training minimises.  It needs one frame, no ground truth and no
+ * pose.  Like the evaluator it keeps the orthographic convention of calc_normals (no per-pixel viewing-ray frame).
+ * tests/polar_loss_ref.py states the definition in NumPy.
+ *
+ * depth        fp32 [N,1,H,W]
+ * K            fp32 [N,4,4] intrinsics
+ * pol_normals, xolp, ldp, valid, rho_min, rho_max, tilt2_min, aolp_sign    exactly as in pd_polar_normals_stats: planar
+ *              [N,9,H,ldp] and [N,2,H,ldp] read in place, the padding columns never read
+ * dolp_weighted   1: the weight of a pixel is w = rho; 0: w = 1
+ *
+ * Per pixel p = the fp32 normal of the depth map, formed exactly as pd_gt_normals forms it without a depth range (min_depth =
+ * -FLT_MAX, max_depth = FLT_MAX): Sobel/8 of the unprojected points with replicate padding, cross product, v / max(|v|, 1e-12),
+ * fp32, no contraction -- bit for bit what the evaluator scores when it is handed the depth map.  From p on every fp32 value is
+ * converted to fp64 first and every decision is the evaluator's, in its operation order:
+ * GATES, in this order: valid == 0 (the pixel counts nowhere); dolp_out; bad.  ORIENTATION: p is negated when pz < 0;
+ * cy' = aolp_sign * cy.
+ * NORMAL TERM: the six cosines c+-, the first strict maximum c* wins, clamped to [-1, 1]:   l_n = 1 - c*   (1 - cos of n_deg).
+ * AZIMUTH TERM: `frontal` when t2 <= tilt2_min * a2 or no branch is usable; otherwise branch d or s, s only when c_s > c_d
+ * strictly (c_d, c_s as the evaluator forms them); with m = (px cx) + (py cy') and u2 of the chosen branch
+ *     l_a = 1 - (m m) / (t2 u2)   clamped to [0, 1]   (sin^2 of az_deg; no square root, smooth at m = 0).
+ * Only + - x / sqrt in fp64 take part.  VALUES: L_n = sum w l_n / sum w over the pixels with a winner, L_a = sum w l_a / sum w
+ * over the pixels counted in the azimuth set, each rounded once to fp32; a term whose sum w is 0 has value 0 and a zero
+ * gradient (an H = 1 or W = 1 frame: every normal is the zero vector, hence `bad`).  The sums are fp64 in the fixed lane /
+ * wave / workgroup / finalize order of csrc/frame_reduce.hpp, no atomics: bit-reproducible.
+ *
+ * Outputs of pd_polar_loss_fwd:
+ *   state   uint8 [N,H,W], the decisions of the pixel:
+ *             bits 0-2  (PD_PLOSS_STATE_WINNER)   0 = no winner, else 1 + the winner's index: the evaluator's `choice`
+ *             bit  3    (PD_PLOSS_STATE_NEGATED)  p was negated
+ *             bits 4-5  (PD_PLOSS_STATE_BRANCH)   the azimuth branch: 0 = none (a gate, or frontal), 1 = d, 2 = s
+ *             bits 6-7  (>> PD_PLOSS_STATE_GATE_SHIFT)  the gate that dropped the pixel: 0 = none, 1 = valid == 0,
+ *                       2 = dolp_out, 3 = bad
+ *   sums    PD_PLOSS_RECORD_BYTES = 96 bytes, 8-byte aligned:
+ *              0  double  sum w l_n          32  int64  pixels with a winner        64  int64  frontal
+ *              8  double  sum w  (normal)    40  int64  pixels in the azimuth set   72  int64  specular winners
+ *             16  double  sum w l_a          48  int64  dolp_out                    80  int64  flipped winners
+ *             24  double  sum w  (azimuth)   56  int64  bad                         88  8 bytes of zero
+ *   values  fp32 [2] = (L_n, L_a)
+ *   maps    NULL or fp32 [N,H,W,2] = (l_n, l_a) rounded to fp32, NaN where the pixel is not counted in that term
+ * workspace: >= pd_polar_loss_rows(N, H, W) * 11 * 8 bytes, 16-byte aligned; pd_polar_loss_rows is monotone and never 0.
+ *
+ * pd_polar_loss_bwd: gdepth [N,1,H,W] = d (g[0] L_n + g[1] L_a) / d depth, written for every pixel, zeros included.  It reads
+ * `state` instead of deciding again (the winner and the branch are data, as the minimum over frames in pd_reproj_combine),
+ * gvalues = the DEVICE fp32 [2] upstream gradient, and `sums` of the forward call.  dL/dp is formed in fp64,
+ *     normal term    -(g[0] w / sum w) (c^ - c* p^) / |p|          c^, p^ the unit candidate and the unit p
+ *     azimuth term   -(g[1] w / sum w) 2 m / (t2 u2) ((cx, cy') - (m / t2) (px, py)),   z component 0
+ * a clamped c* or l_a contributing nothing; the sign is restored for a negated p and the sum is rounded once to fp32.  From
+ * there the path is the fp32 one of pd_sup_loss_bwd: through v / max(|v|, 1e-12) (its |v| <= 1e-12 branch included), dA = B x
+ * wv, dB = wv x A, and the transposed replicate-padded Sobel gather.  One launch: per 8 x 64 tile the (dA, dB) of the 10 x 66
+ * halo go to LDS and the gather runs from there; PD_PLOSS_BWD_TILES_PER_TRIP tiles per grid-stride trip.
+ *
+ * Neither call allocates, copies or synchronises: both can be captured into a graph.  N == 0 returns PD_OK after the checks
+ * and touches nothing (the values of an empty batch are 0).  Every refusal is PD_EINVAL with a message, decided before the
+ * device is touched: bad shape, a null depth / K / pol_normals / xolp / state / sums / values / workspace (/ gvalues /
+ * gdepth), ldp < W, aolp_sign not +-1, dolp_weighted not 0 or 1, a non-finite or inverted rho_min / rho_max, tilt2_min outside
+ * [0, 1), pol_normals or workspace not 16-byte aligned, sums or maps not 8-byte aligned, ws_bytes too small, a frame beyond
+ * 2^30 pixels ("too large"). */
+#define PD_PLOSS_SUMS                4
+#define PD_PLOSS_COUNTERS            7        /* n_normal, n_azimuth, dolp_out, bad, frontal, spec, flipped */
+#define PD_PLOSS_RECORD_BYTES        96
+#define PD_PLOSS_STATE_WINNER        7
+#define PD_PLOSS_STATE_NEGATED       8
+#define PD_PLOSS_STATE_BRANCH        48
+#define PD_PLOSS_STATE_BRANCH_SHIFT  4
+#define PD_PLOSS_STATE_GATE_SHIFT    6
+#define PD_PLOSS_BWD_TILES_PER_TRIP  4096
+int pd_polar_loss_rows(int N, int H, int W);
+int pd_polar_loss_fwd(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp, const void* valid,
+                      float rho_min, float rho_max, double tilt2_min, int aolp_sign, int dolp_weighted, void* state, void* sums,
+                      void* values, void* maps, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+int pd_polar_loss_bwd(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp, const void* state,
+                      const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted, void* gdepth, int N, int H, int W,
+                      void* stream);
 
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward

@@ -12,6 +12,7 @@
 // All sums are reduced per wavefront (shuffles), then per workgroup, written as fp32 partials and
 // finished in fp64 by a one-block kernel -- no float atomics, run-to-run deterministic.
 #include "pd_common.h"
+#include "depth_normals.hpp"
 #include "wave_ops.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -20,6 +21,7 @@ namespace {
 
 using pd_wave::divmod;
 using pd_wave::wave_sum;
+using namespace pd_dn;   // the depth -> normal chain and its transpose, shared with polar_loss.hip
 constexpr int LT = 256;
 static_assert(LT == pd::GRID_THREADS, "pd::flat_grid sizes grids for 256 threads");
 
@@ -151,42 +153,6 @@ __global__ __launch_bounds__(LT) void up_gather_bwd_f_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------ supervised depth + normals terms
-struct Cam { float fx, fy, cx, cy; };
-__device__ __forceinline__ Cam load_cam(const float* K, long n) {
-    const float* k = K + n * 16;  // [4][4]
-    return Cam{k[0], k[5], k[2], k[6]};
-}
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-// Sobel/8 gradients of the unprojected points around (x,y) with replicate padding
-__device__ __forceinline__ void sobel_xyz(const float* __restrict__ D, int H, int W, int x, int y, Cam c, V3& A, V3& B) {
-    A = V3{0, 0, 0}; B = V3{0, 0, 0};
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy) {
-        const int yy = min(max(y + dy, 0), H - 1);
-        const float sy = dy == 0 ? 2.f : 1.f, ddy = (float)dy;
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int xx = min(max(x + dx, 0), W - 1);
-            const float sx = dx == 0 ? 2.f : 1.f, ddx = (float)dx;
-            const float d = D[(long)yy * W + xx];
-            const float X = (xx - c.cx) / c.fx * d, Y = (yy - c.cy) / c.fy * d;
-            const float kx = sy * ddx * 0.125f, ky = ddy * sx * 0.125f;
-            A.x += kx * X; A.y += kx * Y; A.z += kx * d;
-            B.x += ky * X; B.y += ky * Y; B.z += ky * d;
-        }
-    }
-}
-
-__device__ __forceinline__ V3 normalize12(V3 v, float& nv) {
-    nv = sqrtf(dot(v, v));
-    const float inv = 1.f / fmaxf(nv, 1e-12f);
-    return V3{v.x * inv, v.y * inv, v.z * inv};
-}
-
 // gtn[p] = normalised (A x B) of the ground-truth depth at every masked pixel (xyz, w unused): the same value for all
 // scales and for the forward and backward kernels of a step, which otherwise each rebuild it from nine depths
 __global__ __launch_bounds__(LT) void gt_normals_kernel(const float* __restrict__ gt, const float* __restrict__ K,
@@ -373,15 +339,7 @@ __device__ __forceinline__ void normals_grad_ab(const float* __restrict__ pred_n
         } else {
             wn = V3{-wln * gh.x * 1e8f, -wln * gh.y * 1e8f, -wln * gh.z * 1e8f};
         }
-        V3 wv;   // dL/d v, v -> nn = v / max(|v|, 1e-12)
-        if (nv > 1e-12f) {
-            const float inv = 1.f / nv, pr = dot(wn, nn);
-            wv = V3{(wn.x - pr * nn.x) * inv, (wn.y - pr * nn.y) * inv, (wn.z - pr * nn.z) * inv};
-        } else {
-            wv = V3{wn.x * 1e12f, wn.y * 1e12f, wn.z * 1e12f};
-        }
-        dA = cross(B, wv);   // d(A x B).w / dA = B x w
-        dB = cross(wv, A);   // d(A x B).w / dB = w x A
+        normal_grad_to_ab(wn, nn, nv, A, B, dA, dB);
     }
 }
 
@@ -403,16 +361,6 @@ __global__ __launch_bounds__(LT) void sup_bwd_a_kernel(const float* __restrict__
         normals_grad_ab(pred + n * H * W, gt + n * H * W, gtn, i, g, load_cam(K, n), H, W, x, y, wln, min_d, max_d, dA, dB);
         float* o = ab + i * 6;
         o[0] = dA.x; o[1] = dA.y; o[2] = dA.z; o[3] = dB.x; o[4] = dB.y; o[5] = dB.z;
-    }
-}
-
-// separable replicate-padding weights: sum of taps delta in {-1,0,1} of p that land on q
-__device__ __forceinline__ void tap_weights(int q, int p, int n, float& wd, float& ws) {
-    wd = 0.f; ws = 0.f;
-#pragma unroll
-    for (int d = -1; d <= 1; ++d) {
-        const int t = min(max(p + d, 0), n - 1);
-        if (t == q) { wd += (float)d; ws += d == 0 ? 2.f : 1.f; }
     }
 }
 
@@ -455,7 +403,6 @@ __global__ __launch_bounds__(LT) void sup_bwd_b_kernel(const float* __restrict__
 // Passes A and B in one kernel: a workgroup evaluates (dA, dB) for the 10 x 66 halo of an 8 x 64 pixel tile into LDS
 // (1.29x the evaluations) and gathers from there -- the [N,H,W,6] intermediate (126 MB written and re-read per scale)
 // never reaches memory.  Same per-pixel arithmetic and summation order as the two-pass form.
-constexpr int SB_TR = 8, SB_TW = 64, SB_HR = SB_TR + 2, SB_HC = SB_TW + 2, SB_HP = SB_HR * SB_HC;
 __device__ __forceinline__ void sup_bwd_fused_body(float (&abl)[6][SB_HP], const float* __restrict__ pred,
                                                    const float* __restrict__ gt,
                                                    const float* __restrict__ K, const float4* __restrict__ gtn,
@@ -492,19 +439,7 @@ __device__ __forceinline__ void sup_bwd_fused_body(float (&abl)[6][SB_HP], const
             const float g = gt[i], d = pred[i];
             float gd = 0.f;
             if (g >= min_d && g <= max_d) gd = wl1 * (d > g ? 1.f : (d < g ? -1.f : 0.f));
-            V3 s{0, 0, 0};
-            for (int py = max(y - 1, 0); py <= min(y + 1, H - 1); ++py) {
-                float dyw, syw;
-                tap_weights(y, py, H, dyw, syw);
-                for (int px = max(x - 1, 0); px <= min(x + 1, W - 1); ++px) {
-                    float dxw, sxw;
-                    tap_weights(x, px, W, dxw, sxw);
-                    const float ka = syw * dxw * 0.125f, kb = dyw * sxw * 0.125f;
-                    const int q = (py - h0 + 1) * SB_HC + (px - w0 + 1);
-                    s.x += ka * abl[0][q] + kb * abl[3][q]; s.y += ka * abl[1][q] + kb * abl[4][q];
-                    s.z += ka * abl[2][q] + kb * abl[5][q];
-                }
-            }
+            const V3 s = gather_ab(abl, x, y, h0, w0, H, W);
             gd += (x - c.cx) / c.fx * s.x + (y - c.cy) / c.fy * s.y + s.z;
             gout[i] = to_disp ? gd * (-disp_range * d * d) : gd;
         }

@@ -55,6 +55,16 @@ def options_from_environment(opts, env=os.environ):
     # lookup frames of --num_matching_frames / --use_future_frame into inputs[("relative_pose", fi)] (opt.matching_poses)
     if env.get("PD_MATCHING_POSES") == "1":
         opts.matching_poses = True
+    # PD_POLAR_LOSS="w_n,w_a": the polarimetric normals loss with these weights on its normal and azimuth terms
+    # (opt.polar_loss; works in every training mode of this build, PD_STEP_GRAPH=1 is refused with it).
+    # PD_POLAR_LOSS_WHERE=all|holes: every pixel, or only those without ground-truth depth (opt.polar_loss_where; default all).
+    # PD_POL_AOLP_SIGN=-1: a sensor of the other AoLP handedness, as for the evaluation's report (opt.pol_aolp_sign)
+    if env.get("PD_POLAR_LOSS"):
+        opts.polar_loss = [float(x) for x in env["PD_POLAR_LOSS"].split(",")]
+    if env.get("PD_POLAR_LOSS_WHERE"):
+        opts.polar_loss_where = env["PD_POLAR_LOSS_WHERE"]
+    if env.get("PD_POL_AOLP_SIGN"):
+        opts.pol_aolp_sign = int(env["PD_POL_AOLP_SIGN"])
     return opts
 
 

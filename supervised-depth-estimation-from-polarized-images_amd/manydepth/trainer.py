@@ -37,7 +37,10 @@ division by the number of scales) weights frame f of F with F - f, because the r
 over the frames -- with ``frame_ids 0 -1 1`` the first neighbour counts twice, the second once.  The loaders are then built
 with ``need_poses=True``, and -- a deliberate difference from the reference, which has no mask here and supervises a missing
 neighbour towards whatever its loader substituted -- items whose ``frame_valid`` is 0 are left out, the mean being taken over
-the present ones, as in the photometric term.  The cost-volume student's building
+the present ones, as in the photometric term.  ``opt.polar_loss = (w_n, w_a)`` (``PD_POLAR_LOSS``; any of the modes above)
+adds the polarimetric normals loss: per scale the normals of the predicted depth map against the candidates K1 derives from
+DoLP / AoLP, on the decisions of ``Evaluation.test_polar_normals`` (``polar_normal_loss/{s}``, ``polar_azimuth_loss/{s}``;
+``_polar_loss_option``); without it nothing changes in a bit, and ``PD_STEP_GRAPH=1`` is refused with it.  The cost-volume student's building
 blocks exist -- the plane sweep (``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training
 branch (``--train_student``: matching augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it,
 ``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
@@ -113,6 +116,36 @@ def _bf16_variant(opt):
     return bool(getattr(opt, "bf16", False))
 
 
+def _polar_loss_option(opt):
+    """The polarimetric normals loss (polardepth.ops.polar_loss): ``opt.polar_loss = (w_n, w_a)``, the weights of its normal and
+    azimuth terms, or "w_n,w_a"; None / absent = the term is off and nothing changes in a bit.  ``opt.polar_loss_where`` =
+    "all" (default) or "holes": only the pixels whose ground-truth depth is outside [min_depth, max_depth], where the
+    supervised terms see nothing.  ``opt.pol_aolp_sign`` = +1 (default) or -1, the handedness of the sensor's AoLP, as
+    ``Evaluation(aolp_sign=)``.  Not reference CLI flags: manydepth/train.py maps PD_POLAR_LOSS / PD_POLAR_LOSS_WHERE /
+    PD_POL_AOLP_SIGN onto them.  Returns (weights or None, where, sign); the weights are written back as a list of two floats,
+    so that they travel in opt.json."""
+    w = getattr(opt, "polar_loss", None)
+    if w is None:
+        return None, "all", 1
+    if isinstance(w, str):
+        w = w.split(",")
+    try:
+        w = [float(x) for x in w]
+    except (TypeError, ValueError):
+        raise ValueError(f"opt.polar_loss must be (w_n, w_a), got {getattr(opt, 'polar_loss')!r}")
+    if len(w) != 2 or not all(np.isfinite(x) and x >= 0.0 for x in w):
+        raise ValueError(f"opt.polar_loss must be two finite weights >= 0 (w_n, w_a), got {getattr(opt, 'polar_loss')!r}")
+    where = getattr(opt, "polar_loss_where", None) or "all"
+    if where not in ("all", "holes"):
+        raise ValueError(f'opt.polar_loss_where must be "all" or "holes", got {where!r}')
+    sign = getattr(opt, "pol_aolp_sign", None)
+    sign = 1 if sign is None else int(sign)
+    if sign not in (1, -1):
+        raise ValueError(f"opt.pol_aolp_sign must be +1 or -1, got {getattr(opt, 'pol_aolp_sign')!r}")
+    opt.polar_loss = w
+    return w, where, sign
+
+
 class _Bf16Step:
     """The flag words of this Trainer's training forward passes in bf16 mode, restored on exit: the precision is recorded by
     every autograd node when its forward runs, so the backward (and a captured replay) follows it without a global switch."""
@@ -178,6 +211,13 @@ class Trainer:
         if self.photometric and (os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False))):
             raise NotImplementedError("PD_STEP_GRAPH=1 with --pose_input: the photometric term is not captured yet; "
                                       "run this mode without the step graph")
+        # the polarimetric normals loss: the depth map's normals against the candidates K1 derives from DoLP / AoLP, on the
+        # decisions of Evaluation.test_polar_normals (polardepth.functional.polarimetric_loss, csrc/polar_loss.hip).  It needs
+        # no ground truth and no pose, so it works in the supervised-only mode and in both photometric modes
+        self.polar_loss, self.polar_loss_where, self.pol_aolp_sign = _polar_loss_option(self.opt)
+        if self.polar_loss is not None and (os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False))):
+            raise NotImplementedError("PD_STEP_GRAPH=1 with opt.polar_loss: the polarimetric term is not captured yet; "
+                                      "run it without the step graph")
         self.frame_ids = [int(i) for i in self.opt.frame_ids] if self.photometric else [0]
         if self.photometric and (self.frame_ids[0] != 0 or len(self.frame_ids) < 2 or 0 in self.frame_ids[1:]
                                  or len(self.frame_ids) - 1 > ops.REPROJ_MAX_FRAMES):
@@ -432,9 +472,19 @@ class Trainer:
         want = []
         if self.opt.augment_xolp or self.opt.augment_normals:
             want = ["xolp"] + (["normals"] if self.opt.augment_normals else [])
+        if self.polar_loss is not None:           # the polarimetric term scores against the candidates, whatever the encoders take
+            want = ["xolp", "normals"]
         # raw frames from the loader (HAMMER_Dataset(raw_pol=True), uint8 / uint16 / float32) are resized on the device first
-        return pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles,
-                                    dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        normals = pdpolar.polar_inputs(inputs, (self.opt.height, self.opt.width), tuple(want), self.pol_angles,
+                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        if self.polar_loss is not None:
+            if normals is None:                   # a loader that hands over XOLP itself, no planes
+                if ("xolp", 0, 0) not in inputs:
+                    raise ValueError('opt.polar_loss needs the polarisation: a batch with ("pol", 0, 0) planes, a sensor frame '
+                                     'or ("xolp", 0, 0)')
+                normals = pdpolar.normals_from_xolp(inputs[("xolp", 0, 0)].float().contiguous())
+            inputs[("pol_normals", 0, 0)] = normals
+        return normals
 
     def _forward_models(self, inputs):
         normals = self._polar_inputs(inputs)
@@ -570,6 +620,21 @@ class Trainer:
                 losses[f"reproj_loss/{s}"] = reproj[i]
                 losses[f"loss/{s}"] = losses[f"loss/{s}"] + reproj[i]
             losses["loss"] = losses["loss"] + sum(reproj[1:], reproj[0]) / len(reproj)
+        if self.polar_loss is not None:
+            # per scale, the depth map's normals against the polarisation normals of K1 (functional.polarimetric_loss): the
+            # weighted sum of the two terms joins loss/{s}, its mean over the scales joins loss, as the reprojection term does
+            valid = None
+            if self.polar_loss_where == "holes":
+                valid = ~((inputs["depth"] >= self.opt.min_depth) & (inputs["depth"] <= self.opt.max_depth))
+            terms = PF.polarimetric_loss(self.loss_cfg, disps, depths, inputs[("K", 0)], inputs[("pol_normals", 0, 0)],
+                                         inputs[("xolp", 0, 0)], valid, aolp_sign=self.pol_aolp_sign)
+            w_n, w_a = self.polar_loss
+            polar = []
+            for i, s in enumerate(scales):
+                losses[f"polar_normal_loss/{s}"], losses[f"polar_azimuth_loss/{s}"] = terms[i]
+                polar.append(w_n * terms[i][0] + w_a * terms[i][1])
+                losses[f"loss/{s}"] = losses[f"loss/{s}"] + polar[i]
+            losses["loss"] = losses["loss"] + sum(polar[1:], polar[0]) / len(polar)
         if ("normals_pred", 0) in outputs:
             # `arch1++_separate_normals_dec`: the predicted normals against the normals of the ground truth, weighted like
             # the normals term of the depth loss (README.md:54,67: normals_loss_weight)

@@ -888,6 +888,110 @@ def student_combine(reproj, rmask, multi_depth, mono_depth, valid=None, avg=Fals
     return (loss[0], loss[1], sel, sums) if details else (loss[0], loss[1])
 
 
+# ------------------------------------------------------------------ polarimetric normals loss (csrc/polar_loss.hip)
+POLAR_LOSS_COUNTERS = ("n_normal", "n_azimuth", "dolp_out", "bad", "frontal", "spec", "flipped")   # PD_PLOSS_COUNTERS, in order
+POLAR_LOSS_RECORD_BYTES = 96            # PD_PLOSS_RECORD_BYTES: 4 doubles, 7 int64, 8 bytes of zero
+POLAR_STATE_WINNER, POLAR_STATE_NEGATED, POLAR_STATE_BRANCH_SHIFT, POLAR_STATE_GATE_SHIFT = 7, 8, 4, 6
+
+
+class PolarLossDetails:
+    """What ``polar_loss(..., details=True)`` adds: ``state`` uint8 [N,H,W] (the decisions per pixel; bit layout in
+    include/polardepth.h), ``sums`` float64 [4] (sum w l_n, sum w, sum w l_a, sum w), ``counters`` int64 [7]
+    (POLAR_LOSS_COUNTERS) and ``maps`` fp32 [N,H,W,2] = (l_n, l_a), NaN where a pixel is not counted.  All on the device."""
+
+    def __init__(self, state, record, maps):
+        self.state, self.record, self.maps = state, record, maps
+
+    @property
+    def sums(self):
+        return self.record.view(torch.float64)[:4]
+
+    @property
+    def counters(self):
+        return self.record.view(torch.int64)[4:11]
+
+
+class _PolarLossFn(torch.autograd.Function):
+    """pd_polar_loss_fwd / _bwd: returns (values [2], state, record, maps); differentiable in the depth map."""
+
+    @staticmethod
+    def forward(ctx, depth, K, pol, xolp, ldp, valid, opts, want_maps):
+        N, _, H, W = depth.shape
+        dev = depth.device
+        rho_min, rho_max, tilt2, sign, weighted = opts
+        state = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+        record = torch.zeros(POLAR_LOSS_RECORD_BYTES, dtype=torch.uint8, device=dev)
+        values = torch.zeros(2, dtype=torch.float32, device=dev)
+        maps = torch.empty((N, H, W, 2), dtype=torch.float32, device=dev) if want_maps else None
+        ws = torch.empty((lib.pd_polar_loss_rows(N, H, W), 11), dtype=torch.float64, device=dev)
+        check(lib.pd_polar_loss_fwd(ptr(depth), ptr(K), ptr(pol), ptr(xolp), ldp, ptr(valid), rho_min, rho_max, tilt2, sign,
+                                    weighted, ptr(state), ptr(record), ptr(values), ptr(maps), ptr(ws), ws.numel() * 8, N, H, W,
+                                    stream_ptr()), "pd_polar_loss_fwd")
+        ctx.geom = (N, H, W, ldp, sign, weighted)
+        ctx.save_for_backward(depth, K, pol, xolp, state, record)
+        if maps is None:
+            maps = torch.empty(0, dtype=torch.float32, device=dev)
+        ctx.mark_non_differentiable(state, record, maps)
+        return values, state, record, maps
+
+    @staticmethod
+    def backward(ctx, gvalues, _gstate, _grecord, _gmaps):
+        depth, K, pol, xolp, state, record = ctx.saved_tensors
+        N, H, W, ldp, sign, weighted = ctx.geom
+        gdepth = torch.empty_like(depth)
+        check(lib.pd_polar_loss_bwd(ptr(depth), ptr(K), ptr(pol), ptr(xolp), ldp, ptr(state),
+                                    ptr(gvalues.float().reshape(2).contiguous()), ptr(record), sign, weighted, ptr(gdepth), N, H, W,
+                                    stream_ptr()), "pd_polar_loss_bwd")
+        return gdepth, None, None, None, None, None, None, None
+
+
+def polar_loss(depth, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.0, tilt_min_deg=5.0, aolp_sign=1,
+               dolp_weighted=True, details=False):
+    """The polarimetric normals loss of a depth map -> (L_n, L_a): what ``polar_normals_eval.polar_normals_stats`` measures as
+    the angle to the best candidate and the azimuth residual, as two smooth terms on the same per-pixel decisions,
+    L_n = sum w (1 - cos n_deg) / sum w and L_a = sum w sin^2(az_deg) / sum w with w = DoLP (``dolp_weighted``) or 1.  It needs
+    no ground truth and no pose.  Differentiable in ``depth`` only; the winner and the branch of a pixel are data.
+
+    depth        [N,1,H,W] fp32;  K [N,4,4] intrinsics
+    pol_normals  [N,9,H,W], xolp [N,2,H,W] as ``polar_normals_stats`` takes them (padded rows are read in place)
+    valid        [N,1,H,W] or [N,H,W] bool / uint8 or None: a 0 takes the pixel out altogether
+    rho_min, rho_max, tilt_min_deg, aolp_sign     the evaluator's options, with the evaluator's conventions
+    details      also return a ``PolarLossDetails``"""
+    import math
+    from ._records import frames
+    from .polar_normals_eval import _planar
+    _require_cuda(depth, K, pol_normals, xolp, valid)
+    if depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError(f"polar_loss: depth must be [N,1,H,W], got {tuple(depth.shape)}")
+    N, _, H, W = depth.shape
+    if tuple(K.shape) != (N, 4, 4):
+        raise ValueError(f"polar_loss: K must be [{N},4,4], got {tuple(K.shape)}")
+    if tuple(pol_normals.shape) != (N, 9, H, W) or tuple(xolp.shape) != (N, 2, H, W):
+        raise ValueError(f"polar_loss: pol_normals must be {(N, 9, H, W)} and xolp {(N, 2, H, W)}, got "
+                         f"{tuple(pol_normals.shape)} and {tuple(xolp.shape)}")
+    if aolp_sign not in (1, -1):
+        raise ValueError(f"polar_loss: aolp_sign must be +1 or -1, got {aolp_sign!r}")
+    if not 0.0 <= float(tilt_min_deg) < 90.0:
+        raise ValueError(f"polar_loss: tilt_min_deg must be in [0, 90), got {tilt_min_deg!r}")
+    if valid is not None:
+        valid = frames(valid, "valid", N, H, W).ne(0).to(torch.uint8).contiguous()
+    opts = (float(rho_min), float(rho_max), math.sin(math.radians(float(tilt_min_deg))) ** 2, int(aolp_sign), int(bool(dolp_weighted)))
+    if N == 0:                           # nothing to launch: both values are 0, and so is the gradient
+        dev = depth.device
+        values = depth.float().sum() * torch.zeros(2, dtype=torch.float32, device=dev)
+        out = PolarLossDetails(torch.empty((0, H, W), dtype=torch.uint8, device=dev),
+                               torch.zeros(POLAR_LOSS_RECORD_BYTES, dtype=torch.uint8, device=dev),
+                               torch.empty((0, H, W, 2), dtype=torch.float32, device=dev))
+        return (values[0], values[1], out) if details else (values[0], values[1])
+    pol, xl, ldp = _planar(pol_normals.detach(), xolp.detach(), H, W)
+    with torch.cuda.device(depth.device):
+        values, state, record, maps = _PolarLossFn.apply(depth.float().contiguous(), K.detach().float().contiguous(), pol, xl, ldp,
+                                                         valid, opts, bool(details))
+    if details:
+        return values[0], values[1], PolarLossDetails(state, record, maps)
+    return values[0], values[1]
+
+
 def depth_metrics(gt, pred, min_depth, max_depth, mask=None, mask_value=0):
     """Per-image depth metrics on the device: [N,8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count."""
     _require_cuda(gt, pred, mask)

@@ -8,8 +8,8 @@ azimuth residual modulo pi against the diffuse and the specular branch (``.azimu
 and no pose.  The by-product is the classical use of a coarse depth prior: the prediction resolves the pi ambiguity and the
 diffuse / specular ambiguity, and the winning candidate per pixel is a disambiguated normal map (``maps=True``).
 
-Not built: the residual uses the orthographic convention of calc_normals (no per-pixel viewing-ray frame), and there is no
-training loss on it.
+Not built: the residual uses the orthographic convention of calc_normals (no per-pixel viewing-ray frame).  The training loss on
+the same decisions is ``ops.polar_loss``.
 
 The per-image, per-class records stay on the device; ``Pool.metrics`` / ``pooled`` turn them into the report with torch ops.
 The definition is the header's; tests/polar_normals_ref.py states it in NumPy."""

@@ -1205,8 +1205,9 @@ int pd_depth_consistency(const void* depth0, const void* depths, const void* T, 
  * degrees into tens.  The prediction in turn resolves the pi ambiguity and the diffuse / specular ambiguity of the
  * polarisation normal: the chosen candidate per pixel is a disambiguated normal map.  tests/polar_normals_ref.py states the
  * definition in NumPy.
- * NOT BUILT: the residual uses the orthographic convention of calc_normals (the camera looks along -z at every pixel); there
- * is no per-pixel viewing-ray frame.  (The training loss on the same decisions is pd_polar_loss_fwd / _bwd, below.)
+ * By default the residual uses the orthographic convention of calc_normals (the camera looks along -z at every pixel), whose
+ * error grows towards the frame's edge; pd_polar_normals_stats_ray with ray_frame = 1 scores in the frame of each pixel's
+ * viewing ray instead (THE RAY FRAME, below).  (The training loss on the same decisions is pd_polar_loss_fwd / _bwd, below.)
  *
  * pred         fp32 device, pixel-major, pixel stride ld >= 3 floats, as for pd_normals_stats (ld = 3: a channels-last
  *              [N,3,H,W] tensor read in place; ld = 4: what pd_gt_normals writes, read with 16-byte loads when aligned)
@@ -1275,7 +1276,42 @@ int pd_depth_consistency(const void* depth0, const void* depths, const void* T, 
  * before the device is touched: a null pred / pol_normals / xolp / classes / cos_edges / workspace, both record sets NULL,
  * ws_bytes too small, K outside 1 .. 16, a ranged class with mask == NULL, ld < 3, ldp < W, aolp_sign not +-1, a non-finite
  * or inverted rho_min / rho_max, tilt2_min outside [0, 1), pol_normals / records / pol_normal / workspace not 16-byte
- * aligned, a frame beyond 2^30 pixels ("too large"), bad shape. */
+ * aligned, a frame beyond 2^30 pixels ("too large"), bad shape.
+ *
+ * THE RAY FRAME (pd_polar_normals_stats_ray, pd_polar_loss_fwd_ray / _bwd_ray with ray_frame = 1; csrc/ray_frame.hpp;
+ * tests/polar_ray_ref.py states it in NumPy).  K1's candidates are physical quantities about the viewing ray of their pixel:
+ * the zenith from DoLP is the angle between the normal and that ray, the azimuth from AoLP is measured around it.  The
+ * prediction is formed in camera coordinates; the two agree only at the principal point, and at fx = 0.58 W the ray at the
+ * frame's edge is tilted by about 40 degrees.  One rotation per pixel takes the prediction into the frame of its ray; every
+ * rule after that is the one above applied to the rotated vector.  R(x, y) is the MINIMAL rotation that takes the unit ray
+ * u = r / |r|, r = ((x - cx) / fx, (y - cy) / fy, 1), onto (0, 0, 1); (x, y) is the integer pixel position, as in the Sobel
+ * chain of pd_gt_normals.  It is evaluated in fp64 from the fp32 p and the fp32 intrinsics K [N,4,4] of the pixel's batch item
+ * (fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]), in exactly this order, without contraction, + - x / sqrt only:
+ *     xt = (double(x) - cx) / fx          yt = (double(y) - cy) / fy
+ *     L  = sqrt((xt*xt + yt*yt) + 1.0)    ux = xt / L    uy = yt / L    uz = 1.0 / L
+ *     d  = (px*ux + py*uy) + pz*uz        s  = (d + pz) / (1.0 + uz)
+ *     p' = (px - s*ux,  py - s*uy,  d)
+ * and its transpose, used for the pol_normal map and for the loss gradient:
+ *     d = (gx*ux + gy*uy) + gz*uz     s = (d + gz) / (1.0 + uz)     t = 2.0*gz
+ *     R^T g = ((gx - s*ux) + t*ux,  (gy - s*uy) + t*uy,  (gz - s*(uz + 1.0)) + t*uz)
+ * On the axis (xt = yt = 0) R is the identity bit for bit (s = (pz + pz) / 2 = pz); 1 + uz > 1, so no denominator is at risk;
+ * a zero or NaN fx / fy makes p' non-finite and the pixel `bad`, and no address depends on it.  p' replaces the fp64 p
+ * everywhere from the `bad` gate on: a2, t2, m, q are formed from p'.  The orientation p'z >= 0 becomes the physical
+ * visibility condition p.u >= 0, `frontal` becomes "too frontal to the ray".  choice, n_deg and az_deg are those of the ray
+ * frame; pol_normal is R^T of the winning candidate on the prediction's side, formed in fp64 and rounded once: a camera-frame
+ * normal map.
+ * Why the minimal rotation: it gives the exact zenith (p'z = p.u) and keeps every angle between the prediction and the
+ * candidates.  For the azimuth it is the middle of three models, with alpha the ray's tilt: an orthogonal projection of the
+ * field onto the sensor plane shortens the component in the meridional plane by cos alpha; the published perspective
+ * phase-angle model (the plane of incidence cut with the image plane) shortens the component across it by cos alpha; the minimal
+ * rotation shortens neither, which is also how a rotationally symmetric lens carries the s and p components (s is kept, p
+ * turns with the ray).  It differs from the phase-angle model by a mean of about 2.5 degrees and up to 8-10 degrees in the
+ * extreme corner, against an orthographic error of up to 47 degrees.  THE REMAINING LIMIT: this is a convention, not a
+ * measurement; a second azimuth model is not built.
+ * pd_polar_normals_stats_ray takes K (fp32 [N,4,4], device) and ray_frame (0 or 1) after ld and is otherwise
+ * pd_polar_normals_stats: same records, maps, workspace and launches, still capturable.  With ray_frame = 0 it writes the
+ * bytes of pd_polar_normals_stats and ignores K, which may be NULL.  Two more refusals (PD_EINVAL, before the device is
+ * touched): ray_frame not 0 or 1; ray_frame = 1 with K == NULL. */
 #define PD_PNSTAT_NORMAL_BINS          720      /* 0.25 degree bins over [0, 180] */
 #define PD_PNSTAT_AZIMUTH_BINS         360      /* 0.25 degree bins over [0, 90] */
 #define PD_PNSTAT_MAX_CLASSES          16
@@ -1289,10 +1325,16 @@ int pd_polar_normals_stats(const void* pred, long ld, const void* pol_normals, c
                            double tilt2_min, int aolp_sign, void* stats_normal, void* stats_azimuth, void* az_deg,
                            void* n_deg, void* choice, void* pol_normal, void* workspace, size_t ws_bytes, int N, int H, int W,
                            void* stream);
+int pd_polar_normals_stats_ray(const void* pred, long ld, const void* K, int ray_frame, const void* pol_normals,
+                               const void* xolp, long ldp, const void* mask, const int* classes, int n_classes,
+                               const void* valid, const void* cos_edges, float rho_min, float rho_max, double tilt2_min,
+                               int aolp_sign, void* stats_normal, void* stats_azimuth, void* az_deg, void* n_deg, void* choice,
+                               void* pol_normal, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
 
 /* The polarimetric normals loss (csrc/polar_loss.hip): the two figures of pd_polar_normals_stats as a training term on a depth
  * map, so that Evaluation.test_polar_normals reports what training minimises.  It needs one frame, no ground truth and no
- * pose.  Like the evaluator it keeps the orthographic convention of calc_normals (no per-pixel viewing-ray frame).
+ * pose.  Like the evaluator it keeps the orthographic convention of calc_normals by default; pd_polar_loss_fwd_ray / _bwd_ray
+ * with ray_frame = 1 form both terms in the frame of each pixel's viewing ray (THE RAY FRAME, above, and the last paragraph).
  * tests/polar_loss_ref.py states the definition in NumPy.
  *
  * depth        fp32 [N,1,H,W]
@@ -1347,7 +1389,16 @@ int pd_polar_normals_stats(const void* pred, long ld, const void* pol_normals, c
  * device is touched: bad shape, a null depth / K / pol_normals / xolp / state / sums / values / workspace (/ gvalues /
  * gdepth), ldp < W, aolp_sign not +-1, dolp_weighted not 0 or 1, a non-finite or inverted rho_min / rho_max, tilt2_min outside
  * [0, 1), pol_normals or workspace not 16-byte aligned, sums or maps not 8-byte aligned, ws_bytes too small, a frame beyond
- * 2^30 pixels ("too large"). */
+ * 2^30 pixels ("too large").
+ *
+ * pd_polar_loss_fwd_ray / pd_polar_loss_bwd_ray take ray_frame (0 or 1) after dolp_weighted and are otherwise the two calls
+ * above: same outputs, workspace and launches, still capturable; with ray_frame = 0 they write the bytes of the old entries.
+ * One more refusal: ray_frame not 0 or 1.  With ray_frame = 1 (THE RAY FRAME, above): forward, p' = R(x, y) p is formed right
+ * after the conversion of p to fp64 and stands for p from the `bad` gate on; the NEGATED bit means p'z < 0, i.e. the surface is
+ * seen from behind (p.u < 0), which a depth map's own normal is not under a sane camera.  Backward: the halo evaluation
+ * rebuilds p' from p, dL/dp' is formed exactly as above with p' for p, then dL/dp = R^T dL/dp' in fp64, then the sign is
+ * restored for a negated vector, then the sum is rounded once to fp32 and the fp32 chain above follows.  There is no gradient
+ * with respect to K. */
 #define PD_PLOSS_SUMS                4
 #define PD_PLOSS_COUNTERS            7        /* n_normal, n_azimuth, dolp_out, bad, frontal, spec, flipped */
 #define PD_PLOSS_RECORD_BYTES        96
@@ -1364,6 +1415,13 @@ int pd_polar_loss_fwd(const void* depth, const void* K, const void* pol_normals,
 int pd_polar_loss_bwd(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp, const void* state,
                       const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted, void* gdepth, int N, int H, int W,
                       void* stream);
+int pd_polar_loss_fwd_ray(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+                          const void* valid, float rho_min, float rho_max, double tilt2_min, int aolp_sign, int dolp_weighted,
+                          int ray_frame, void* state, void* sums, void* values, void* maps, void* workspace, size_t ws_bytes,
+                          int N, int H, int W, void* stream);
+int pd_polar_loss_bwd_ray(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+                          const void* state, const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted,
+                          int ray_frame, void* gdepth, int N, int H, int W, void* stream);
 
 /* Row softmax of the attention variant (BASELINE config 5; SURVEY A17 -- defined by this build, the reference
  * branch is absent): in place x[r][:] = softmax(scale * x[r][:]) and its backward

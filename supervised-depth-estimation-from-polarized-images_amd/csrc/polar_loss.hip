@@ -17,8 +17,14 @@
 // state byte; a counted pixel forms dL/dp in fp64 from the winner and the branch the byte names (data, not decisions made
 // again), rounds it once to fp32 and takes it through normalize12 and the cross product to (dA, dB) in LDS; the 3 x 3
 // transposed Sobel gather runs from there.  No [N,H,W,6] intermediate reaches memory.
+//
+// RAY (a compile-time parameter of both kernels): the terms are formed in the frame of the pixel's viewing ray
+// (ray_frame.hpp).  Forward: p' = R(x, y) p right after the conversion to fp64, and p' stands for p from the `bad` gate on.
+// Backward: the halo evaluation rebuilds p' from p, forms dL/dp' as before and takes it back with R^T in fp64 before the
+// single rounding.  There is no gradient with respect to K.
 #include "pd_common.h"
 #include "depth_normals.hpp"
+#include "ray_frame.hpp"
 #include "frame_reduce.hpp"
 #include "wave_ops.hpp"
 
@@ -64,8 +70,11 @@ struct Pix {
     double cx[3], cy[3], cz[3], b2[3];
     bool fin, any;
 };
-__device__ __forceinline__ void load_pix(Pix& q, V3 p, const float* __restrict__ pol_f, size_t plane, size_t po, double sign) {
+template <bool RAY>
+__device__ __forceinline__ void load_pix(Pix& q, V3 p, Cam c, int x, int y, const float* __restrict__ pol_f, size_t plane,
+                                         size_t po, double sign) {
     q.px = (double)p.x; q.py = (double)p.y; q.pz = (double)p.z;
+    if constexpr (RAY) pd_ray::rotate(pd_ray::make(c, x, y), q.px, q.py, q.pz);
     q.a2 = (q.px * q.px + q.py * q.py) + q.pz * q.pz;
     q.fin = true; q.any = false;
 #pragma unroll
@@ -80,6 +89,7 @@ __device__ __forceinline__ void load_pix(Pix& q, V3 p, const float* __restrict__
 }
 __device__ __forceinline__ void negate(Pix& q) { q.px = -q.px; q.py = -q.py; q.pz = -q.pz; }
 
+template <bool RAY>
 __global__ __launch_bounds__(LT) void ploss_fwd_kernel(const float* __restrict__ depth, const float* __restrict__ K,
                                                        const float* __restrict__ pol, const float* __restrict__ xolp,
                                                        const unsigned char* __restrict__ valid,
@@ -109,9 +119,10 @@ __global__ __launch_bounds__(LT) void ploss_fwd_kernel(const float* __restrict__
                 acc[kSums + cDolpOut] += 1.0;
             } else {
                 V3 A, B; float nv;
-                const V3 p = depth_normal(depth + n * g.H * g.W, g.H, g.W, x, y, load_cam(K, n), A, B, nv);
+                const Cam c = load_cam(K, n);
+                const V3 p = depth_normal(depth + n * g.H * g.W, g.H, g.W, x, y, c, A, B, nv);
                 Pix q;
-                load_pix(q, p, pol + (size_t)n * 9 * g.plane, g.plane, po, g.sign);
+                load_pix<RAY>(q, p, c, x, y, pol + (size_t)n * 9 * g.plane, g.plane, po, g.sign);
                 if (!(__builtin_isfinite(q.a2) && q.a2 > 0.0 && q.fin && q.any)) {
                     gate = gateBad;
                     acc[kSums + cBad] += 1.0;
@@ -192,10 +203,16 @@ __global__ __launch_bounds__(256) void ploss_finalize_kernel(const double* __res
 
 // dL/d(nn) of a counted pixel, fp64, rounded once: the winner and the branch are what `st` says, so only their candidates are
 // read.  cand = the pixel's entry of plane 0; wn_ = g_n w / sum w, wa_ = g_a w / sum w
-__device__ __forceinline__ V3 grad_normal(V3 nn, const float* __restrict__ cand, size_t plane, double sign, int st, double wn_,
-                                          double wa_) {
+template <bool RAY>
+__device__ __forceinline__ V3 grad_normal(V3 nn, Cam c, int x, int y, const float* __restrict__ cand, size_t plane, double sign,
+                                          int st, double wn_, double wa_) {
     const bool neg = (st & PD_PLOSS_STATE_NEGATED) != 0;
-    const double ux = (double)nn.x, uy = (double)nn.y, uz = (double)nn.z;
+    double ux = (double)nn.x, uy = (double)nn.y, uz = (double)nn.z;
+    pd_ray::Frame fr{0.0, 0.0, 1.0};
+    if constexpr (RAY) {
+        fr = pd_ray::make(c, x, y);
+        pd_ray::rotate(fr, ux, uy, uz);               // the forward pass's p', before the orientation
+    }
     const double a2 = (ux * ux + uy * uy) + uz * uz;                  // negation is exact: the forward pass's a2
     const double px = neg ? -ux : ux, py = neg ? -uy : uy, pz = neg ? -uz : uz;
     double gx = 0.0, gy = 0.0, gz = 0.0;
@@ -224,10 +241,12 @@ __device__ __forceinline__ V3 grad_normal(V3 nn, const float* __restrict__ cand,
             gx += f * (cx - mt * px); gy += f * (cy - mt * py);
         }
     }
+    if constexpr (RAY) pd_ray::rotate_t(fr, gx, gy, gz);              // dL/dp = R^T dL/dp'
     if (neg) { gx = -gx; gy = -gy; gz = -gz; }
     return V3{(float)gx, (float)gy, (float)gz};
 }
 
+template <bool RAY>
 __global__ __launch_bounds__(LT) void ploss_bwd_kernel(const float* __restrict__ depth, const float* __restrict__ K,
                                                        const float* __restrict__ pol, const float* __restrict__ xolp,
                                                        const unsigned char* __restrict__ state, const float* __restrict__ gv,
@@ -258,7 +277,7 @@ __global__ __launch_bounds__(LT) void ploss_bwd_kernel(const float* __restrict__
                     V3 A, B; float nv;
                     const V3 nn = depth_normal(dn, H, W, x, y, c, A, B, nv);
                     const double w = g.weighted ? (double)rho_f[po] : 1.0;
-                    const V3 wn = grad_normal(nn, pol_f + po, g.plane, g.sign, st, cn * w, ca * w);
+                    const V3 wn = grad_normal<RAY>(nn, c, x, y, pol_f + po, g.plane, g.sign, st, cn * w, ca * w);
                     normal_grad_to_ab(wn, nn, nv, A, B, dA, dB);
                 }
             }
@@ -277,7 +296,8 @@ __global__ __launch_bounds__(LT) void ploss_bwd_kernel(const float* __restrict__
 
 // what both entry points refuse
 inline int common_args(const char* who, const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
-                       int aolp_sign, int dolp_weighted, int N, int H, int W) {
+                       int aolp_sign, int dolp_weighted, int ray_frame, int N, int H, int W) {
+    PD_REQUIRE(ray_frame == 0 || ray_frame == 1, "%s: ray_frame = %d must be 0 or 1", who, ray_frame);
     PD_REQUIRE(N >= 0 && H > 0 && W > 0, "%s: bad shape (N = %d, H = %d, W = %d)", who, N, H, W);
     PD_REQUIRE(depth && K && pol_normals && xolp, "%s: depth, K, pol_normals and xolp must not be null", who);
     PD_REQUIRE(ldp >= W, "%s: the row pitch ldp = %ld must be at least W = %d", who, ldp, W);
@@ -297,6 +317,14 @@ inline Geo geo_of(long ldp, int aolp_sign, int dolp_weighted, int N, int H, int 
     return g;
 }
 
+int fwd_call(const char* who, const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+             const void* valid, float rho_min, float rho_max, double tilt2_min, int aolp_sign, int dolp_weighted, int ray_frame,
+             void* state, void* sums, void* values, void* maps, void* workspace, size_t ws_bytes, int N, int H, int W,
+             void* stream);
+int bwd_call(const char* who, const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+             const void* state, const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted, int ray_frame,
+             void* gdepth, int N, int H, int W, void* stream);
+
 }  // namespace
 
 extern "C" int pd_polar_loss_rows(int N, int H, int W) {
@@ -307,8 +335,39 @@ extern "C" int pd_polar_loss_fwd(const void* depth, const void* K, const void* p
                                  const void* valid, float rho_min, float rho_max, double tilt2_min, int aolp_sign,
                                  int dolp_weighted, void* state, void* sums, void* values, void* maps, void* workspace,
                                  size_t ws_bytes, int N, int H, int W, void* stream) {
-    const char* who = "pd_polar_loss_fwd";
-    if (int e = common_args(who, depth, K, pol_normals, xolp, ldp, aolp_sign, dolp_weighted, N, H, W)) return e;
+    return fwd_call("pd_polar_loss_fwd", depth, K, pol_normals, xolp, ldp, valid, rho_min, rho_max, tilt2_min, aolp_sign,
+                    dolp_weighted, 0, state, sums, values, maps, workspace, ws_bytes, N, H, W, stream);
+}
+
+extern "C" int pd_polar_loss_fwd_ray(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+                                     const void* valid, float rho_min, float rho_max, double tilt2_min, int aolp_sign,
+                                     int dolp_weighted, int ray_frame, void* state, void* sums, void* values, void* maps,
+                                     void* workspace, size_t ws_bytes, int N, int H, int W, void* stream) {
+    return fwd_call("pd_polar_loss_fwd_ray", depth, K, pol_normals, xolp, ldp, valid, rho_min, rho_max, tilt2_min, aolp_sign,
+                    dolp_weighted, ray_frame, state, sums, values, maps, workspace, ws_bytes, N, H, W, stream);
+}
+
+extern "C" int pd_polar_loss_bwd(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+                                 const void* state, const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted,
+                                 void* gdepth, int N, int H, int W, void* stream) {
+    return bwd_call("pd_polar_loss_bwd", depth, K, pol_normals, xolp, ldp, state, gvalues, sums, aolp_sign, dolp_weighted, 0,
+                    gdepth, N, H, W, stream);
+}
+
+extern "C" int pd_polar_loss_bwd_ray(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+                                     const void* state, const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted,
+                                     int ray_frame, void* gdepth, int N, int H, int W, void* stream) {
+    return bwd_call("pd_polar_loss_bwd_ray", depth, K, pol_normals, xolp, ldp, state, gvalues, sums, aolp_sign, dolp_weighted,
+                    ray_frame, gdepth, N, H, W, stream);
+}
+
+namespace {
+
+int fwd_call(const char* who, const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+             const void* valid, float rho_min, float rho_max, double tilt2_min, int aolp_sign, int dolp_weighted, int ray_frame,
+             void* state, void* sums, void* values, void* maps, void* workspace, size_t ws_bytes, int N, int H, int W,
+             void* stream) {
+    if (int e = common_args(who, depth, K, pol_normals, xolp, ldp, aolp_sign, dolp_weighted, ray_frame, N, H, W)) return e;
     PD_REQUIRE(state && sums && values && workspace, "%s: state, sums, values and workspace must not be null", who);
     PD_REQUIRE(std::isfinite(rho_min) && std::isfinite(rho_max) && rho_min <= rho_max,
                "%s: the DoLP range [rho_min = %g, rho_max = %g] must be finite and not inverted", who, (double)rho_min,
@@ -324,7 +383,7 @@ extern "C" int pd_polar_loss_fwd(const void* depth, const void* K, const void* p
     hipStream_t st = (hipStream_t)stream;
     Geo g = geo_of(ldp, aolp_sign, dolp_weighted, N, H, W);
     g.rho_min = (double)rho_min; g.rho_max = (double)rho_max; g.tilt2_min = tilt2_min;
-    hipLaunchKernelGGL(ploss_fwd_kernel, dim3((unsigned)rows), dim3(LT), 0, st, static_cast<const float*>(depth),
+    hipLaunchKernelGGL(ray_frame ? ploss_fwd_kernel<true> : ploss_fwd_kernel<false>, dim3((unsigned)rows), dim3(LT), 0, st, static_cast<const float*>(depth),
                        static_cast<const float*>(K), static_cast<const float*>(pol_normals), static_cast<const float*>(xolp),
                        static_cast<const unsigned char*>(valid), static_cast<unsigned char*>(state), static_cast<float2*>(maps),
                        static_cast<double*>(workspace), g);
@@ -333,11 +392,10 @@ extern "C" int pd_polar_loss_fwd(const void* depth, const void* K, const void* p
     return pd::check_launch(who);
 }
 
-extern "C" int pd_polar_loss_bwd(const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
-                                 const void* state, const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted,
-                                 void* gdepth, int N, int H, int W, void* stream) {
-    const char* who = "pd_polar_loss_bwd";
-    if (int e = common_args(who, depth, K, pol_normals, xolp, ldp, aolp_sign, dolp_weighted, N, H, W)) return e;
+int bwd_call(const char* who, const void* depth, const void* K, const void* pol_normals, const void* xolp, long ldp,
+             const void* state, const void* gvalues, const void* sums, int aolp_sign, int dolp_weighted, int ray_frame,
+             void* gdepth, int N, int H, int W, void* stream) {
+    if (int e = common_args(who, depth, K, pol_normals, xolp, ldp, aolp_sign, dolp_weighted, ray_frame, N, H, W)) return e;
     PD_REQUIRE(state && gvalues && sums && gdepth, "%s: state, gvalues, sums and gdepth must not be null", who);
     PD_REQUIRE(pd::aligned8(sums), "%s: sums must be 8-byte aligned", who);
     const int tiles_h = (H + SB_TR - 1) / SB_TR, tiles_w = (W + SB_TW - 1) / SB_TW;
@@ -345,10 +403,12 @@ extern "C" int pd_polar_loss_bwd(const void* depth, const void* K, const void* p
     PD_REQUIRE(ntiles < (1L << 31), "%s: a batch of %d frames of %d x %d has too many tiles", who, N, H, W);
     if (N == 0) return PD_OK;
     const Geo g = geo_of(ldp, aolp_sign, dolp_weighted, N, H, W);
-    hipLaunchKernelGGL(ploss_bwd_kernel, dim3((unsigned)(ntiles > PD_PLOSS_BWD_TILES_PER_TRIP ? PD_PLOSS_BWD_TILES_PER_TRIP : ntiles)),
+    hipLaunchKernelGGL(ray_frame ? ploss_bwd_kernel<true> : ploss_bwd_kernel<false>, dim3((unsigned)(ntiles > PD_PLOSS_BWD_TILES_PER_TRIP ? PD_PLOSS_BWD_TILES_PER_TRIP : ntiles)),
                        dim3(LT), 0, (hipStream_t)stream, static_cast<const float*>(depth), static_cast<const float*>(K),
                        static_cast<const float*>(pol_normals), static_cast<const float*>(xolp),
                        static_cast<const unsigned char*>(state), static_cast<const float*>(gvalues),
                        static_cast<const double*>(sums), static_cast<float*>(gdepth), g, tiles_h, tiles_w, (int)ntiles);
     return pd::check_launch(who);
 }
+
+}  // namespace

@@ -15,6 +15,7 @@
 // A bin is the number of table entries cos_edges[j] >= c, found by binary search over a copy of the caller's table in LDS:
 // acos takes no part in any decision.
 #include "class_records.hpp"
+#include "ray_frame.hpp"
 
 #include <cmath>
 
@@ -61,6 +62,10 @@ __device__ __forceinline__ int bin_of(const double* edges, double c, int n) {
     return lo;
 }
 
+// RAY: the prediction is scored in the frame of its pixel's viewing ray (ray_frame.hpp): p' = R(x, y) p replaces p from the
+// `bad` gate on, and the pol_normal map leaves as R^T of the winner.  The frame is three doubles next to 128 VGPRs of sums:
+// it is formed, used and dropped before the accumulators are touched, and formed again for the pol_normal map.
+template <bool RAY>
 __global__ __launch_bounds__(kThreads) void pnstat_kernel(const float* __restrict__ pred, const float* __restrict__ pol,
                                                           const float* __restrict__ xolp, const int* __restrict__ mask,
                                                           const unsigned char* __restrict__ valid,
@@ -68,7 +73,8 @@ __global__ __launch_bounds__(kThreads) void pnstat_kernel(const float* __restric
                                                           float* __restrict__ n_deg, unsigned char* __restrict__ choice,
                                                           float4* __restrict__ pol_normal, unsigned* __restrict__ stats_n,
                                                           unsigned* __restrict__ stats_a, double* __restrict__ ws_n,
-                                                          double* __restrict__ ws_a, Classes cls, Geo g) {
+                                                          double* __restrict__ ws_a, Classes cls, Geo g,
+                                                          const float* __restrict__ Kmat) {
     extern __shared__ __align__(16) unsigned char smem[];
     double* edges = reinterpret_cast<double*>(smem);                                  // [720], the last one is padding
     double* wsum = edges + RecN::kBins;                                               // [kWaves][kMaxK][4]
@@ -91,6 +97,8 @@ __global__ __launch_bounds__(kThreads) void pnstat_kernel(const float* __restric
     const int* mask_f = mask ? mask + base : nullptr;
     const unsigned char* valid_f = valid ? valid + base : nullptr;
     const float nanf_ = __builtin_nanf("");
+    pd_dn::Cam cam{1.f, 1.f, 0.f, 0.f};
+    if constexpr (RAY) cam = pd_dn::load_cam(Kmat, (long)img);      // uniform: once per workgroup
 
     double s[kMaxK][kSums];
 #pragma unroll
@@ -120,6 +128,7 @@ __global__ __launch_bounds__(kThreads) void pnstat_kernel(const float* __restric
                     const float* pp = pred_f + (size_t)item * (size_t)g.ld;
                     px = (double)pp[0]; py = (double)pp[1]; pz = (double)pp[2];
                 }
+                if constexpr (RAY) pd_ray::rotate(pd_ray::make(cam, (int)x, (int)y), px, py, pz);
                 // fp32 products are exact in fp64; the sums keep the order of the definition (the file is built without
                 // contraction)
                 a2 = (px * px + py * py) + pz * pz;
@@ -179,6 +188,7 @@ __global__ __launch_bounds__(kThreads) void pnstat_kernel(const float* __restric
                     double ox = cx[b], oy = cy[b], oz = cz[b];
                     if (win & 1) { ox = -ox; oy = -oy; }
                     if (neg) { ox = -ox; oy = -oy; oz = -oz; }
+                    if constexpr (RAY) pd_ray::rotate_t(pd_ray::make(cam, (int)x, (int)y), ox, oy, oz);   // camera coordinates
                     o = make_float4((float)ox, (float)oy, (float)oz, 0.f);
                 }
                 pol_normal[base + item] = o;
@@ -251,12 +261,15 @@ extern "C" size_t pd_polar_normals_stats_workspace(int N, int H, int W, int K) {
     return 2 * records_workspace(N, K, groups_of(H, W), kSums);      // the normal set's partial sums, then the azimuth set's
 }
 
-extern "C" int pd_polar_normals_stats(const void* pred, long ld, const void* pol_normals, const void* xolp, long ldp,
-                                      const void* mask, const int* classes, int K, const void* valid, const void* cos_edges,
-                                      float rho_min, float rho_max, double tilt2_min, int aolp_sign, void* stats_normal,
-                                      void* stats_azimuth, void* az_deg, void* n_deg, void* choice, void* pol_normal,
-                                      void* workspace, size_t ws_bytes, int N, int H, int W, void* stream) {
-    const char* who = "pd_polar_normals_stats";
+namespace {
+
+int pnstat_call(const char* who, const void* pred, long ld, const void* intrinsics, int ray_frame, const void* pol_normals,
+                const void* xolp, long ldp, const void* mask, const int* classes, int K, const void* valid, const void* cos_edges,
+                float rho_min, float rho_max, double tilt2_min, int aolp_sign, void* stats_normal, void* stats_azimuth,
+                void* az_deg, void* n_deg, void* choice, void* pol_normal, void* workspace, size_t ws_bytes, int N, int H, int W,
+                void* stream) {
+    PD_REQUIRE(ray_frame == 0 || ray_frame == 1, "%s: ray_frame = %d must be 0 or 1", who, ray_frame);
+    PD_REQUIRE(ray_frame == 0 || intrinsics, "%s: ray_frame = 1 needs the intrinsics K [N,4,4], K must not be null", who);
     PD_REQUIRE(N >= 0 && H > 0 && W > 0, "%s: bad shape (N = %d, H = %d, W = %d)", who, N, H, W);
     PD_REQUIRE(pred && pol_normals && xolp && classes && cos_edges && workspace,
                "%s: pred, pol_normals, xolp, classes, cos_edges and workspace must not be null", who);
@@ -300,7 +313,9 @@ extern "C" int pd_polar_normals_stats(const void* pred, long ld, const void* pol
         double* ws_a = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + half) + part;
         if (rec_n) zero_records<RecN>(rec_n, nb, K, st);
         if (rec_a) zero_records<RecA>(rec_a, nb, K, st);
-        hipLaunchKernelGGL(pnstat_kernel, dim3((unsigned)(nb * g.G), (unsigned)sets), dim3(kThreads), lds, st,
+        const float* Kn = ray_frame ? static_cast<const float*>(intrinsics) + (size_t)n0 * 16 : nullptr;
+        const auto kern = ray_frame ? pnstat_kernel<true> : pnstat_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(nb * g.G), (unsigned)sets), dim3(kThreads), lds, st,
                            static_cast<const float*>(pred) + o * (size_t)ld,
                            static_cast<const float*>(pol_normals) + (size_t)n0 * 9 * g.plane,
                            static_cast<const float*>(xolp) + (size_t)n0 * 2 * g.plane,
@@ -309,11 +324,34 @@ extern "C" int pd_polar_normals_stats(const void* pred, long ld, const void* pol
                            static_cast<const double*>(cos_edges), az_deg ? static_cast<float*>(az_deg) + o : nullptr,
                            n_deg ? static_cast<float*>(n_deg) + o : nullptr,
                            choice ? static_cast<unsigned char*>(choice) + o : nullptr,
-                           pol_normal ? static_cast<float4*>(pol_normal) + o : nullptr, rec_n, rec_a, ws_n, ws_a, cls, g);
+                           pol_normal ? static_cast<float4*>(pol_normal) + o : nullptr, rec_n, rec_a, ws_n, ws_a, cls, g, Kn);
         if (rec_n) hipLaunchKernelGGL(HIP_KERNEL_NAME(records_finalize_kernel<RecN>), dim3((unsigned)(nb * K)), dim3(kThreads),
                                       0, st, rec_n, ws_n, K, (int)g.G);
         if (rec_a) hipLaunchKernelGGL(HIP_KERNEL_NAME(records_finalize_kernel<RecA>), dim3((unsigned)(nb * K)), dim3(kThreads),
                                       0, st, rec_a, ws_a, K, (int)g.G);
     }
     return pd::check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int pd_polar_normals_stats(const void* pred, long ld, const void* pol_normals, const void* xolp, long ldp,
+                                      const void* mask, const int* classes, int K, const void* valid, const void* cos_edges,
+                                      float rho_min, float rho_max, double tilt2_min, int aolp_sign, void* stats_normal,
+                                      void* stats_azimuth, void* az_deg, void* n_deg, void* choice, void* pol_normal,
+                                      void* workspace, size_t ws_bytes, int N, int H, int W, void* stream) {
+    return pnstat_call("pd_polar_normals_stats", pred, ld, nullptr, 0, pol_normals, xolp, ldp, mask, classes, K, valid, cos_edges,
+                       rho_min, rho_max, tilt2_min, aolp_sign, stats_normal, stats_azimuth, az_deg, n_deg, choice, pol_normal,
+                       workspace, ws_bytes, N, H, W, stream);
+}
+
+extern "C" int pd_polar_normals_stats_ray(const void* pred, long ld, const void* K_intrinsics, int ray_frame,
+                                          const void* pol_normals, const void* xolp, long ldp, const void* mask,
+                                          const int* classes, int K, const void* valid, const void* cos_edges, float rho_min,
+                                          float rho_max, double tilt2_min, int aolp_sign, void* stats_normal,
+                                          void* stats_azimuth, void* az_deg, void* n_deg, void* choice, void* pol_normal,
+                                          void* workspace, size_t ws_bytes, int N, int H, int W, void* stream) {
+    return pnstat_call("pd_polar_normals_stats_ray", pred, ld, K_intrinsics, ray_frame, pol_normals, xolp, ldp, mask, classes, K,
+                       valid, cos_edges, rho_min, rho_max, tilt2_min, aolp_sign, stats_normal, stats_azimuth, az_deg, n_deg,
+                       choice, pol_normal, workspace, ws_bytes, N, H, W, stream);
 }

@@ -32,7 +32,8 @@ class Evaluation:
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
                  pol_calibration=None, normals_decoder=None, pose_network=None, multi_frame=False, matching_ids=(0, -1),
-                 multi_poses="files", num_depth_bins=96, depth_binning="linear", aolp_sign=None):
+                 multi_poses="files", num_depth_bins=96, depth_binning="linear", aolp_sign=None,
+                 polar_ray_frame=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -67,7 +68,10 @@ class Evaluation:
         ``predict_multi``, ``test_depth(source="multi")``; ``test_pose_chain`` needs the pose network only.
 
         ``aolp_sign``: +1 or -1, the handedness of the sensor's AoLP as ``test_polar_normals`` takes it (or
-        $PD_POL_AOLP_SIGN); None = +1.  Nothing else reads it."""
+        $PD_POL_AOLP_SIGN); None = +1.  Nothing else reads it.  ``polar_ray_frame``: ``test_polar_normals`` scores in the frame
+        of each pixel's viewing ray instead of the orthographic convention (``polar_normals_stats(ray_frame=True)``), for all
+        its sources; None reads $PD_POLAR_RAY_FRAME == "1".  Nothing else reads it."""
+        self.polar_ray_frame = (os.environ.get("PD_POLAR_RAY_FRAME") == "1") if polar_ray_frame is None else bool(polar_ray_frame)
         aolp_sign = aolp_sign if aolp_sign is not None else os.environ.get("PD_POL_AOLP_SIGN")
         self.aolp_sign = 1 if aolp_sign is None else int(aolp_sign)
         if self.aolp_sign not in (1, -1):
@@ -330,7 +334,8 @@ class Evaluation:
         window is inside the depth range -- how well measurement and true geometry agree per material, the ceiling for any
         prediction.  ``xolp`` and the nine-channel normals come from ``polar_inputs`` whatever ``augment_normals`` says; the
         handedness is ``Evaluation(aolp_sign=)``.  ``rho_min`` and ``tilt_min_deg`` are conventions, not measurements
-        (``polar_normals_stats``).
+        (``polar_normals_stats``).  With ``Evaluation(polar_ray_frame=True)`` every source is scored in the frame of each
+        pixel's viewing ray, and the headings say "ray frame".
 
         Prints, and returns {class: {"normal": r, "azimuth": r}} with r = {"per_image": [8], "pooled": [8], and the set's
         four counters by name (ints)}: mean, median, rmse (degrees), the shares within 11.25 / 22.5 / 30 degrees, the pixel
@@ -358,7 +363,8 @@ class Evaluation:
                                        dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
             st = polar_normals_eval.polar_normals_stats(pred, pol, inputs["xolp", 0, 0], K=inputs[("K", 0)],
                                                         mask=inputs[("mask", 0, 0)], valid=valid, rho_min=rho_min,
-                                                        rho_max=rho_max, tilt_min_deg=tilt_min_deg, aolp_sign=self.aolp_sign)
+                                                        rho_max=rho_max, tilt_min_deg=tilt_min_deg, aolp_sign=self.aolp_sign,
+                                                        ray_frame=self.polar_ray_frame)
             for name in sets:
                 rs = getattr(st, name)
                 m = rs.metrics()
@@ -378,7 +384,8 @@ class Evaluation:
             rs = getattr(total, sname)
             per_image = (sums[sname] / counts[sname][:, None].double()).cpu().numpy()
             pooled, counters = rs.pooled().cpu().numpy(), rs.pooled_counters().cpu().numpy()
-            print(f"polar {sname} ({source}) " + ("{:>9} " * nm).format(*polar_normals_eval.METRIC_NAMES))
+            frame = ", ray frame" if self.polar_ray_frame else ""
+            print(f"polar {sname} ({source}{frame}) " + ("{:>9} " * nm).format(*polar_normals_eval.METRIC_NAMES))
             for k, name in enumerate(total.names):
                 r = {"per_image": per_image[k], "pooled": pooled[k]}
                 r.update({c: int(counters[k][j]) for j, c in enumerate(rs.counter_names)})

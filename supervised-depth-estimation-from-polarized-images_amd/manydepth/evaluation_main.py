@@ -4,7 +4,7 @@ PD_EVAL_POINTCLOUD=1 the point-cloud report (Evaluation.test_pointcloud), PD_EVA
 pose network (Evaluation.test_pose; needs PD_POSE_NETWORK=1, which makes Evaluation build and load the pose network),
 PD_EVAL_CONSISTENCY=1 the multi-view consistency report of the predicted depth (Evaluation.test_consistency),
 PD_EVAL_POLAR_NORMALS=1 the polarimetric normals report (Evaluation.test_polar_normals; PD_POL_AOLP_SIGN=-1 for a sensor of
-the other AoLP handedness)."""
+the other AoLP handedness, PD_POLAR_RAY_FRAME=1 to score in the frame of each pixel's viewing ray)."""
 import os
 
 from manydepth.evaluation import Evaluation

@@ -59,12 +59,15 @@ def options_from_environment(opts, env=os.environ):
     # (opt.polar_loss; works in every training mode of this build, PD_STEP_GRAPH=1 is refused with it).
     # PD_POLAR_LOSS_WHERE=all|holes: every pixel, or only those without ground-truth depth (opt.polar_loss_where; default all).
     # PD_POL_AOLP_SIGN=-1: a sensor of the other AoLP handedness, as for the evaluation's report (opt.pol_aolp_sign)
+    # PD_POLAR_RAY_FRAME=1: the term in the frame of each pixel's viewing ray (opt.polar_ray_frame; needs PD_POLAR_LOSS)
     if env.get("PD_POLAR_LOSS"):
         opts.polar_loss = [float(x) for x in env["PD_POLAR_LOSS"].split(",")]
     if env.get("PD_POLAR_LOSS_WHERE"):
         opts.polar_loss_where = env["PD_POLAR_LOSS_WHERE"]
     if env.get("PD_POL_AOLP_SIGN"):
         opts.pol_aolp_sign = int(env["PD_POL_AOLP_SIGN"])
+    if env.get("PD_POLAR_RAY_FRAME"):
+        opts.polar_ray_frame = env["PD_POLAR_RAY_FRAME"] == "1"
     return opts
 
 

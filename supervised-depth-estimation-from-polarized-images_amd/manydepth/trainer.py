@@ -40,7 +40,8 @@ neighbour towards whatever its loader substituted -- items whose ``frame_valid``
 the present ones, as in the photometric term.  ``opt.polar_loss = (w_n, w_a)`` (``PD_POLAR_LOSS``; any of the modes above)
 adds the polarimetric normals loss: per scale the normals of the predicted depth map against the candidates K1 derives from
 DoLP / AoLP, on the decisions of ``Evaluation.test_polar_normals`` (``polar_normal_loss/{s}``, ``polar_azimuth_loss/{s}``;
-``_polar_loss_option``); without it nothing changes in a bit, and ``PD_STEP_GRAPH=1`` is refused with it.  The cost-volume student's building
+``_polar_loss_option``; ``opt.polar_ray_frame`` / ``PD_POLAR_RAY_FRAME=1``: in the frame of each pixel's viewing ray); without it
+nothing changes in a bit, and ``PD_STEP_GRAPH=1`` is refused with it.  The cost-volume student's building
 blocks exist -- the plane sweep (``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training
 branch (``--train_student``: matching augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it,
 ``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
@@ -123,9 +124,17 @@ def _polar_loss_option(opt):
     supervised terms see nothing.  ``opt.pol_aolp_sign`` = +1 (default) or -1, the handedness of the sensor's AoLP, as
     ``Evaluation(aolp_sign=)``.  Not reference CLI flags: manydepth/train.py maps PD_POLAR_LOSS / PD_POLAR_LOSS_WHERE /
     PD_POL_AOLP_SIGN onto them.  Returns (weights or None, where, sign); the weights are written back as a list of two floats,
-    so that they travel in opt.json."""
+    so that they travel in opt.json.  ``opt.polar_ray_frame`` (PD_POLAR_RAY_FRAME=1; default off) forms the term in the frame
+    of each pixel's viewing ray instead of the orthographic convention; it is validated here, written back as a bool, and
+    refused without ``opt.polar_loss``: there is no term it could apply to."""
     w = getattr(opt, "polar_loss", None)
+    ray = getattr(opt, "polar_ray_frame", None)
+    if ray is not None and not (isinstance(ray, (bool, int, np.integer)) and int(ray) in (0, 1)):
+        raise ValueError(f"opt.polar_ray_frame must be True or False, got {ray!r}")
     if w is None:
+        if ray:
+            raise ValueError("opt.polar_ray_frame is set without opt.polar_loss: the ray frame is an option of the "
+                             "polarimetric term, set opt.polar_loss = (w_n, w_a) too")
         return None, "all", 1
     if isinstance(w, str):
         w = w.split(",")
@@ -143,6 +152,8 @@ def _polar_loss_option(opt):
     if sign not in (1, -1):
         raise ValueError(f"opt.pol_aolp_sign must be +1 or -1, got {getattr(opt, 'pol_aolp_sign')!r}")
     opt.polar_loss = w
+    if ray is not None:
+        opt.polar_ray_frame = bool(ray)
     return w, where, sign
 
 
@@ -215,6 +226,7 @@ class Trainer:
         # decisions of Evaluation.test_polar_normals (polardepth.functional.polarimetric_loss, csrc/polar_loss.hip).  It needs
         # no ground truth and no pose, so it works in the supervised-only mode and in both photometric modes
         self.polar_loss, self.polar_loss_where, self.pol_aolp_sign = _polar_loss_option(self.opt)
+        self.polar_ray_frame = bool(getattr(self.opt, "polar_ray_frame", False))     # validated just above
         if self.polar_loss is not None and (os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False))):
             raise NotImplementedError("PD_STEP_GRAPH=1 with opt.polar_loss: the polarimetric term is not captured yet; "
                                       "run it without the step graph")
@@ -627,7 +639,8 @@ class Trainer:
             if self.polar_loss_where == "holes":
                 valid = ~((inputs["depth"] >= self.opt.min_depth) & (inputs["depth"] <= self.opt.max_depth))
             terms = PF.polarimetric_loss(self.loss_cfg, disps, depths, inputs[("K", 0)], inputs[("pol_normals", 0, 0)],
-                                         inputs[("xolp", 0, 0)], valid, aolp_sign=self.pol_aolp_sign)
+                                         inputs[("xolp", 0, 0)], valid, aolp_sign=self.pol_aolp_sign,
+                                         ray_frame=self.polar_ray_frame)
             w_n, w_a = self.polar_loss
             polar = []
             for i, s in enumerate(scales):

@@ -1175,7 +1175,7 @@ def student_loss(cfg, disps, depths, mono_depths, target, sources, K, inv_K, pos
 
 
 def polarimetric_loss(cfg, disps, depths, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.0, tilt_min_deg=5.0,
-                      aolp_sign=1, dolp_weighted=True):
+                      aolp_sign=1, dolp_weighted=True, ray_frame=False):
     """The polarimetric normals term per scale -> [(L_n, L_a)]: every full-resolution depth map goes on the tape through
     ``DispDepthFn``, as ``_multiview_chain`` does it, and is scored against the polarisation by ``ops.polar_loss``.  The term
     needs one frame, no ground truth and no pose.
@@ -1184,12 +1184,13 @@ def polarimetric_loss(cfg, disps, depths, K, pol_normals, xolp, valid=None, rho_
              map is data); depths: the full-resolution depth maps [N,1,H,W] ``multiscale_loss`` returned for them
     K        [N,4,4] of scale 0; pol_normals [N,9,H,W], xolp [N,2,H,W]: what K1 returns as "normals" and "xolp"
     valid    [N,1,H,W] or [N,H,W] or None: the pixels the term may use
-    The remaining options are those of ``ops.polar_loss``."""
+    The remaining options are those of ``ops.polar_loss`` (``ray_frame``: the terms in the per-pixel viewing-ray frame)."""
     losses = []
     for i, d in enumerate(depths):
         if disps is not None and disps[i] is not None:
             d = DispDepthFn.apply(disps[i], d, cfg.min_depth, cfg.max_depth)
-        losses.append(ops.polar_loss(d, K, pol_normals, xolp, valid, rho_min, rho_max, tilt_min_deg, aolp_sign, dolp_weighted))
+        losses.append(ops.polar_loss(d, K, pol_normals, xolp, valid, rho_min, rho_max, tilt_min_deg, aolp_sign, dolp_weighted,
+                                     ray_frame=ray_frame))
     return losses
 
 

@@ -918,16 +918,16 @@ class _PolarLossFn(torch.autograd.Function):
     def forward(ctx, depth, K, pol, xolp, ldp, valid, opts, want_maps):
         N, _, H, W = depth.shape
         dev = depth.device
-        rho_min, rho_max, tilt2, sign, weighted = opts
+        rho_min, rho_max, tilt2, sign, weighted, ray = opts
         state = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
         record = torch.zeros(POLAR_LOSS_RECORD_BYTES, dtype=torch.uint8, device=dev)
         values = torch.zeros(2, dtype=torch.float32, device=dev)
         maps = torch.empty((N, H, W, 2), dtype=torch.float32, device=dev) if want_maps else None
         ws = torch.empty((lib.pd_polar_loss_rows(N, H, W), 11), dtype=torch.float64, device=dev)
-        check(lib.pd_polar_loss_fwd(ptr(depth), ptr(K), ptr(pol), ptr(xolp), ldp, ptr(valid), rho_min, rho_max, tilt2, sign,
-                                    weighted, ptr(state), ptr(record), ptr(values), ptr(maps), ptr(ws), ws.numel() * 8, N, H, W,
-                                    stream_ptr()), "pd_polar_loss_fwd")
-        ctx.geom = (N, H, W, ldp, sign, weighted)
+        check(lib.pd_polar_loss_fwd_ray(ptr(depth), ptr(K), ptr(pol), ptr(xolp), ldp, ptr(valid), rho_min, rho_max, tilt2, sign,
+                                        weighted, ray, ptr(state), ptr(record), ptr(values), ptr(maps), ptr(ws), ws.numel() * 8,
+                                        N, H, W, stream_ptr()), "pd_polar_loss_fwd_ray")
+        ctx.geom = (N, H, W, ldp, sign, weighted, ray)
         ctx.save_for_backward(depth, K, pol, xolp, state, record)
         if maps is None:
             maps = torch.empty(0, dtype=torch.float32, device=dev)
@@ -937,16 +937,16 @@ class _PolarLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gvalues, _gstate, _grecord, _gmaps):
         depth, K, pol, xolp, state, record = ctx.saved_tensors
-        N, H, W, ldp, sign, weighted = ctx.geom
+        N, H, W, ldp, sign, weighted, ray = ctx.geom
         gdepth = torch.empty_like(depth)
-        check(lib.pd_polar_loss_bwd(ptr(depth), ptr(K), ptr(pol), ptr(xolp), ldp, ptr(state),
-                                    ptr(gvalues.float().reshape(2).contiguous()), ptr(record), sign, weighted, ptr(gdepth), N, H, W,
-                                    stream_ptr()), "pd_polar_loss_bwd")
+        check(lib.pd_polar_loss_bwd_ray(ptr(depth), ptr(K), ptr(pol), ptr(xolp), ldp, ptr(state),
+                                        ptr(gvalues.float().reshape(2).contiguous()), ptr(record), sign, weighted, ray, ptr(gdepth),
+                                        N, H, W, stream_ptr()), "pd_polar_loss_bwd_ray")
         return gdepth, None, None, None, None, None, None, None
 
 
 def polar_loss(depth, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.0, tilt_min_deg=5.0, aolp_sign=1,
-               dolp_weighted=True, details=False):
+               dolp_weighted=True, details=False, ray_frame=False):
     """The polarimetric normals loss of a depth map -> (L_n, L_a): what ``polar_normals_eval.polar_normals_stats`` measures as
     the angle to the best candidate and the azimuth residual, as two smooth terms on the same per-pixel decisions,
     L_n = sum w (1 - cos n_deg) / sum w and L_a = sum w sin^2(az_deg) / sum w with w = DoLP (``dolp_weighted``) or 1.  It needs
@@ -956,7 +956,10 @@ def polar_loss(depth, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.
     pol_normals  [N,9,H,W], xolp [N,2,H,W] as ``polar_normals_stats`` takes them (padded rows are read in place)
     valid        [N,1,H,W] or [N,H,W] bool / uint8 or None: a 0 takes the pixel out altogether
     rho_min, rho_max, tilt_min_deg, aolp_sign     the evaluator's options, with the evaluator's conventions
-    details      also return a ``PolarLossDetails``"""
+    details      also return a ``PolarLossDetails``
+    ray_frame    form both terms in the frame of each pixel's viewing ray (the minimal rotation of the ray onto the optical
+                 axis, include/polardepth.h) instead of the orthographic convention of calc_normals; the gradient comes back
+                 through the transposed rotation.  No gradient with respect to K"""
     import math
     from ._records import frames
     from .polar_normals_eval import _planar
@@ -975,7 +978,8 @@ def polar_loss(depth, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.
         raise ValueError(f"polar_loss: tilt_min_deg must be in [0, 90), got {tilt_min_deg!r}")
     if valid is not None:
         valid = frames(valid, "valid", N, H, W).ne(0).to(torch.uint8).contiguous()
-    opts = (float(rho_min), float(rho_max), math.sin(math.radians(float(tilt_min_deg))) ** 2, int(aolp_sign), int(bool(dolp_weighted)))
+    opts = (float(rho_min), float(rho_max), math.sin(math.radians(float(tilt_min_deg))) ** 2, int(aolp_sign), int(bool(dolp_weighted)),
+            int(bool(ray_frame)))
     if N == 0:                           # nothing to launch: both values are 0, and so is the gradient
         dev = depth.device
         values = depth.float().sum() * torch.zeros(2, dtype=torch.float32, device=dev)

@@ -8,8 +8,10 @@ azimuth residual modulo pi against the diffuse and the specular branch (``.azimu
 and no pose.  The by-product is the classical use of a coarse depth prior: the prediction resolves the pi ambiguity and the
 diffuse / specular ambiguity, and the winning candidate per pixel is a disambiguated normal map (``maps=True``).
 
-Not built: the residual uses the orthographic convention of calc_normals (no per-pixel viewing-ray frame).  The training loss on
-the same decisions is ``ops.polar_loss``.
+The candidates are quantities about the viewing ray of their pixel; by default the prediction is scored the orthographic way
+of calc_normals, whose error grows towards the frame's edge.  ``ray_frame=True`` rotates the prediction into the frame of each
+pixel's ray first (the minimal rotation of the ray onto the optical axis; include/polardepth.h).  The training loss on the same
+decisions is ``ops.polar_loss``.
 
 The per-image, per-class records stay on the device; ``Pool.metrics`` / ``pooled`` turn them into the report with torch ops.
 The definition is the header's; tests/polar_normals_ref.py states it in NumPy."""
@@ -112,7 +114,7 @@ class PolarNormalsStats:
 
 
 def polar_normals_stats(pred, pol_normals, xolp, K=None, mask=None, valid=None, classes=DEFAULT_CLASSES, rho_min=0.05,
-                        rho_max=1.0, tilt_min_deg=5.0, aolp_sign=1, maps=False):
+                        rho_max=1.0, tilt_min_deg=5.0, aolp_sign=1, maps=False, ray_frame=False):
     """Records of ``pred`` against the polarisation normals -> ``PolarNormalsStats``.
 
     pred          [N,3,H,W] normals (any length; a channels-last tensor is read in place), or [N,1,H,W] a depth map, whose
@@ -129,7 +131,9 @@ def polar_normals_stats(pred, pol_normals, xolp, K=None, mask=None, valid=None, 
     tilt_min_deg  the smallest tilt of the prediction against the optical axis at which its azimuth is defined; flatter pixels
                   count as ``frontal`` in the azimuth set.  5 degrees is a CONVENTION too, not a measurement
     aolp_sign     +1 or -1: multiplies the y component of every candidate -- the handedness of the sensor's AoLP
-    maps          also return the per-pixel maps (class docstring)"""
+    maps          also return the per-pixel maps (class docstring)
+    ray_frame     score in the frame of each pixel's viewing ray; ``K`` is then needed for [N,3,H,W] normals too.  ``choice``,
+                  ``n_deg`` and ``az_deg`` are those of the ray frame, ``pol_normal`` is returned in camera coordinates"""
     need_cuda("polar_normals_stats", pred, pol_normals, xolp, K, mask, valid)
     if pred.dim() != 4 or pred.shape[1] not in (1, 3):
         raise ValueError(f"pred must be [N,3,H,W] normals or [N,1,H,W] depth, got {tuple(pred.shape)}")
@@ -139,6 +143,10 @@ def polar_normals_stats(pred, pol_normals, xolp, K=None, mask=None, valid=None, 
                          f"{tuple(xolp.shape)}")
     if C == 1 and K is None:
         raise ValueError("a depth map needs the intrinsics K to become normals")
+    if ray_frame and K is None:
+        raise ValueError("ray_frame=True needs the intrinsics K [N,4,4]: the viewing ray of a pixel comes from them")
+    if ray_frame and tuple(K.shape) != (N, 4, 4):
+        raise ValueError(f"K must be [{N},4,4], got {tuple(K.shape)}")
     if aolp_sign not in (1, -1):
         raise ValueError(f"aolp_sign must be +1 or -1, got {aolp_sign!r}")
     if not 0.0 <= float(tilt_min_deg) < 90.0:
@@ -165,18 +173,19 @@ def polar_normals_stats(pred, pol_normals, xolp, K=None, mask=None, valid=None, 
     tilt2 = math.sin(math.radians(float(tilt_min_deg))) ** 2
     with torch.cuda.device(dev):
         st = stream_ptr()
+        Km = K.float().contiguous() if (C == 1 or ray_frame) else None
         if C == 1:
             depth = pred.float().contiguous()
-            Km = K.float().contiguous()
             pred, ld = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev), 4
             check(lib.pd_gt_normals(ptr(depth), ptr(Km), ptr(pred), N, H, W, -_F32_MAX, _F32_MAX, st), "pd_gt_normals")
         else:
             pred, ld = pixel_major(pred)
         ws = torch.empty(int(lib.pd_polar_normals_stats_workspace(N, H, W, nk)), dtype=torch.uint8, device=dev)
-        check(lib.pd_polar_normals_stats(ptr(pred), ld, ptr(pol_normals), ptr(xolp), ldp, ptr(mask), table, nk, ptr(valid),
-                                         ptr(cos_edges(dev)), float(rho_min), float(rho_max), tilt2, int(aolp_sign), ptr(rec_n),
-                                         ptr(rec_a), ptr(az_deg), ptr(n_deg), ptr(choice), ptr(pol_normal), ptr(ws), ws.numel(),
-                                         N, H, W, st), "pd_polar_normals_stats")
+        check(lib.pd_polar_normals_stats_ray(ptr(pred), ld, ptr(Km) if ray_frame else None, int(bool(ray_frame)), ptr(pol_normals),
+                                             ptr(xolp), ldp, ptr(mask), table, nk, ptr(valid), ptr(cos_edges(dev)), float(rho_min),
+                                             float(rho_max), tilt2, int(aolp_sign), ptr(rec_n), ptr(rec_a), ptr(az_deg),
+                                             ptr(n_deg), ptr(choice), ptr(pol_normal), ptr(ws), ws.numel(), N, H, W, st),
+              "pd_polar_normals_stats_ray")
     return out
 
 

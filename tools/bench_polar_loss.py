@@ -11,7 +11,10 @@ half written, rotating buffers, the same timing).  Then, in the same run and on 
 torch ops (fp32, Sobel by F.conv2d, the six cosines, max, the azimuth branch, two weighted means) under autograd, forward +
 backward, and how far its two values are from the kernel's.  ``--step``: the supervised training step of a Trainer at that
 size on synthetic items with and without ``opt.polar_loss``, for the share the term adds.  One JSON line per measurement,
-printed and written to ``--out`` (default: profiles/polar_loss.log).  It needs the GPU: there is no CPU fallback."""
+printed and written to ``--out`` (default: profiles/polar_loss.log).  ``--ray_frame``: after the orthographic pair, in the same
+run and on the same rotating sets, pd_polar_loss_fwd_ray + pd_polar_loss_bwd_ray with ray_frame = 1 are timed the same way
+(``ray_ms`` with its min..max, ``ray_fwd_ms``, ``ray_bwd_ms``, the ratio to the orthographic pair, the two values), and with
+``--step`` the training step with ``opt.polar_ray_frame`` too.  It needs the GPU: there is no CPU fallback."""
 import argparse
 import json
 import math
@@ -118,7 +121,7 @@ def torch_loss(depth, K, pol, xolp, rho_min=RHO_MIN, rho_max=RHO_MAX, tilt2=TILT
     return (wn * torch.where(ok, l_n, zero)).sum() / wn.sum(), (wa * torch.where(ca, l_a, zero)).sum() / wa.sum()
 
 
-def _step_ms(N, H, W, iters, polar_loss):
+def _step_ms(N, H, W, iters, polar_loss, ray_frame=False):
     """One supervised training step (zero_grad .. Adam) of a Trainer on synthetic items, median of ``iters``."""
     import torch
     from manydepth.options import MonodepthOptions
@@ -131,6 +134,8 @@ def _step_ms(N, H, W, iters, polar_loss):
             "--data_path_val", "synthetic", "--num_workers", "0", "--weights_init", "scratch"])
         if polar_loss is not None:
             opt.polar_loss = polar_loss
+        if ray_frame:
+            opt.polar_ray_frame = True
         tr = Trainer(opt)
         tr.set_train()
         ds = tr.train_loader.dataset
@@ -148,7 +153,7 @@ def _step_ms(N, H, W, iters, polar_loss):
         return _median_ms(step, iters)[0]
 
 
-def time_loss(N, H, W, iters=24, sets=None, torch_iters=5, with_step=False):
+def time_loss(N, H, W, iters=24, sets=None, torch_iters=5, with_step=False, ray_frame=False):
     import torch
     from polardepth._lib import lib, check, ptr, stream_ptr
     if not torch.cuda.is_available():
@@ -178,6 +183,21 @@ def time_loss(N, H, W, iters=24, sets=None, torch_iters=5, with_step=False):
         fwd(i)
         bwd(i)
 
+    def fwd_ray(i):
+        depth, K, pol, xolp = data[i % sets]
+        check(lib.pd_polar_loss_fwd_ray(ptr(depth), ptr(K), ptr(pol), ptr(xolp), W, None, RHO_MIN, RHO_MAX, TILT2, 1, 1, 1,
+                                        ptr(state), ptr(record), ptr(values), None, ptr(ws), ws.numel() * 8, N, H, W,
+                                        stream_ptr()), "pd_polar_loss_fwd_ray")
+
+    def bwd_ray(i):
+        depth, K, pol, xolp = data[i % sets]
+        check(lib.pd_polar_loss_bwd_ray(ptr(depth), ptr(K), ptr(pol), ptr(xolp), W, ptr(state), ptr(g), ptr(record), 1, 1, 1,
+                                        ptr(gdepth), N, H, W, stream_ptr()), "pd_polar_loss_bwd_ray")
+
+    def both_ray(i):
+        fwd_ray(i)
+        bwd_ray(i)
+
     for i in range(sets):
         both(i)
     torch.cuda.synchronize()
@@ -185,6 +205,21 @@ def time_loss(N, H, W, iters=24, sets=None, torch_iters=5, with_step=False):
     fwd_ms = _median_ms(fwd, iters)[0]
     fwd(0)
     bwd_ms = _median_ms(lambda i: bwd(0), iters)[0]          # the state of set 0 throughout
+    ray = {}
+    if ray_frame:
+        for i in range(sets):
+            both_ray(i)
+        torch.cuda.synchronize()
+        r_ms, r_min, r_max = _median_ms(both_ray, iters)
+        rf_ms = _median_ms(fwd_ray, iters)[0]
+        fwd_ray(0)
+        rb_ms = _median_ms(lambda i: bwd_ray(0), iters)[0]
+        both_ray(0)
+        torch.cuda.synchronize()
+        rv = values.cpu().numpy().astype(np.float64)
+        ray = {"ray_ms": round(r_ms, 4), "ray_ms_min": round(r_min, 4), "ray_ms_max": round(r_max, 4),
+               "ray_fwd_ms": round(rf_ms, 4), "ray_bwd_ms": round(rb_ms, 4), "ray_over_orthographic": round(r_ms / ms, 3),
+               "ray_L_n": float(rv[0]), "ray_L_a": float(rv[1])}
     both(0)
     torch.cuda.synchronize()
     vals = values.cpu().numpy().astype(np.float64)
@@ -197,6 +232,7 @@ def time_loss(N, H, W, iters=24, sets=None, torch_iters=5, with_step=False):
            "copy_ms": round(copy_ms, 4), "copy_GBps": round(moved / (copy_ms * 1e-3) / 1e9, 1),
            "time_over_copy": round(ms / copy_ms, 2), "L_n": float(vals[0]), "L_a": float(vals[1]),
            "normal_pixels": cnt[0], "azimuth_pixels": cnt[1]}
+    out.update(ray)
 
     def torch_pair(i):
         depth, K, pol, xolp = data[i % sets]
@@ -218,6 +254,9 @@ def time_loss(N, H, W, iters=24, sets=None, torch_iters=5, with_step=False):
         base, with_term = _step_ms(N, H, W, step_iters, None), _step_ms(N, H, W, step_iters, (0.5, 0.5))
         out.update({"supervised_step_ms": round(base, 3), "step_with_term_ms": round(with_term, 3),
                     "added_share_of_step": round((with_term - base) / base, 4)})
+        if ray_frame:
+            with_ray = _step_ms(N, H, W, step_iters, (0.5, 0.5), True)
+            out.update({"step_with_ray_term_ms": round(with_ray, 3), "ray_added_share_of_step": round((with_ray - base) / base, 4)})
     else:
         out["supervised_step_ms"] = out["step_with_term_ms"] = out["added_share_of_step"] = "not measured"
     return out
@@ -229,10 +268,11 @@ if __name__ == "__main__":
     ap.add_argument("--sets", type=int, default=None)
     ap.add_argument("--step", action="store_true", help="also time the supervised training step with and without the term")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "polar_loss.log"), help="the log; '' = print only")
+    ap.add_argument("--ray_frame", action="store_true", help="also time the pair in the per-pixel viewing-ray frame")
     args = ap.parse_args()
     log = open(args.out, "w") if args.out else None
     for N, H, W in SIZES:
-        line = json.dumps(time_loss(N, H, W, args.iters, args.sets, with_step=args.step))
+        line = json.dumps(time_loss(N, H, W, args.iters, args.sets, with_step=args.step, ray_frame=args.ray_frame))
         print(line, flush=True)
         if log:
             log.write(line + "\n")

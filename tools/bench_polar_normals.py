@@ -8,7 +8,10 @@ mask 4; the second record set's workgroups re-read the same pixels and that is N
 copy that moves the SAME number of bytes (half read, half written; rotating buffers, the same timing) and the ratio of the
 two.  Then, in the same run and on the same inputs, the same figures (n, the counters, the four sums and the histogram of
 both sets, for the twelve classes) written with torch ops in fp64, and how far its pooled means are from the kernel's.  One
-JSON line per measurement, printed and written to ``--out`` (default: profiles/polar_normals.log)."""
+JSON line per measurement, printed and written to ``--out`` (default: profiles/polar_normals.log).  ``--ray_frame``: after the
+orthographic call, in the same run and on the same rotating sets, pd_polar_normals_stats_ray with ray_frame = 1 (the
+intrinsics of polardepth.synthetic, 64 more bytes per image) is timed the same way: ``ray_ms`` with its min..max, its ratio to
+the orthographic call, and its pooled means."""
 import argparse
 import json
 import math
@@ -126,7 +129,7 @@ def torch_figures(pred, pol, xolp, mask, classes, edges, rho_min=0.05, rho_max=1
     return out
 
 
-def time_stats(N, H, W, iters=24, sets=None, torch_iters=5):
+def time_stats(N, H, W, iters=24, sets=None, torch_iters=5, ray_frame=False):
     import torch
     from polardepth import normals_eval as ne
     from polardepth import polar_normals_eval as pe
@@ -149,10 +152,32 @@ def time_stats(N, H, W, iters=24, sets=None, torch_iters=5):
                                          TILT2, 1, ptr(rec_n), ptr(rec_a), None, None, None, None, ptr(ws), ws.numel(), N, H, W,
                                          stream_ptr()), "pd_polar_normals_stats")
 
+    Km = torch.eye(4, device="cuda")[None].repeat(N, 1, 1)
+    Km[:, 0, 0] = Km[:, 1, 1] = 0.65 * W
+    Km[:, 0, 2], Km[:, 1, 2] = W / 2, H / 2
+
+    def call_ray(i):
+        pred, pol, xolp, mask = data[i % sets]
+        check(lib.pd_polar_normals_stats_ray(ptr(pred), 4, ptr(Km), 1, ptr(pol), ptr(xolp), W, ptr(mask), table, K, None,
+                                             ptr(edges), 0.05, 1.0, TILT2, 1, ptr(rec_n), ptr(rec_a), None, None, None, None,
+                                             ptr(ws), ws.numel(), N, H, W, stream_ptr()), "pd_polar_normals_stats_ray")
+
     for i in range(sets):
         call(i)
     torch.cuda.synchronize()
     ms, ms_min, ms_max = _median_ms(call, iters)
+    ray = {}
+    if ray_frame:
+        for i in range(sets):
+            call_ray(i)
+        torch.cuda.synchronize()
+        r_ms, r_min, r_max = _median_ms(call_ray, iters)
+        call_ray(0)
+        rn = pe.RecordSet(rec_n, names, pe.NORMAL_COUNTERS, 720).pooled().cpu().numpy()
+        ra = pe.RecordSet(rec_a, names, pe.AZIMUTH_COUNTERS, 360).pooled().cpu().numpy()
+        ray = {"ray_ms": round(r_ms, 4), "ray_ms_min": round(r_min, 4), "ray_ms_max": round(r_max, 4),
+               "ray_over_orthographic": round(r_ms / ms, 3), "ray_normal_mean_deg_all": round(float(rn[0, 0]), 4),
+               "ray_azimuth_mean_deg_all": round(float(ra[0, 0]), 4)}
     call(0)
     st_n, st_a = pe.RecordSet(rec_n, names, pe.NORMAL_COUNTERS, 720), pe.RecordSet(rec_a, names, pe.AZIMUTH_COUNTERS, 360)
     pooled_n, pooled_a = st_n.pooled().cpu().numpy(), st_a.pooled().cpu().numpy()
@@ -164,6 +189,7 @@ def time_stats(N, H, W, iters=24, sets=None, torch_iters=5):
            "time_over_copy": round(ms / copy_ms, 2),
            "normal_mean_deg_all": round(float(pooled_n[0, 0]), 4), "azimuth_mean_deg_all": round(float(pooled_a[0, 0]), 4),
            "normal_pixels_all": int(pooled_n[0, 6]), "azimuth_pixels_all": int(pooled_a[0, 6])}
+    out.update(ray)
 
     lohi = [(1, 0) if r is None else r for _, r in ne.DEFAULT_CLASSES]
     figures = lambda i: torch_figures(*data[i % sets], lohi, edges)
@@ -185,10 +211,11 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=24)
     ap.add_argument("--sets", type=int, default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "polar_normals.log"), help="the log; '' = print only")
+    ap.add_argument("--ray_frame", action="store_true", help="also time the call in the per-pixel viewing-ray frame")
     args = ap.parse_args()
     log = open(args.out, "w") if args.out else None
     for N, H, W in SIZES:
-        line = json.dumps(time_stats(N, H, W, args.iters, args.sets))
+        line = json.dumps(time_stats(N, H, W, args.iters, args.sets, ray_frame=args.ray_frame))
         print(line, flush=True)
         if log:
             log.write(line + "\n")

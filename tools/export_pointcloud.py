@@ -11,7 +11,8 @@ predicted depth maps agree with this one at MVSNet's thresholds under the loader
 ``--normals depth`` adds the properties nx ny nz to ``pred.ply``: the normals of the depth map that is exported
 (pd_gt_normals).  ``--normals polar`` writes the polarisation normal instead wherever the measurement gives one: of the three
 physical candidates of K1 and their pi flips, the one closest to the depth normal (``pol_normal`` where ``choice != 0`` of
-``polardepth.polar_normals_eval.polar_normals_stats``), the depth normal elsewhere.  ``gt.ply`` is unchanged."""
+``polardepth.polar_normals_eval.polar_normals_stats``), the depth normal elsewhere.  ``--ray_frame`` makes that choice in the
+frame of each pixel's viewing ray; the normal written is still a camera-frame one.  ``gt.ply`` is unchanged."""
 import argparse
 import os
 import sys
@@ -20,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarized-images_amd"))
 
 
-def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None, normals=None, aolp_sign=None):
+def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None, normals=None, aolp_sign=None,
+           ray_frame=None):
     import torch
     from torch.utils.data.dataloader import default_collate
     from manydepth.evaluation import Evaluation
@@ -28,7 +30,7 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True, con
     if normals not in (None, "polar", "depth"):
         raise ValueError(f'--normals takes "polar" or "depth", got {normals!r}')
     ev = Evaluation(load_weights_folder=weights, data_path=data_path, height=height, width=width, batch_size=1,
-                    aolp_sign=aolp_sign)
+                    aolp_sign=aolp_sign, polar_ray_frame=ray_frame)
     ev.load_mono_model()
     ds = ev.test_loader.dataset
     if not 0 <= index < len(ds):
@@ -72,8 +74,8 @@ def pixel_normals(ev, inputs, depth, kind):
     if kind == "polar":
         pol = pdpolar.polar_inputs(inputs, (ev.height, ev.width), ("xolp", "normals"), ev.pol_angles, dofp=ev.pol_dofp,
                                    cdofp=ev.pol_cdofp, calibration=ev.pol_calibration)
-        st = pe.polar_normals_stats(dn.permute(0, 3, 1, 2)[:, :3], pol, inputs["xolp", 0, 0], classes=(("all", None),),
-                                    aolp_sign=ev.aolp_sign, maps=True)
+        st = pe.polar_normals_stats(dn.permute(0, 3, 1, 2)[:, :3], pol, inputs["xolp", 0, 0], K=K, classes=(("all", None),),
+                                    aolp_sign=ev.aolp_sign, maps=True, ray_frame=ev.polar_ray_frame)
         out = torch.where((st.choice[0] != 0)[..., None], st.pol_normal[0, ..., :3], out)
     return out.reshape(H * W, 3).cpu()
 
@@ -113,7 +115,9 @@ if __name__ == "__main__":
     ap.add_argument("--normals", choices=("polar", "depth"), default=None,
                     help="add nx ny nz to pred.ply: the depth map's normals, or the polarisation normal where there is one")
     ap.add_argument("--aolp_sign", type=int, choices=(1, -1), default=None, help="the AoLP handedness for --normals polar")
+    ap.add_argument("--ray_frame", action="store_true", default=None,
+                    help="--normals polar: choose the candidate in the frame of each pixel's viewing ray")
     args = ap.parse_args()
     for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip,
-                          args.consistent, args.normals, args.aolp_sign).items():
+                          args.consistent, args.normals, args.aolp_sign, args.ray_frame).items():
         print(f"{path}: {n} points")

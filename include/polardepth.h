@@ -485,7 +485,9 @@ int pd_step_set_hyper(void* step_state, float lr, float grad_scale, void* stream
 int pd_loss_rows(long n);
 int pd_disp_to_depth(const void* disp, void* depth, void* updisp, int N, int hs, int ws, int H, int W,
                      float min_depth, float max_depth, void* stream);
-/* generic != 0: the any-ratio kernel instead of the one specialised for zooms 1 / 2 / 4 / 8 (tests compare the two) */
+/* generic != 0: the any-ratio kernel instead of the one specialised for zooms 1 / 2 / 4 / 8 (tests compare the two); it
+ * alone also takes a full size that is no integer multiple of the scale size (H >= hs, W >= ws), as pd_unc_loss_bwd's
+ * callers need */
 int pd_up_gather_bwd(const void* gup, void* gdisp, int N, int hs, int ws, int H, int W, int accumulate, int generic,
                      void* stream);
 /* gt_normals (optional, NULL = recompute per call): [N,H,W,4] floats written by pd_gt_normals -- the unit normal of the
@@ -1645,6 +1647,88 @@ int pd_disphead_bwd_weight(const void* dy, const void* y, const void* x, void* d
 int pd_disphead_bwd(const void* dy, const void* y, const void* x, const void* w, const void* add, int elu, void* dx,
                     void* dw, void* dbias, void* workspace, size_t ws_bytes, int N, int H, int W, int C, int accumulate,
                     void* stream);
+
+/* ---- Depth uncertainty (csrc/unc_loss.hip, csrc/unc_stats.hip): the decoder's sigmoid uncertainty heads
+ * (depth_decoder.py:46-73, "unc_conv") trained and scored as the scale of a Laplace error model of the predicted depth.
+ * tests/unc_loss_ref.py and tests/unc_stats_ref.py state the definitions in NumPy.
+ *
+ * THE SCALE of a pixel.  u in [0, 1] is the head's output; with (b_lo, b_hi) in metres, 0 < b_lo < b_hi < inf,
+ *     log b = fma((double)u, log(b_hi / b_lo), log b_lo)        in fp64, the two logarithms taken on the host;
+ *     b = exp(log b)                                             in metres;    log 2b = log b + M_LN2.
+ * (b_lo, b_hi) is a convention of the caller (the Python layer's default is 0.5 mm .. 0.5 m), not a measurement.
+ *
+ * THE LOSS (pd_unc_loss_fwd / _bwd).  depth fp32 [N,H,W] contiguous (what pd_disp_to_depth wrote); gt fp32 [N,H,W] with
+ * row pitch ldg >= W elements (image pitch H * ldg); unc fp32 [N,hs,ws] contiguous with hs <= H, ws <= W, sampled at every
+ * pixel of the frame by the align_corners=False bilinear rule of pd_disp_to_depth in fp32 (csrc/up_index.hpp), any ratio;
+ * valid uint8 [N,H,W] or NULL.
+ *     m   = min_depth <= gt <= max_depth (inclusive, NaN fails: the mask of the supervised term) and valid != 0 and the
+ *           sampled u finite (a non-finite u takes the pixel out, as it makes a pixel `bad` in the evaluator)
+ *     L   = sum m (|gt - depth| / b + log 2b) / sum m,   every term in fp64 from the fp32 inputs, the difference exact;
+ *           0 where sum m = 0.  A non-finite depth UNDER the mask makes the value non-finite, as in the supervised term;
+ *           outside the mask nothing is read into a sum.
+ *   sums    double[PD_ULOSS_SUMS = 4], 8-byte aligned: sum |gt - depth| / b, sum log 2b, sum m, sum b -- added per lane over
+ *           its grid-stride items, then lane -> wave -> workgroup -> one finalize workgroup in a fixed order: bit-reproducible.
+ *   value   fp32 [1] = (float)((sums[0] + sums[1]) / sums[2]), rounded once
+ *   maps    NULL or fp32 [N,H,W,2] = (the pixel's term, b), NaN where m = 0; 8-byte aligned
+ *   workspace: >= pd_unc_loss_rows(N, H, W) * 4 * 8 bytes, 16-byte aligned; pd_unc_loss_rows is monotone and never 0.
+ * pd_unc_loss_bwd: with c = gvalue[0] / sums[2] (0 where sums[2] = 0) and sums as the forward call left them,
+ *   gdepth  fp32 [N,H,W] = c sign(depth - gt) / b under the mask (0 at depth == gt), 0 elsewhere; NULL = the detached mode:
+ *           the gradient is neither formed nor written
+ *   gup     fp32 [N,H,W] = c (1 - |gt - depth| / b) log(b_hi / b_lo) under the mask, 0 elsewhere: the gradient with respect
+ *           to the SAMPLED u; pd_up_gather_bwd(gup, gunc, N, hs, ws, H, W, 0, generic, stream) folds it to [N,hs,ws]
+ *           (generic != 0 where H / hs or W / ws is no integer).
+ * Two launches forward, one backward; where W and ldg are multiples of 4 and the pointers 16-byte aligned a work item is
+ * four pixels with 16-byte accesses.  No atomics, no allocation, no synchronisation, no environment variable: capturable.
+ * N == 0 returns PD_OK after the checks.  Refusals (PD_EINVAL, before the device is touched): null pointers, bad shapes,
+ * ldg < W, !(0 < min_depth < max_depth), !(0 < b_lo < b_hi < inf), misaligned pointers, a too-small workspace (naming the
+ * needed size), a frame beyond 2^30 pixels.
+ *
+ * THE EVALUATOR (pd_unc_stats): calibration and sparsification per pixel class in one read of the batch, the sixth evaluator
+ * on csrc/class_records.hpp.  gt, pred, unc fp32 [N,H,W] (unc at full resolution); mask, classes, edges, min_depth as
+ * pd_depth_stats takes them; max_depth finite and <= PD_USTAT_MAX_DEPTH.
+ * PIXEL SET  S(n,k) and p0: those of pd_depth_stats (strict gate, finite pred), and additionally 0 <= u <= 1 (a NaN u fails).
+ *            A pixel that passes the gate and the class but not the rest adds 1 to `bad` and takes part in nothing else.
+ * Per pixel of S(n,k), in fp64:  e = |gt - p0| (exact);  b, log 2b as above;  e_um = (uint64) rint(e * 1e6), the error in
+ *            whole micrometres (<= 1e9);  ub = min(511, (int)(u * 512.f)) (exact in fp32);  eb = the 0.5 mm bin of
+ *            pd_depth_stats, #{ j >= 1 : edges[j-1] <= e }, by the same binary search.
+ * stats: [N][K] records of PD_USTAT_RECORD_BYTES, written whole by every call; byte offsets:
+ *      0  int64   n          |S(n,k)| (the sum of the bins)
+ *      8  int64   bad
+ *     16  int64   cover50    e <= b * M_LN2    (the central 50 % of a Laplace density of scale b), decided in fp64
+ *     24  int64   cover90    e <= b * M_LN10   (the central 90 %)
+ *     32  double  sum_nll    sum (e / b + log 2b)
+ *     40  double  sum_b      sum b
+ *     48  double  sum_e      sum e
+ *     56  8 bytes of zero
+ *     64  uint32  hist[512]  the count per ub
+ * tables: uint64 [N][K][PD_USTAT_TABLE_ROWS = 3][512], written whole by every call: row 0 = sum e_um by ub, row 1 = the
+ * count by eb (= pd_depth_stats' hist), row 2 = sum e_um by eb.  From hist and row 0 the host draws the sparsification curve
+ * of the stated uncertainty, from rows 1 and 2 the oracle's (polardepth/uncertainty_eval.py).  Two limits of the binning:
+ * pixels that share a 1/512 step of u are tied, and the oracle's last error bin (>= 255.5 mm) is open-ended.
+ * The integer fields and the tables are integer sums: exact, no order can change them.  The three fp64 sums are
+ * bit-reproducible (the scheme of pd_normals_stats).  A class's histogram and tables take 14 KiB of LDS, so a workgroup serves
+ * four classes at a time and goes over its pixels once per four classes.  Four launches per 2^20 images; capturable.
+ * workspace: >= pd_unc_stats_workspace(N, H, W, K) bytes (never 0, a multiple of 16, monotone), 16-byte aligned.
+ * Refusals: those of pd_depth_stats, max_depth above PD_USTAT_MAX_DEPTH or not finite, !(0 < b_lo < b_hi < inf), stats /
+ * tables / workspace not 16-byte aligned. */
+#define PD_ULOSS_SUMS          4
+#define PD_USTAT_BINS          512
+#define PD_USTAT_COUNTERS      3        /* bad, cover50, cover90 */
+#define PD_USTAT_SUMS          3        /* nll, b, e */
+#define PD_USTAT_TABLE_ROWS    3
+#define PD_USTAT_RECORD_BYTES  2112     /* 64 + 4 * 512 */
+#define PD_USTAT_MAX_DEPTH     1000
+int pd_unc_loss_rows(int N, int H, int W);
+int pd_unc_loss_fwd(const void* depth, const void* gt, long ldg, const void* unc, int hs, int ws, const void* valid,
+                    float min_depth, float max_depth, double b_lo, double b_hi, void* sums, void* value, void* maps,
+                    void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+int pd_unc_loss_bwd(const void* depth, const void* gt, long ldg, const void* unc, int hs, int ws, const void* valid,
+                    float min_depth, float max_depth, double b_lo, double b_hi, const void* gvalue, const void* sums,
+                    void* gdepth, void* gup, int N, int H, int W, void* stream);
+size_t pd_unc_stats_workspace(int N, int H, int W, int K);
+int pd_unc_stats(const void* gt, const void* pred, const void* unc, const void* mask, const int* classes, int K,
+                 const void* edges, double b_lo, double b_hi, void* stats, void* tables, void* workspace, size_t ws_bytes,
+                 int N, int H, int W, float min_depth, float max_depth, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@
 #include "pd_common.h"
 #include "depth_normals.hpp"
 #include "wave_ops.hpp"
+#include "up_index.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -40,14 +41,7 @@ __device__ __forceinline__ void block_sum(float (&v)[K], float* smem /* [4][K] *
         for (int k = 0; k < K; ++k) v[k] = smem[k] + smem[K + k] + smem[2 * K + k] + smem[3 * K + k];
 }
 
-// torch upsample_bilinear2d source index (align_corners=False)
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
-    const float s = fmaxf(scale * (dst + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1);
-    l1 = s - i0;
-}
+using pd_up::src_index;   // torch upsample_bilinear2d source index (align_corners=False), shared with unc_loss.hip
 
 // ------------------------------------------------------------------ disp -> full-res depth
 __device__ __forceinline__ void disp_to_depth_body(const float* __restrict__ disp, float* __restrict__ depth,
@@ -82,14 +76,15 @@ __global__ __launch_bounds__(LT) void up_gather_bwd_kernel(const float* __restri
                                                            int N, int hs, int ws, int H, int W, int accumulate) {
     const long total = (long)N * hs * ws;
     const float sh = (float)hs / H, sw = (float)ws / W;
-    const int fh = H / hs, fw = W / ws;   // integer zoom factors (checked on the host)
     for (long i = blockIdx.x * (long)LT + threadIdx.x; i < total; i += (long)gridDim.x * LT) {
         int xs, ys;
         const long t = divmod(i, ws, xs);
         const long n = divmod(t, hs, ys);
         float acc = 0.f;
-        const int ylo = max(0, (ys - 1) * fh), yhi = min(H - 1, (ys + 2) * fh - 1);
-        const int xlo = max(0, (xs - 1) * fw), xhi = min(W - 1, (xs + 2) * fw - 1);
+        // the footprint of (ys, xs) lies inside [(ys - 1) H / hs, (ys + 2) H / hs]: for any ratio H / hs >= 1, not only an
+        // integer one; a pixel of that range outside the footprint has weight 0 and adds nothing
+        const int ylo = max(0, (int)((long)(ys - 1) * H / hs)), yhi = min(H - 1, (int)(((long)(ys + 2) * H + hs - 1) / hs));
+        const int xlo = max(0, (int)((long)(xs - 1) * W / ws)), xhi = min(W - 1, (int)(((long)(xs + 2) * W + ws - 1) / ws));
         for (int y = ylo; y <= yhi; ++y) {
             int y0, y1; float ly1;
             src_index(y, sh, hs, y0, y1, ly1);
@@ -833,7 +828,8 @@ extern "C" int pd_disp_to_depth(const void* disp, void* depth, void* updisp, int
 extern "C" int pd_up_gather_bwd(const void* gup, void* gdisp, int N, int hs, int ws, int H, int W, int accumulate,
                                 int generic, void* stream) {
     PD_REQUIRE(gup && gdisp && N >= 0 && hs > 0 && ws > 0, "pd_up_gather_bwd: bad arguments");
-    PD_REQUIRE(H % hs == 0 && W % ws == 0, "pd_up_gather_bwd: full size must be an integer multiple of the scale size");
+    PD_REQUIRE(generic ? (H >= hs && W >= ws) : (H % hs == 0 && W % ws == 0),
+               "pd_up_gather_bwd: full size must be an integer multiple of the scale size (generic != 0: at least the scale size)");
     if (N == 0) return PD_OK;
     const int f = generic ? 0 : H / hs;                                // generic != 0: the any-ratio kernel (tests compare the two)
     const unsigned grid = pd::flat_grid((long)N * hs * ws);

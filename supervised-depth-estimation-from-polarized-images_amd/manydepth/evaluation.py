@@ -20,6 +20,7 @@ from polardepth import pointcloud
 from polardepth import pose_eval
 from polardepth import consistency_eval
 from polardepth import polar_normals_eval
+from polardepth import uncertainty_eval
 from polardepth import matching as pdmatching
 from polardepth._lib import lib, check, ptr, stream_ptr
 
@@ -33,7 +34,7 @@ class Evaluation:
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
                  pol_calibration=None, normals_decoder=None, pose_network=None, multi_frame=False, matching_ids=(0, -1),
                  multi_poses="files", num_depth_bins=96, depth_binning="linear", aolp_sign=None,
-                 polar_ray_frame=None):
+                 polar_ray_frame=None, uncertainty=None, uncertainty_range=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -70,7 +71,20 @@ class Evaluation:
         ``aolp_sign``: +1 or -1, the handedness of the sensor's AoLP as ``test_polar_normals`` takes it (or
         $PD_POL_AOLP_SIGN); None = +1.  Nothing else reads it.  ``polar_ray_frame``: ``test_polar_normals`` scores in the frame
         of each pixel's viewing ray instead of the orthographic convention (``polar_normals_stats(ray_frame=True)``), for all
-        its sources; None reads $PD_POLAR_RAY_FRAME == "1".  Nothing else reads it."""
+        its sources; None reads $PD_POLAR_RAY_FRAME == "1".  Nothing else reads it.
+
+        ``uncertainty``: build the decoder with its uncertainty heads (``predict_all``'s "uncertainty", ``test_uncertainty``); None
+        reads $PD_UNCERTAINTY == "1".  The weights folder must then hold the heads (``load_mono_model`` says so otherwise).
+        ``uncertainty_range``: the (b_lo, b_hi) in metres, or "lo,hi", that turns the heads' output into a Laplace scale; None
+        looks at a trainer_state.pth in ``load_weights_folder`` that carries the range the heads were trained with and ends at
+        ``ops.UNCERTAINTY_RANGE``.  A convention, not a measurement.  Without ``uncertainty`` the object is what it was."""
+        self.uncertainty = (os.environ.get("PD_UNCERTAINTY") == "1") if uncertainty is None else bool(uncertainty)
+        if isinstance(uncertainty_range, str):
+            uncertainty_range = [float(x) for x in uncertainty_range.split(",")]
+        if uncertainty_range is not None and not self.uncertainty:
+            raise ValueError("uncertainty_range is an option of the uncertainty heads: it needs Evaluation(uncertainty=True) "
+                             "(or PD_UNCERTAINTY=1)")
+        self.uncertainty_range = None if uncertainty_range is None else ops.uncertainty_range(uncertainty_range)
         self.polar_ray_frame = (os.environ.get("PD_POLAR_RAY_FRAME") == "1") if polar_ray_frame is None else bool(polar_ray_frame)
         aolp_sign = aolp_sign if aolp_sign is not None else os.environ.get("PD_POL_AOLP_SIGN")
         self.aolp_sign = 1 if aolp_sign is None else int(aolp_sign)
@@ -111,6 +125,11 @@ class Evaluation:
         state_path = os.path.join(load_weights_folder, "trainer_state.pth") if load_weights_folder is not None else None
         if self.xolp_norm is None and state_path is not None and os.path.isfile(state_path):
             self.xolp_norm = pdpolar.parse_xolp_norm(torch.load(state_path, map_location="cpu").get("xolp_norm"))
+        if self.uncertainty and self.uncertainty_range is None:
+            stored = None
+            if state_path is not None and os.path.isfile(state_path):
+                stored = torch.load(state_path, map_location="cpu").get("uncertainty_range")
+            self.uncertainty_range = ops.uncertainty_range(stored)
         self.device = torch.device("cuda")
         self.models = {"rgb_encoder": networks.ShallowResnetEncoder(18, False)}
         if augment_normals:
@@ -120,7 +139,11 @@ class Evaluation:
         self.models["joint_encoder"] = networks.JointEncoder(
             0.0, augment_normals, augment_xolp,
             attention=(os.environ.get("PD_JOINT_ATTENTION") == "1") if joint_attention is None else joint_attention)
-        self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.scales)
+        if self.uncertainty:
+            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.scales,
+                                                              uncertainty=True)
+        else:
+            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.scales)
         if (os.environ.get("PD_NORMALS_DECODER") == "1") if normals_decoder is None else normals_decoder:
             if not augment_normals:
                 raise ValueError("the separate normals decoder sits behind the normals encoder: it needs augment_normals")
@@ -189,6 +212,13 @@ class Evaluation:
                         raise ValueError(f"encoder.pth was trained at {k} {int(extra[k])}, this Evaluation runs at {own}")
                 if extra.get("min_depth_bin") is not None and extra.get("max_depth_bin") is not None:
                     m.compute_depth_bins(float(extra["min_depth_bin"]), float(extra["max_depth_bin"]))
+            if n == "mono_depth" and self.uncertainty:
+                ids = {id(p) for key, conv in m.convs.items() if key[0] == "unc_conv" for p in conv.parameters()}
+                heads = [k for k, p in m.named_parameters() if id(p) in ids]      # by the decoder's keys, not by index
+                missing = [k for k in heads if k not in sd]
+                if missing:
+                    raise ValueError(f"{path} holds no unc_conv weights ({missing[0]} and {len(missing) - 1} more are missing): "
+                                     "Evaluation(uncertainty=True) needs a checkpoint trained with opt.uncertainty_loss")
             m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()})
 
     @torch.no_grad()
@@ -198,7 +228,9 @@ class Evaluation:
     @torch.no_grad()
     def predict_all(self, inputs):
         """{"depth": what ``predict`` returns, "normals_pred": the NormalsDecoder's [N,3,H,W] output} -- the latter only with
-        the decoder, wired as Trainer._forward_models wires it (on the normals encoder's features)."""
+        the decoder, wired as Trainer._forward_models wires it (on the normals encoder's features).  With
+        ``Evaluation(uncertainty=True)`` also "uncertainty": the Laplace scale b in metres [N,1,H,W] the scale-0 head states
+        (``uncertainty_eval.scale_of`` with ``uncertainty_range``), and "uncertainty_u", the head's own output in [0, 1]."""
         return self._forward(inputs, True)
 
     def _forward(self, inputs, with_normals_pred):
@@ -212,12 +244,16 @@ class Evaluation:
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None
         nf = self.models["normals_encoder"](inputs["xolp", 0, 0].float(), normals=normals) if self.augment_normals else None
         feats = list(feats) + self.models["joint_encoder"](feats[-1], xf, nf)
-        disp = self.models["mono_depth"](feats)[("disp", 0)].contiguous()
+        dec = self.models["mono_depth"](feats)
+        disp = dec[("disp", 0)].contiguous()
         N = disp.shape[0]
         depth = torch.empty((N, 1, self.height, self.width), device=disp.device)
         check(lib.pd_disp_to_depth(ptr(disp), ptr(depth), None, N, disp.shape[2], disp.shape[3], self.height, self.width,
                                    self.min_depth, self.max_depth, stream_ptr()), "pd_disp_to_depth")
         out = {"depth": depth.clamp(self.min_depth, self.max_depth)}
+        if with_normals_pred and self.uncertainty:            # scale 0 is already H x W
+            out["uncertainty_u"] = dec[("uncertainty", 0)].contiguous()
+            out["uncertainty"] = uncertainty_eval.scale_of(out["uncertainty_u"], self.uncertainty_range)
         if with_normals_pred and "normals_decoder" in self.models:
             out["normals_pred"] = self.models["normals_decoder"](nf)
         return out
@@ -440,6 +476,41 @@ class Evaluation:
                 print(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
                 print(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
         return results
+
+    @torch.no_grad()
+    def test_uncertainty(self):
+        """Does the network know where its depth is wrong (polardepth.uncertainty_eval; the reference builds the heads and
+        stops there)?  Per class -- the whole frame, all objects, each material -- and per batch ONE pd_unc_stats call scores
+        the scale-0 uncertainty head, read as the Laplace scale b of ``uncertainty_range``, against the error of ``predict``:
+        n and bad, the mean absolute error and the mean stated scale in millimetres, the mean negative log-likelihood, the
+        shares of pixels inside the central 50 % and 90 % of their stated density (0.5 and 0.9 when calibrated), and the
+        sparsification figures AUSE and AURG in millimetres and relative to the mean error.  Prints, and returns {class:
+        {"per_image": [10], "pooled": [10], "bad": int}} (``uncertainty_eval.METRIC_NAMES``): "per_image" is the mean over
+        images of the per-image figures (images without a pixel of the class do not count), "pooled" takes all pixels of all
+        images as one set, its tables added exactly.  The records stay on the device until the loop is over."""
+        if not self.uncertainty:
+            raise ValueError("test_uncertainty needs Evaluation(uncertainty=True) (or PD_UNCERTAINTY=1)")
+        calls = []
+        for inputs in self.test_loader:
+            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+            out = self._forward(inputs, True)
+            calls.append(uncertainty_eval.uncertainty_stats(out["depth"], inputs["depth_gt"], out["uncertainty_u"],
+                                                            mask=inputs[("mask", 0, 0)], b_range=self.uncertainty_range,
+                                                            min_depth=self.min_depth, max_depth=self.max_depth))
+        if not calls:
+            return {}
+        per = np.concatenate([st.metrics() for st in calls], 0)              # [images, K, 10]
+        total = calls[0]
+        for st in calls[1:]:
+            total += st
+        valid = per[..., 9] > 0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            per_image = np.where(valid[..., None], per, 0.0).sum(0) / valid.sum(0)[:, None]
+        pooled, bad = total.pooled(), total.pooled_bad().cpu().numpy()
+        lo, hi = self.uncertainty_range
+        print(uncertainty_eval.format_report(total.names, per_image, pooled, bad,
+                                             title=f"uncertainty (b from {lo * 1e3:g} to {hi * 1e3:g} mm)"))
+        return {name: {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k])} for k, name in enumerate(total.names)}
 
     @torch.no_grad()
     def predict_poses(self, inputs):

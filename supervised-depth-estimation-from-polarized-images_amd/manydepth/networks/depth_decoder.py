@@ -35,6 +35,9 @@ class DepthDecoder(nn.Module):
         for s in self.scales:
             self.convs[("dispconv", s)] = Conv3x3(self.num_ch_dec[s], self.num_output_channels)
         self.uncertainty = bool(uncertainty)
+        # True: the uncertainty heads read the features without a tape, so that nothing they are trained with reaches the
+        # rest of the network (Trainer's opt.uncertainty_detach: heads on top of a finished checkpoint)
+        self.uncertainty_detach = False
         if self.uncertainty:            # depth_decoder.py:46-50: two 5x5 heads per scale, ModuleList entries 14.. in this order
             for s in self.scales:
                 self.convs[("unc_conv", s)] = Conv5x5(self.num_ch_dec[s], self.num_output_channels)
@@ -60,8 +63,9 @@ class DepthDecoder(nn.Module):
             if i in self.scales:
                 self.outputs[("disp", i)] = self.convs[("dispconv", i)](x, act=ops.ACT_SIGMOID, head_mail=m1)
                 if self.uncertainty:     # depth_decoder.py:71-73: sigmoid(Conv5x5(x)), the sigmoid in the conv epilogue
-                    self.outputs[("uncertainty", i)] = self.convs[("unc_conv", i)](x, act=ops.ACT_SIGMOID)
-                    self.outputs[("uncertainty_color", i)] = self.convs[("unc_conv_color", i)](x, act=ops.ACT_SIGMOID)
+                    xu = x.detach() if self.uncertainty_detach else x
+                    self.outputs[("uncertainty", i)] = self.convs[("unc_conv", i)](xu, act=ops.ACT_SIGMOID)
+                    self.outputs[("uncertainty_color", i)] = self.convs[("unc_conv_color", i)](xu, act=ops.ACT_SIGMOID)
             pend = m1
         if fuse and len(self.outputs) > 1:
             # every head an ancestor of every output: a backward pass from a subset of the scales still runs all heads,

@@ -68,6 +68,17 @@ def options_from_environment(opts, env=os.environ):
         opts.pol_aolp_sign = int(env["PD_POL_AOLP_SIGN"])
     if env.get("PD_POLAR_RAY_FRAME"):
         opts.polar_ray_frame = env["PD_POLAR_RAY_FRAME"] == "1"
+    # PD_UNCERTAINTY_LOSS=w: build the decoder's uncertainty heads and train them as the scale of a Laplace error model of the
+    # depth, with weight w (opt.uncertainty_loss; PD_STEP_GRAPH=1, PD_BF16=1 and torch.distributed are refused with it).
+    # PD_UNCERTAINTY_RANGE="lo,hi": the scale at u = 0 and u = 1 in metres (opt.uncertainty_range; default 0.0005,0.5: a
+    # convention).  PD_UNCERTAINTY_DETACH=1: the term trains the heads only, on top of the network as it is
+    # (opt.uncertainty_detach)
+    if env.get("PD_UNCERTAINTY_LOSS"):
+        opts.uncertainty_loss = float(env["PD_UNCERTAINTY_LOSS"])
+    if env.get("PD_UNCERTAINTY_RANGE"):
+        opts.uncertainty_range = [float(x) for x in env["PD_UNCERTAINTY_RANGE"].split(",")]
+    if env.get("PD_UNCERTAINTY_DETACH"):
+        opts.uncertainty_detach = env["PD_UNCERTAINTY_DETACH"] == "1"
     return opts
 
 

@@ -41,7 +41,10 @@ the present ones, as in the photometric term.  ``opt.polar_loss = (w_n, w_a)`` (
 adds the polarimetric normals loss: per scale the normals of the predicted depth map against the candidates K1 derives from
 DoLP / AoLP, on the decisions of ``Evaluation.test_polar_normals`` (``polar_normal_loss/{s}``, ``polar_azimuth_loss/{s}``;
 ``_polar_loss_option``; ``opt.polar_ray_frame`` / ``PD_POLAR_RAY_FRAME=1``: in the frame of each pixel's viewing ray); without it
-nothing changes in a bit, and ``PD_STEP_GRAPH=1`` is refused with it.  The cost-volume student's building
+nothing changes in a bit, and ``PD_STEP_GRAPH=1`` is refused with it.  ``opt.uncertainty_loss = w`` (``PD_UNCERTAINTY_LOSS``; any
+of the modes above) builds the decoder with its uncertainty heads and trains the ``unc_conv`` ones as the scale of a Laplace error
+model of the depth (``uncertainty_loss/{s}``; ``_uncertainty_option``; ``opt.uncertainty_range``, ``opt.uncertainty_detach``);
+``PD_STEP_GRAPH=1``, ``opt.bf16`` and ``torch.distributed`` are refused with it.  The cost-volume student's building
 blocks exist -- the plane sweep (``polardepth.ops.cost_volume``) and ``networks.ResnetEncoderMatching`` -- but its training
 branch (``--train_student``: matching augmentation, consistency loss, adaptive-bin tracker, second decoder) does not: it,
 ``--v1_multiscale``, DPT and stereo branches raise NotImplementedError.
@@ -157,6 +160,44 @@ def _polar_loss_option(opt):
     return w, where, sign
 
 
+def _uncertainty_option(opt):
+    """The depth-uncertainty term (polardepth.functional.uncertainty_loss): ``opt.uncertainty_loss = w``, its weight; None /
+    absent = the term is off, the decoder is built without its uncertainty heads and nothing changes in a bit.
+    ``opt.uncertainty_range = (b_lo, b_hi)`` or "lo,hi": the Laplace scale in metres at u = 0 and u = 1 (default
+    ``ops.UNCERTAINTY_RANGE``; a convention, not a measurement).  ``opt.uncertainty_detach``: the term trains the heads only --
+    no gradient reaches the depth maps or the decoder's features.  Not reference CLI flags: manydepth/train.py maps
+    PD_UNCERTAINTY_LOSS / PD_UNCERTAINTY_RANGE / PD_UNCERTAINTY_DETACH onto them.  Returns (w or None, range, detach); with
+    the term on, the three are written back in a form that travels in opt.json."""
+    w = getattr(opt, "uncertainty_loss", None)
+    rng = getattr(opt, "uncertainty_range", None)
+    detach = getattr(opt, "uncertainty_detach", None)
+    if detach is not None and not (isinstance(detach, (bool, int, np.integer)) and int(detach) in (0, 1)):
+        raise ValueError(f"opt.uncertainty_detach must be True or False, got {detach!r}")
+    if w is None:
+        if rng is not None or detach:
+            raise ValueError("opt.uncertainty_range / opt.uncertainty_detach are set without opt.uncertainty_loss: they are "
+                             "options of the uncertainty term, set opt.uncertainty_loss = w too")
+        return None, None, False
+    try:
+        w = float(w)
+    except (TypeError, ValueError):
+        raise ValueError(f"opt.uncertainty_loss must be a finite weight >= 0, got {getattr(opt, 'uncertainty_loss')!r}")
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError(f"opt.uncertainty_loss must be a finite weight >= 0, got {getattr(opt, 'uncertainty_loss')!r}")
+    if isinstance(rng, str):
+        rng = rng.split(",")
+    if rng is not None:
+        try:
+            rng = [float(x) for x in rng]
+        except (TypeError, ValueError):
+            rng = ()
+        if len(rng) != 2:
+            raise ValueError(f"opt.uncertainty_range must be (b_lo, b_hi), got {getattr(opt, 'uncertainty_range')!r}")
+    rng = ops.uncertainty_range(rng)              # 0 < b_lo < b_hi < inf, or ValueError
+    opt.uncertainty_loss, opt.uncertainty_range, opt.uncertainty_detach = w, list(rng), bool(detach)
+    return w, rng, bool(detach)
+
+
 class _Bf16Step:
     """The flag words of this Trainer's training forward passes in bf16 mode, restored on exit: the precision is recorded by
     every autograd node when its forward runs, so the backward (and a captured replay) follows it without a global switch."""
@@ -230,6 +271,20 @@ class Trainer:
         if self.polar_loss is not None and (os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False))):
             raise NotImplementedError("PD_STEP_GRAPH=1 with opt.polar_loss: the polarimetric term is not captured yet; "
                                       "run it without the step graph")
+        # the depth-uncertainty term: the decoder's uncertainty heads as the scale of a Laplace error model of the depth
+        # (polardepth.functional.uncertainty_loss, csrc/unc_loss.hip); it needs the ground-truth depth every mode here has
+        self._uncertainty_range_given = getattr(self.opt, "uncertainty_range", None) is not None
+        self.uncertainty_loss, self.uncertainty_range, self.uncertainty_detach = _uncertainty_option(self.opt)
+        if self.uncertainty_loss is not None:
+            if os.environ.get("PD_STEP_GRAPH") == "1" or bool(getattr(self.opt, "step_graph", False)):
+                raise NotImplementedError("PD_STEP_GRAPH=1 with opt.uncertainty_loss: the uncertainty term is not captured "
+                                          "yet; run it without the step graph")
+            if _bf16_variant(self.opt):
+                raise NotImplementedError("opt.bf16 with opt.uncertainty_loss: the uncertainty heads have not been verified in "
+                                          "bf16")
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                raise NotImplementedError("torch.distributed with opt.uncertainty_loss: the gradient reducer's bucket order "
+                                          "has not been verified with the uncertainty heads; run this mode on one GPU")
         self.frame_ids = [int(i) for i in self.opt.frame_ids] if self.photometric else [0]
         if self.photometric and (self.frame_ids[0] != 0 or len(self.frame_ids) < 2 or 0 in self.frame_ids[1:]
                                  or len(self.frame_ids) - 1 > ops.REPROJ_MAX_FRAMES):
@@ -302,7 +357,12 @@ class Trainer:
                                                              include_normals=self.opt.augment_normals,
                                                              include_xolp=self.opt.augment_xolp,
                                                              attention=_attention_variant(self.opt))
-        self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.opt.scales)
+        if self.uncertainty_loss is not None:     # the reference's heads, under its checkpoint names (depth_decoder.py:46-73)
+            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.opt.scales,
+                                                              uncertainty=True)
+            self.models["mono_depth"].uncertainty_detach = self.uncertainty_detach
+        else:
+            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.opt.scales)
         if _normals_decoder_variant(self.opt):
             if not self.opt.augment_normals:
                 raise ValueError("the separate normals decoder sits behind the normals encoder: it needs --augment_normals")
@@ -321,7 +381,15 @@ class Trainer:
 
         order = [n for n in ("rgb_encoder", "xolp_encoder", "normals_encoder", "joint_encoder", "mono_depth",
                              "normals_decoder", "pose_encoder", "pose") if n in self.models]
-        self.store = ParamStore(self.models, order=order, unused=_unused_resnet_param, device=self.device)
+        unused = _unused_resnet_param
+        if self.uncertainty_loss is not None:
+            # the unc_conv_color heads run but nothing consumes them: no gradient, no Adam update; they stay in the checkpoint.
+            # Found through the decoder's own keys, not by their place in its ModuleList
+            dec = self.models["mono_depth"]
+            idle = {id(p) for key, m in dec.convs.items() if key[0] == "unc_conv_color" for p in m.parameters()}
+            idle_names = {n for n, p in dec.named_parameters() if id(p) in idle}
+            unused = lambda mn, pn: _unused_resnet_param(mn, pn) or (mn == "mono_depth" and pn in idle_names)
+        self.store = ParamStore(self.models, order=order, unused=unused, device=self.device)
         for n in order:
             self.parameters_to_train += list(self.models[n].parameters())
         self.reducer = GradReducer(self.store) if self.distributed else None
@@ -648,6 +716,17 @@ class Trainer:
                 polar.append(w_n * terms[i][0] + w_a * terms[i][1])
                 losses[f"loss/{s}"] = losses[f"loss/{s}"] + polar[i]
             losses["loss"] = losses["loss"] + sum(polar[1:], polar[0]) / len(polar)
+        if self.uncertainty_loss is not None:
+            # per scale, the ground truth under the Laplace model whose scale the scale's uncertainty head states
+            # (functional.uncertainty_loss): w L_s joins loss/{s}, its mean over the scales joins loss, as the polarimetric term
+            terms = PF.uncertainty_loss(self.loss_cfg, disps, depths, [outputs[("uncertainty", s)] for s in scales],
+                                        inputs["depth"], self.uncertainty_range, detach_depth=self.uncertainty_detach)
+            unc = []
+            for i, s in enumerate(scales):
+                losses[f"uncertainty_loss/{s}"] = terms[i]
+                unc.append(self.uncertainty_loss * terms[i])
+                losses[f"loss/{s}"] = losses[f"loss/{s}"] + unc[i]
+            losses["loss"] = losses["loss"] + sum(unc[1:], unc[0]) / len(unc)
         if ("normals_pred", 0) in outputs:
             # `arch1++_separate_normals_dec`: the predicted normals against the normals of the ground truth, weighted like
             # the normals term of the depth loss (README.md:54,67: normals_loss_weight)
@@ -820,12 +899,14 @@ class Trainer:
             # resume state (not in the reference, which restarts epoch/step/LR schedule on load).
             # run_epoch saves on its logging steps BEFORE self.step += 1 and before lr_scheduler.step(): such a
             # checkpoint is marked incomplete and resumes inside the same epoch.
-            _save({"epoch": self.epoch, "step": self.step, "epoch_complete": bool(epoch_complete),
-                   "batch_idx": int(batch_idx), "lr_scheduler": self.model_lr_scheduler.state_dict(),
-                   "dropout_seed": PF.DropoutState.seed,
-                   "dropout_step": PF.DropoutState.get_step(getattr(self, "device", None)),
-                   "xolp_norm": None if getattr(self, "xolp_norm", None) is None else list(self.xolp_norm)},
-                  "trainer_state.pth")
+            state = {"epoch": self.epoch, "step": self.step, "epoch_complete": bool(epoch_complete),
+                     "batch_idx": int(batch_idx), "lr_scheduler": self.model_lr_scheduler.state_dict(),
+                     "dropout_seed": PF.DropoutState.seed,
+                     "dropout_step": PF.DropoutState.get_step(getattr(self, "device", None)),
+                     "xolp_norm": None if getattr(self, "xolp_norm", None) is None else list(self.xolp_norm)}
+            if getattr(self, "uncertainty_loss", None) is not None:      # the scale the uncertainty heads were trained to state
+                state["uncertainty_range"] = list(self.uncertainty_range)
+            _save(state, "trainer_state.pth")
         if self.distributed:
             torch.distributed.barrier()
 
@@ -870,6 +951,15 @@ class Trainer:
                 self.opt.xolp_norm = list(theirs)
                 if "xolp_encoder" in self.models:
                     self.models["xolp_encoder"].Conv1.in_affine = theirs
+        if st is not None and getattr(self, "uncertainty_loss", None) is not None and st.get("uncertainty_range") is not None:
+            # the heads state their scale in the checkpoint's range: adopt it, or refuse a different one
+            theirs = ops.uncertainty_range(st["uncertainty_range"])
+            if getattr(self, "_uncertainty_range_given", False) and tuple(theirs) != tuple(self.uncertainty_range):
+                raise ValueError(f"uncertainty_range = {tuple(self.uncertainty_range)!r} is set, but the heads of the "
+                                 f"checkpoint in {folder} were trained with {tuple(theirs)!r}: unset the option to adopt "
+                                 "the checkpoint's range")
+            self.uncertainty_range = theirs
+            self.opt.uncertainty_range = list(theirs)
         if st is not None and getattr(self.opt, "resume_state", True):
             if st.get("epoch_complete", True):       # written by train() after run_epoch (scheduler already stepped)
                 self.resume_epoch, self.resume_step, self.resume_batch = int(st["epoch"]) + 1, int(st["step"]), 0

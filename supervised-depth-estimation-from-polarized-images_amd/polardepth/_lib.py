@@ -176,6 +176,11 @@ SIGNATURES = {
     "pd_polar_loss_fwd_ray": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _dbl, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i,
                                    _vp]),
     "pd_polar_loss_bwd_ray": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "pd_unc_loss_rows": (_i, [_i, _i, _i]),
+    "pd_unc_loss_fwd": (_i, [_vp, _vp, _l, _vp, _i, _i, _vp, _f, _f, _dbl, _dbl, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pd_unc_loss_bwd": (_i, [_vp, _vp, _l, _vp, _i, _i, _vp, _f, _f, _dbl, _dbl, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "pd_unc_stats_workspace": (_sz, [_i, _i, _i, _i]),
+    "pd_unc_stats": (_i, [_vp, _vp, _vp, _vp, _ip, _i, _vp, _dbl, _dbl, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
 }
 
 

@@ -1194,6 +1194,27 @@ def polarimetric_loss(cfg, disps, depths, K, pol_normals, xolp, valid=None, rho_
     return losses
 
 
+def uncertainty_loss(cfg, disps, depths, uncs, gt, b_range=None, valid=None, detach_depth=False):
+    """The depth-uncertainty term per scale -> [L_s]: every full-resolution depth map goes on the tape through
+    ``DispDepthFn`` (unless ``detach_depth``), as ``polarimetric_loss`` does it, and ``ops.uncertainty_loss`` scores the
+    ground truth under the Laplace model whose scale the scale's uncertainty head states.
+
+    disps    the disparity maps [N,1,hs,ws] the term is differentiable in (an entry, or the list, may be None: that depth
+             map is data); depths: the full-resolution depth maps [N,1,H,W] ``multiscale_loss`` returned for them
+    uncs     the uncertainty maps [N,1,hs,ws], one per scale: the decoder's ("uncertainty", s)
+    gt       [N,1,H,W] ground-truth depth; the mask is the supervised term's, cfg.min_depth <= gt <= cfg.max_depth
+    b_range  (b_lo, b_hi) in metres, None = ``ops.UNCERTAINTY_RANGE``; valid: the pixels the term may use, or None
+    detach_depth   no gradient reaches the disparity maps: the heads are trained on top of the network as it is"""
+    if len(uncs) != len(depths):
+        raise ValueError("uncertainty_loss: one uncertainty map per scale")
+    losses = []
+    for i, d in enumerate(depths):
+        if not detach_depth and disps is not None and disps[i] is not None:
+            d = DispDepthFn.apply(disps[i], d, cfg.min_depth, cfg.max_depth)
+        losses.append(ops.uncertainty_loss(d, gt, uncs[i], b_range, cfg.min_depth, cfg.max_depth, valid, detach_depth))
+    return losses
+
+
 # ------------------------------------------------------------------ layers.get_smooth_loss as a function of its own
 class SmoothLossFn(torch.autograd.Function):
     """layers.py:452-465 on the K5 kernels: mean |dx disp| e^{-|dx I|} + mean |dy disp| e^{-|dy I|} of the disparity AS GIVEN

@@ -996,6 +996,112 @@ def polar_loss(depth, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.
     return values[0], values[1]
 
 
+# ------------------------------------------------------------------ depth-uncertainty loss (csrc/unc_loss.hip)
+UNCERTAINTY_RANGE = (0.0005, 0.5)       # (b_lo, b_hi) in metres: a convention (0.5 mm .. 0.5 m, u = 0.5 -> 15.8 mm), not a measurement
+
+
+class UncertaintyLossDetails:
+    """What ``uncertainty_loss(..., details=True)`` adds: ``sums`` float64 [4] (sum |g - d| / b, sum log 2b, sum m, sum b) and
+    ``maps`` fp32 [N,H,W,2] = (the pixel's term, b in metres), NaN where a pixel is not under the mask.  On the device."""
+
+    def __init__(self, sums, maps):
+        self.sums, self.maps = sums, maps
+
+
+def uncertainty_range(b_range):
+    """(b_lo, b_hi) as floats; ``None`` is UNCERTAINTY_RANGE.  0 < b_lo < b_hi < inf or ValueError."""
+    import math
+    lo, hi = UNCERTAINTY_RANGE if b_range is None else b_range
+    lo, hi = float(lo), float(hi)
+    if not (0.0 < lo < hi and math.isfinite(hi)):
+        raise ValueError(f"uncertainty range must be 0 < b_lo < b_hi < inf (metres), got ({lo!r}, {hi!r})")
+    return lo, hi
+
+
+class _UncLossFn(torch.autograd.Function):
+    """pd_unc_loss_fwd / _bwd + pd_up_gather_bwd: returns (value [1], sums [4], maps); differentiable in the depth map (unless
+    detached) and in the uncertainty map."""
+
+    @staticmethod
+    def forward(ctx, depth, unc, gt, ldg, valid, opts, detach, want_maps):
+        N, _, H, W = depth.shape
+        hs, ws = unc.shape[2], unc.shape[3]
+        dev = depth.device
+        min_d, max_d, b_lo, b_hi = opts
+        sums = torch.zeros(4, dtype=torch.float64, device=dev)
+        value = torch.zeros(1, dtype=torch.float32, device=dev)
+        maps = torch.empty((N, H, W, 2), dtype=torch.float32, device=dev) if want_maps else None
+        ws_ = torch.empty((lib.pd_unc_loss_rows(N, H, W), 4), dtype=torch.float64, device=dev)
+        check(lib.pd_unc_loss_fwd(ptr(depth), ptr(gt), ldg, ptr(unc), hs, ws, ptr(valid), min_d, max_d, b_lo, b_hi, ptr(sums),
+                                  ptr(value), ptr(maps), ptr(ws_), ws_.numel() * 8, N, H, W, stream_ptr()), "pd_unc_loss_fwd")
+        ctx.geom = (N, H, W, hs, ws, ldg, opts, detach)
+        ctx.save_for_backward(depth, unc, gt, valid, sums)
+        if maps is None:
+            maps = torch.empty(0, dtype=torch.float32, device=dev)
+        ctx.mark_non_differentiable(sums, maps)
+        return value, sums, maps
+
+    @staticmethod
+    def backward(ctx, gvalue, _gsums, _gmaps):
+        depth, unc, gt, valid, sums = ctx.saved_tensors
+        N, H, W, hs, ws, ldg, (min_d, max_d, b_lo, b_hi), detach = ctx.geom
+        st = stream_ptr()
+        gdepth = torch.empty_like(depth) if (ctx.needs_input_grad[0] and not detach) else None
+        gup = torch.empty((N, 1, H, W), dtype=torch.float32, device=depth.device)
+        check(lib.pd_unc_loss_bwd(ptr(depth), ptr(gt), ldg, ptr(unc), hs, ws, ptr(valid), min_d, max_d, b_lo, b_hi,
+                                  ptr(gvalue.float().reshape(1).contiguous()), ptr(sums), ptr(gdepth), ptr(gup), N, H, W, st),
+              "pd_unc_loss_bwd")
+        gunc = None
+        if ctx.needs_input_grad[1]:
+            gunc = torch.empty_like(unc)
+            generic = int(H % hs != 0 or W % ws != 0)
+            check(lib.pd_up_gather_bwd(ptr(gup), ptr(gunc), N, hs, ws, H, W, 0, generic, st), "pd_up_gather_bwd")
+        return gdepth, gunc, None, None, None, None, None, None
+
+
+def uncertainty_loss(depth, gt, unc, b_range=None, min_depth=0.1, max_depth=2.0, valid=None, detach_depth=False, details=False):
+    """The negative log-likelihood of the ground-truth depth under a Laplace error model whose scale the network states:
+    L = sum m (|gt - depth| / b + log 2b) / sum m, with log b = log b_lo + u log(b_hi / b_lo) and u the uncertainty head's
+    sigmoid output sampled to the frame (bilinear, align_corners=False, inside the kernel).  Definition:
+    include/polardepth.h.  Returns the scalar loss (and an ``UncertaintyLossDetails``).
+
+    depth         [N,1,H,W] fp32 full-resolution depth in metres
+    gt            [N,1,H,W] or [N,H,W] ground truth; a view whose rows are padded is read in place
+    unc           [N,1,hs,ws] the head's output, hs <= H and ws <= W at any ratio
+    b_range       (b_lo, b_hi) in metres, None = UNCERTAINTY_RANGE.  A convention, not a measurement
+    min_depth, max_depth   the supervised term's mask, min_depth <= gt <= max_depth
+    valid         [N,1,H,W] or [N,H,W] bool / uint8 or None: a 0 takes the pixel out
+    detach_depth  no gradient reaches ``depth`` (it is not formed): heads trained on top of a finished network
+    details       also return an ``UncertaintyLossDetails``"""
+    from ._records import frames
+    _require_cuda(depth, gt, unc, valid)
+    if depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError(f"uncertainty_loss: depth must be [N,1,H,W], got {tuple(depth.shape)}")
+    N, _, H, W = depth.shape
+    if unc.dim() != 4 or unc.shape[0] != N or unc.shape[1] != 1 or not (0 < unc.shape[2] <= H and 0 < unc.shape[3] <= W):
+        raise ValueError(f"uncertainty_loss: unc must be [{N},1,hs,ws] with hs <= {H} and ws <= {W}, got {tuple(unc.shape)}")
+    b_lo, b_hi = uncertainty_range(b_range)
+    gt = frames(gt.detach(), "gt", N, H, W)
+    if gt.dtype != torch.float32 or gt.stride(2) != 1 or gt.stride(1) < W or (N > 1 and gt.stride(0) != H * gt.stride(1)):
+        gt = gt.float().contiguous()
+    ldg = gt.stride(1)
+    if valid is not None:
+        valid = frames(valid, "valid", N, H, W).ne(0).to(torch.uint8).contiguous()
+    opts = (float(min_depth), float(max_depth), b_lo, b_hi)
+    if N == 0:                           # nothing to launch: the value is 0, and so is the gradient
+        dev = depth.device
+        value = (depth.float().sum() + unc.float().sum()) * 0.0
+        out = UncertaintyLossDetails(torch.zeros(4, dtype=torch.float64, device=dev),
+                                     torch.empty((0, H, W, 2), dtype=torch.float32, device=dev))
+        return (value, out) if details else value
+    with torch.cuda.device(depth.device):
+        value, sums, maps = _UncLossFn.apply(depth.float().contiguous(), unc.float().contiguous(), gt, int(ldg), valid, opts,
+                                             bool(detach_depth), bool(details))
+    if details:
+        return value[0], UncertaintyLossDetails(sums, maps)
+    return value[0]
+
+
 def depth_metrics(gt, pred, min_depth, max_depth, mask=None, mask_value=0):
     """Per-image depth metrics on the device: [N,8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count."""
     _require_cuda(gt, pred, mask)

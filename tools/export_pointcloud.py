@@ -12,7 +12,10 @@ predicted depth maps agree with this one at MVSNet's thresholds under the loader
 (pd_gt_normals).  ``--normals polar`` writes the polarisation normal instead wherever the measurement gives one: of the three
 physical candidates of K1 and their pi flips, the one closest to the depth normal (``pol_normal`` where ``choice != 0`` of
 ``polardepth.polar_normals_eval.polar_normals_stats``), the depth normal elsewhere.  ``--ray_frame`` makes that choice in the
-frame of each pixel's viewing ray; the normal written is still a camera-frame one.  ``gt.ply`` is unchanged."""
+frame of each pixel's viewing ray; the normal written is still a camera-frame one.  ``--max_uncertainty_mm X`` writes only the
+predicted points whose stated uncertainty -- the Laplace scale b of the decoder's uncertainty head, ``Evaluation(uncertainty=True)``
+-- is at most X millimetres; it needs weights trained with ``opt.uncertainty_loss`` and combines with ``--consistent``.
+``gt.ply`` is unchanged."""
 import argparse
 import os
 import sys
@@ -22,7 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarize
 
 
 def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None, normals=None, aolp_sign=None,
-           ray_frame=None):
+           ray_frame=None, max_uncertainty_mm=None):
     import torch
     from torch.utils.data.dataloader import default_collate
     from manydepth.evaluation import Evaluation
@@ -30,19 +33,26 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True, con
     if normals not in (None, "polar", "depth"):
         raise ValueError(f'--normals takes "polar" or "depth", got {normals!r}')
     ev = Evaluation(load_weights_folder=weights, data_path=data_path, height=height, width=width, batch_size=1,
-                    aolp_sign=aolp_sign, polar_ray_frame=ray_frame)
+                    aolp_sign=aolp_sign, polar_ray_frame=ray_frame, **({} if max_uncertainty_mm is None else {"uncertainty": True}))
     ev.load_mono_model()
     ds = ev.test_loader.dataset
     if not 0 <= index < len(ds):
         raise IndexError(f"--index {index}: the test split holds {len(ds)} items")
     inputs = {k: v.to(ev.device) for k, v in default_collate([ds[index]]).items()}
     colour = inputs[("color", 0, 0)][0].float()                        # [3,H,W] in 0 .. 1, before predict expands the batch
-    depth = ev.predict(inputs)
+    scale = None
+    if max_uncertainty_mm is not None:            # one pass gives the depth and the head's Laplace scale b
+        both = ev.predict_all(inputs)
+        depth, scale = both["depth"], both["uncertainty"]
+    else:
+        depth = ev.predict(inputs)
     gt, K = inputs["depth_gt"], inputs[("K", 0)]
     if consistent is not None:
         depth, gt_gate = consistent_depth(ev, index, depth, gt, int(consistent))
     else:
         gt_gate = gt
+    if scale is not None:                         # the head's own statement of where the prediction should not be trusted
+        gt_gate = torch.where(scale * 1e3 <= float(max_uncertainty_mm), gt_gate, torch.zeros_like(gt_gate))
     clouds = {"pred": pc.backproject(depth, K, gate=gt_gate, min_depth=ev.min_depth, max_depth=ev.max_depth),
               "gt": pc.backproject(gt, K, min_depth=ev.min_depth, max_depth=ev.max_depth)}
     rgb = (colour.permute(1, 2, 0).reshape(-1, 3) * 255).round().clamp(0, 255).to(torch.uint8).cpu()
@@ -117,7 +127,9 @@ if __name__ == "__main__":
     ap.add_argument("--aolp_sign", type=int, choices=(1, -1), default=None, help="the AoLP handedness for --normals polar")
     ap.add_argument("--ray_frame", action="store_true", default=None,
                     help="--normals polar: choose the candidate in the frame of each pixel's viewing ray")
+    ap.add_argument("--max_uncertainty_mm", type=float, default=None, metavar="X",
+                    help="keep the predicted points whose stated uncertainty (Laplace scale b) is at most X mm")
     args = ap.parse_args()
     for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip,
-                          args.consistent, args.normals, args.aolp_sign, args.ray_frame).items():
+                          args.consistent, args.normals, args.aolp_sign, args.ray_frame, args.max_uncertainty_mm).items():
         print(f"{path}: {n} points")

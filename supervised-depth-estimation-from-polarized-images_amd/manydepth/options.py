@@ -15,6 +15,11 @@ _DATASETS = ["kitti", "kitti_odom", "kitti_depth", "kitti_test", "cityscapes_pre
 _EVAL_SPLITS = ["eigen", "eigen_benchmark", "benchmark", "odom_9", "odom_10", "cityscapes", "ppp", "HAMMER",
                 "HAMMER_unseen", "eccv_depth_stereo"]
 
+# --models_to_load as the reference's parser presets it (options.py:310-314).  Trainer.load_model reads a list equal to it
+# as "nothing was named" and loads every model of the run: the names are the reference's, and this build's depth networks
+# (rgb_encoder, ..., mono_depth) are not among them.
+MODELS_TO_LOAD_DEFAULT = ("depth", "pose_encoder", "pose")
+
 # (flag, kwargs).  'flag' entries are store_true switches.
 _TYPED = [
     ("data_path", dict(type=_S, default=os.path.join("/media/patrick/LargeSSD/Datasets", "kitti"))),
@@ -49,7 +54,7 @@ _TYPED = [
     ("num_matching_frames", dict(type=_I, default=1)), ("dropout_rate", dict(type=_F, default=0.1)),
     ("num_workers", dict(type=_I, default=12)), ("load_weights_folder", dict(type=_S)),
     ("mono_weights_folder", dict(type=_S)),
-    ("models_to_load", dict(nargs="+", type=_S, default=["depth", "pose_encoder", "pose"])),
+    ("models_to_load", dict(nargs="+", type=_S, default=list(MODELS_TO_LOAD_DEFAULT))),
     ("log_frequency", dict(type=_I, default=500)), ("save_frequency", dict(type=_I, default=2)),
     ("pred_depth_scale_factor", dict(type=_F, default=1)), ("ext_disp_to_eval", dict(type=_S)),
     ("eval_split", dict(type=_S, default="eigen", choices=_EVAL_SPLITS)), ("eval_out_dir", dict(type=_S)),

@@ -65,6 +65,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
+from .options import MODELS_TO_LOAD_DEFAULT
 from .utils import readlines, sec_to_hm_str
 from .layers import SSIM, compute_depth_errors, compute_depth_errors_numpy
 from manydepth import datasets, networks
@@ -884,7 +885,21 @@ class Trainer:
 
     def save_model(self, epoch_complete=True, batch_idx=-1):
         """trainer.py:1597-1617 layout (<model>.pth + adam.pth) plus trainer_state.pth.  Only rank 0 writes; every file
-        goes through a temporary name + os.replace, and all ranks meet at a barrier afterwards."""
+        goes through a temporary name + os.replace, and all ranks meet at a barrier afterwards.
+
+        "A loaded trainer_state.pth continues where the checkpoint stopped" (train) covers what these files hold.  Restored by
+        load_model: every model's parameters and buffers (BatchNorm running statistics, num_batches_tracked); Adam's two
+        moment buffers, step count (the bias correction of the next step; the device word of a captured step too) and
+        hyper-parameters, the learning rate among them; the StepLR state; epoch, step and the batch to resume behind; the
+        dropout stream (Philox seed and step counter); the XOLP standardisation and the uncertainty range.  A resumed run
+        fed the batches and torch seeds of the uninterrupted one repeats it bit for bit, in every training mode
+        (tests/test_resume_gpu.py).
+
+        NOT in the checkpoint, so a resumed run differs from the uninterrupted one in them:
+          * the order of the shuffled ``train_loader`` (``shuffle=True`` without a seeded generator): ``resume_batch`` skips
+            that many batches of a DIFFERENT permutation of the epoch;
+          * the loaders' augmentation draws (colour jitter, flips);
+          * torch's global generator, from which the photometric modes draw their automask noise."""
         save_folder = os.path.join(self.log_path, "models", "weights_{}".format(self.epoch))
         if self.rank == 0:
             os.makedirs(save_folder, exist_ok=True)
@@ -923,11 +938,25 @@ class Trainer:
             if n in self.models and os.path.isfile(path):
                 self._load_into(n, path, strict=True)
 
+    def _models_to_load(self):
+        """The models load_model reads.  --models_to_load left at the parser's preset (options.MODELS_TO_LOAD_DEFAULT: the
+        reference's names, which never cover this build's depth networks) means nothing was named: every model of this run,
+        in every mode -- with the pose network too, whose ``pose_encoder`` / ``pose`` are among the preset's names.  A list
+        that differs from the preset is explicit and keeps the reference's meaning (trainer.py:1659): exactly those names;
+        the ones this run does not build are skipped, and a list none of whose names it builds falls back to every model."""
+        named = list(getattr(self.opt, "models_to_load", None) or [])
+        if named == list(MODELS_TO_LOAD_DEFAULT):
+            return list(self.models)
+        return [n for n in named if n in self.models] or list(self.models)
+
     def load_model(self):
+        """Reads what save_model wrote: of the models ``_models_to_load`` names those that have a file in the folder, then
+        adam.pth and trainer_state.pth (``opt.resume_state = False`` leaves the resume point, the LR schedule and the dropout
+        stream alone).  Works on a Trainer that has already trained: nothing derived from the weights outlives a forward
+        pass (the transposed data-gradient operands are rebuilt behind every forward convolution)."""
         folder = os.path.expanduser(self.opt.load_weights_folder)
         assert os.path.isdir(folder), "Cannot find folder {}".format(folder)
-        names = [n for n in self.opt.models_to_load if n in self.models] or list(self.models)
-        for n in names:
+        for n in Trainer._models_to_load(self):
             path = os.path.join(folder, "{}.pth".format(n))
             if os.path.isfile(path):
                 self._load_into(n, path)

@@ -270,6 +270,8 @@ class FusedAdam(torch.optim.Optimizer):
             self.store._view(self.exp_avg, p, off).copy_(st["exp_avg"])
             self.store._view(self.exp_avg_sq, p, off).copy_(st["exp_avg_sq"])
         self.step_count = max(steps) if steps else 0
+        if self.device_step:                   # a captured step reads t from the device word: it follows the loaded count
+            self.dev_state[1] = self.step_count
 
 
 class GradReducer:

@@ -288,6 +288,56 @@ def test_resume_state_distinguishes_mid_epoch_from_end_of_epoch_checkpoints():
         assert not [f for f in os.listdir(b.opt.load_weights_folder) if f.endswith(".tmp")]    # atomic writes leave no temp files
 
 
+_DEPTH_MODELS = ["rgb_encoder", "xolp_encoder", "normals_encoder", "joint_encoder", "mono_depth"]
+
+
+@pytest.mark.parametrize("models, named, want", [
+    # the parser's preset names none of the supervised modes' models: every model
+    (_DEPTH_MODELS, None, _DEPTH_MODELS),
+    # ... and with the pose network it names two of seven: still every model, not just those two
+    (_DEPTH_MODELS + ["pose_encoder", "pose"], None, _DEPTH_MODELS + ["pose_encoder", "pose"]),
+    # an explicit list: exactly those names
+    (_DEPTH_MODELS + ["pose_encoder", "pose"], ["pose"], ["pose"]),
+    # ... and a name this run does not build is skipped without error
+    (_DEPTH_MODELS, ["mono_depth", "normals_decoder"], ["mono_depth"]),
+], ids=["default-supervised", "default-with-pose-models", "explicit-pose", "explicit-absent-name"])
+def test_load_model_reads_the_models_the_options_name(tmp_path, models, named, want):
+    """Which ``<model>.pth`` files Trainer.load_model reads, with a checkpoint folder that holds one for every model and
+    ``--models_to_load`` parsed by the real parser (left out = its preset)."""
+    import types
+    from manydepth.options import MonodepthOptions, MODELS_TO_LOAD_DEFAULT
+    from manydepth.trainer import Trainer
+    assert MonodepthOptions().parser.get_default("models_to_load") == list(MODELS_TO_LOAD_DEFAULT) == ["depth", "pose_encoder", "pose"]
+
+    def fake_trainer():
+        t = types.SimpleNamespace()
+        t.rank, t.distributed, t.epoch, t.step, t.log_path = 0, False, 0, 0, str(tmp_path)
+        t.models = {n: torch.nn.Linear(2, 2) for n in models}
+        opt = torch.optim.SGD([p for m in t.models.values() for p in m.parameters()], lr=1.0)
+        t.model_optimizer = opt
+        t.model_lr_scheduler = torch.optim.lr_scheduler.StepLR(opt, 2, 0.1)
+        t.opt = MonodepthOptions().parse([] if named is None else ["--models_to_load", *named])
+        t.opt.resume_state = True
+        t.device = None
+        t.read = []
+        t._load_into = lambda n, path, strict=False: t.read.append((n, os.path.basename(path)))
+        return t
+    a = fake_trainer()
+    Trainer.save_model(a)
+    folder = os.path.join(str(tmp_path), "models", "weights_0")
+    assert all(os.path.isfile(os.path.join(folder, n + ".pth")) for n in models)
+    b = fake_trainer()
+    b.opt.load_weights_folder = folder
+    Trainer.load_model(b)
+    assert b.read == [(n, n + ".pth") for n in want]
+    if named is None:                              # a model without a file in the folder is passed over, the others still load
+        os.remove(os.path.join(folder, models[0] + ".pth"))
+        c = fake_trainer()
+        c.opt.load_weights_folder = folder
+        Trainer.load_model(c)
+        assert c.read == [(n, n + ".pth") for n in want[1:]]
+
+
 def test_lanczos_coefficient_tables_reproduce_pillow_on_the_host():
     """polardepth.resize.lanczos_coeffs (Pillow's precompute_coeffs / normalize_coeffs_8bpc) applied with NumPy
     integer arithmetic equals PIL's LANCZOS resize -- pins the tables the device kernels consume."""

@@ -107,11 +107,19 @@ def test_freeze_teacher_and_pose_runs_the_pose_pass_without_a_tape(trainer):
 
 
 def test_checkpoints_hold_both_pose_models_and_load_back(trainer):
-    """save_model writes pose_encoder.pth / pose.pth under the reference's key names; load_model (the default
-    --models_to_load names both) copies them back into the parameters the optimiser holds."""
+    """save_model writes pose_encoder.pth / pose.pth under the reference's key names; load_model copies them back into the
+    parameters the optimiser holds.  --models_to_load is at the parser's preset, which names both pose models and none of
+    the depth networks: load_model reads the preset as "nothing named" and loads EVERY model of the run, so a parameter of
+    ``mono_depth`` and one of ``rgb_encoder`` come back as well (the whole resume: tests/test_resume_gpu.py)."""
     import os
+    from manydepth.options import MODELS_TO_LOAD_DEFAULT
     tr, _ = trainer
     assert "pose_encoder" in tr.opt.models_to_load and "pose" in tr.opt.models_to_load
+    assert list(tr.opt.models_to_load) == list(MODELS_TO_LOAD_DEFAULT)
+    depth = {f"{m}.{k}": dict(tr.models[m].named_parameters())[k]
+             for m, k in (("mono_depth", "decoder.0.conv.conv.weight"), ("rgb_encoder", "encoder.conv1.weight"))}
+    depth_before = {k: p.detach().clone() for k, p in depth.items()}
+    assert all(v.abs().max().item() > 0 for v in depth_before.values())
     tr.save_model()
     folder = os.path.join(tr.log_path, "models", "weights_{}".format(tr.epoch))
     saved = {m: torch.load(os.path.join(folder, m + ".pth"), map_location="cpu") for m in ("pose_encoder", "pose")}
@@ -123,10 +131,12 @@ def test_checkpoints_hold_both_pose_models_and_load_back(trainer):
         for k, v in tr.models[m].state_dict().items():
             assert torch.equal(saved[m][k], v.detach().cpu()), (m, k)
     with torch.no_grad():
-        for p in named.values():
+        for p in list(named.values()) + list(depth.values()):
             p.zero_()
     tr.opt.load_weights_folder = folder
     tr.load_model()
+    for k, p in depth.items():
+        assert torch.equal(p.detach(), depth_before[k]), k
     for k, p in named.items():
         m, key = k.split(".", 1)
         assert torch.equal(p.detach().cpu(), saved[m][key]), k

@@ -1730,6 +1730,78 @@ int pd_unc_stats(const void* gt, const void* pred, const void* unc, const void* 
                  const void* edges, double b_lo, double b_hi, void* stats, void* tables, void* workspace, size_t ws_bytes,
                  int N, int H, int W, float min_depth, float max_depth, void* stream);
 
+/* ---- Polarimetric depth refinement (csrc/polar_refine.hip): the disambiguated polarisation normals (`pol_normal` of
+ * pd_polar_normals_stats) integrated back into the depth that disambiguated them.  The coarse depth keeps the low
+ * frequencies, the normals supply the relief.  The reference has no counterpart: the definition is this comment, and
+ * tests/polar_refine_ref.py states it in NumPy.  fp64 throughout, only + - x / sqrt in the order written here (the library is
+ * built without contraction), plus one log per pixel on the way in and one exp on the way out.
+ *
+ * Inputs.  depth fp32 [N,H,W] contiguous, the prior z; K fp32 [N,4,4] (fx = K[0][0], fy = K[1][1], cx = K[0][2],
+ * cy = K[1][2]); pol_normal fp32 [N,H,W,4], 16-byte aligned (the fourth float is not read); xolp fp32 [N,2,H,ldp], only
+ * channel 0 (the DoLP rho) is read, with the row pitch ldp >= W in elements (image pitch 2 * H * ldp); valid uint8 [N,H,W] or
+ * NULL.
+ *
+ * A PIXEL (x, y), all in fp64 from the fp32 inputs:
+ *     xt = ((double)x - cx) / fx,  yt = ((double)y - cy) / fy            the viewing ray r = (xt, yt, 1)
+ *     nr = (nx*xt + ny*yt) + nz,   n2 = (nx*nx + ny*ny) + nz*nz,   r2 = (xt*xt + yt*yt) + 1.0
+ *     zeta0 = log((double)z) where z is finite and > 0, else 0.0
+ *     live  = z finite and > 0,  n2 finite and > 0,  rho finite and > 0,  valid != 0,  and
+ *             fabs(nr) >= cos_inc * (sqrt(n2) * sqrt(r2))                (a NaN fails)
+ *     p = -nx / (fx * nr),  q = -ny / (fy * nr)                          d zeta/dx, d zeta/dy of the surface n . dP = 0, P = z r;
+ *                                                                        unchanged under n -> -n
+ * AN EDGE between a = (x, y) and b = (x+1, y) (E of a, W of b) or b = (x, y+1) (S of a, N of b) is live when both pixels are
+ * live and fabs(zeta0_b - zeta0_a) <= edge_max; then  w = sqrt(rho_a * rho_b),  g = (p_a + p_b) * 0.5  (q for S).  A dead edge,
+ * and every edge that leaves the image, has w = 0 and g = 0.
+ * THE SYSTEM per item: E = sum lam (zeta - zeta0)^2 + sum w (zeta_b - zeta_a - g)^2, whose normal equations have
+ *     s    = ((wE + wW) + wS) + wN                                       wW = wE of the left, wN = wS of the upper pixel
+ *     diag = (((lam + wE) + wW) + wS) + wN,      idiag = 1.0 / diag
+ *     rhs  = (((lam*zeta0 - wE*gE) + wW*gW) - wS*gS) + wN*gN
+ * pd_polar_refine_setup writes zeta0 double [N][H][W], coef double [N][4][H][W] = the planes wE, wS, rhs, idiag, and, where pq
+ * is not NULL, pq double [N][2][H][W] = (p, q), 0 where the pixel is not live.  A pixel is TOUCHED when s > 0.
+ * S[n] = max over the item of s: an exact maximum (partials per workgroup in the workspace, no atomics).
+ *
+ * THE SOLVER: Chebyshev semi-iteration on D^-1 A, whose spectrum lies in [a, 2 - a], a = lam / (lam + S) (Gershgorin's
+ * circles, and the grid is bipartite so the spectrum is symmetric about 1).  No inner products, hence no ordered sums.
+ * pd_polar_refine_table writes S and table double [N][iters][2] = (alpha_k, beta_k):
+ *     a = lam / (lam + S),  delta = 1.0 - a,  sigma = 1.0 / delta,  rho_0 = 1.0 / sigma
+ *     (alpha_0, beta_0) = (0, 1);   rho_k = 1.0 / (2.0*sigma - rho_{k-1}),  alpha_k = rho_k * rho_{k-1},
+ *     beta_k = (2.0*rho_k) / delta;   S == 0 (or not finite): every entry of the item is 0 and the item stays at its prior.
+ * pd_polar_refine_step, step k, a lane per pixel, zeta ping-pong (zeta_in != zeta_out), d in place:
+ *     r = touched ? (rhs + (((wE*zE + wW*zW) + wS*zS) + wN*zN)) * idiag - zeta : 0.0      (a zero weight's neighbour is not read)
+ *     d = k == 0 ? beta_0 * r : alpha_k * d + beta_k * r            (k == 0 does not read d)
+ *     zeta_out = zeta + d
+ * The start is zeta_0 = zeta0.  k must be in [0, iters).
+ *
+ * pd_polar_refine_finish: depth_out fp32 [N,H,W] = (float)exp(zeta) where touched, else the prior's bits (dead pixels,
+ * non-finite and non-positive priors included); touched uint8 [N,H,W]; residual double [N] = max over touched pixels of
+ * fabs(r) with r formed from zeta as above (0 where nothing is touched; a NaN is ignored).
+ *
+ * workspace: >= pd_polar_refine_workspace(N, H, W) bytes (never 0, a multiple of 16, monotone), 16-byte aligned; setup
+ * leaves the partial maxima there for table, finish uses it for the residual's.  One launch per call, two for finish
+ * (the map, then the maximum): plain vector stores, no atomics, no allocation, no synchronisation, no waiting between workgroups; capturable.
+ * N == 0 returns PD_OK after the checks.  Refusals (PD_EINVAL before any launch): null pointers, bad shapes, ldp < W, !(lam > 0),
+ * lam / edge_max not finite, edge_max < 0, cos_inc outside (0, 1], iters < 1, k outside [0, iters), zeta_in == zeta_out,
+ * misaligned pointers, a too-small workspace, a frame beyond 2^30 pixels or a batch beyond 2^31 workgroups.
+ * lam, iters, edge_max and the incidence limit are conventions of the caller, not measurements (polardepth/refine.py). */
+size_t pd_polar_refine_workspace(int N, int H, int W);
+int pd_polar_refine_setup(const void* depth, const void* K_intrinsics, const void* pol_normal, const void* xolp, long ldp,
+                          const void* valid, double lam, double edge_max, double cos_inc, void* zeta0, void* coef, void* pq,
+                          void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+int pd_polar_refine_table(const void* workspace, size_t ws_bytes, double lam, int iters, void* S, void* table, int N, int H,
+                          int W, void* stream);
+int pd_polar_refine_step(const void* coef, const void* table, int iters, int k, const void* zeta_in, void* zeta_out, void* d,
+                         int N, int H, int W, void* stream);
+/* pd_polar_refine_steps: the steps k0 .. k0 + T - 1, 1 <= T <= PD_POLAR_REFINE_MAX_T, in ONE launch: a workgroup holds its
+ * 64 x 18 pixels and a rim of T around them in LDS and reads the coefficients once (overlapped tiling, the rim is redundant
+ * work; workgroups do not wait for each other).  The result equals T calls of pd_polar_refine_step bit for bit.  Here d
+ * ping-pongs too: d_in (not read when k0 == 0, may then be NULL) != d_out.  Refusals: those of the step, T outside its range,
+ * k0 < 0 or k0 + T > iters, d_in == d_out. */
+#define PD_POLAR_REFINE_MAX_T 8
+int pd_polar_refine_steps(const void* coef, const void* table, int iters, int k0, int T, const void* zeta_in, void* zeta_out,
+                          const void* d_in, void* d_out, int N, int H, int W, void* stream);
+int pd_polar_refine_finish(const void* depth, const void* coef, const void* zeta, void* depth_out, void* touched,
+                           void* residual, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

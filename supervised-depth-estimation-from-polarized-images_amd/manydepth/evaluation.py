@@ -20,6 +20,7 @@ from polardepth import pointcloud
 from polardepth import pose_eval
 from polardepth import consistency_eval
 from polardepth import polar_normals_eval
+from polardepth import refine as pdrefine
 from polardepth import uncertainty_eval
 from polardepth import matching as pdmatching
 from polardepth._lib import lib, check, ptr, stream_ptr
@@ -28,13 +29,35 @@ _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, 
                   "glass": 160, "table": 180, "wall": 200}
 
 
+_REFINE_OPTIONS = ("lam", "iters", "edge_max", "incidence_max_deg", "rho_min", "rho_max", "rounds")
+
+
+def _polar_refine_option(value):
+    """Evaluation(polar_refine=) / $PD_POLAR_REFINE -> None (off) or the dict of options ``polar_refine`` is called with."""
+    if value is None or value is False or value in ("", "0"):
+        return None
+    if value is True or value == "1":
+        return {}
+    if isinstance(value, str):
+        parts = value.split(",")
+        if len(parts) != 2:
+            raise ValueError(f'PD_POLAR_REFINE must be "1" or "lam,iters", got {value!r}')
+        value = {"lam": float(parts[0]), "iters": int(parts[1])}
+    if not isinstance(value, dict) or set(value) - set(_REFINE_OPTIONS):
+        raise ValueError(f"polar_refine must be True or a dict with keys of {_REFINE_OPTIONS}, got {value!r}")
+    opts = dict(value)
+    d = {"lam": 0.02, "iters": 100, "edge_max": 0.05, "incidence_max_deg": 80.0, "rounds": 1}
+    pdrefine._check_solver_args(**{k: opts.get(k, v) for k, v in d.items()})
+    return opts
+
+
 class Evaluation:
     def __init__(self, load_weights_folder=None, data_path=None, height=320, width=480, batch_size=12,
                  augment_xolp=True, augment_normals=True, num_workers=0, joint_attention=None, pol_angles=None,
                  pol_layout=None, pol_demosaic=None, pol_bayer=None, pol_gains=None, pol_color_scale=None, xolp_norm=None,
                  pol_calibration=None, normals_decoder=None, pose_network=None, multi_frame=False, matching_ids=(0, -1),
                  multi_poses="files", num_depth_bins=96, depth_binning="linear", aolp_sign=None,
-                 polar_ray_frame=None, uncertainty=None, uncertainty_range=None):
+                 polar_ray_frame=None, uncertainty=None, uncertainty_range=None, polar_refine=None):
         """The reference hard-codes its machine's paths (evaluation.py:27-31); here they are arguments, falling back to
         $PD_EVAL_DATA_PATH / $PD_EVAL_WEIGHTS.  ``data_path="synthetic"`` serves seeded synthetic items; anything else
         must be a HAMMER tree (FileNotFoundError otherwise, like the reference on a wrong path).  ``pol_angles``: the
@@ -77,7 +100,15 @@ class Evaluation:
         reads $PD_UNCERTAINTY == "1".  The weights folder must then hold the heads (``load_mono_model`` says so otherwise).
         ``uncertainty_range``: the (b_lo, b_hi) in metres, or "lo,hi", that turns the heads' output into a Laplace scale; None
         looks at a trainer_state.pth in ``load_weights_folder`` that carries the range the heads were trained with and ends at
-        ``ops.UNCERTAINTY_RANGE``.  A convention, not a measurement.  Without ``uncertainty`` the object is what it was."""
+        ``ops.UNCERTAINTY_RANGE``.  A convention, not a measurement.  Without ``uncertainty`` the object is what it was.
+
+        ``polar_refine``: True, or a dict of ``polardepth.refine.polar_refine``'s options (lam, iters, edge_max,
+        incidence_max_deg, rho_min, rho_max, rounds): ``predict_all`` also returns the predicted depth refined with the
+        polarisation normals it disambiguates ("depth_refined", "refine_residual", "refine_touched"), and ``test_depth`` /
+        ``test_normals`` take ``source="refined"``.  None reads $PD_POLAR_REFINE: "1" = the defaults (conventions, not
+        measurements), "lam,iters" = those two.  It honours ``aolp_sign`` and ``polar_ray_frame``.  Without it not a bit of any
+        call or report changes."""
+        self.polar_refine = _polar_refine_option(os.environ.get("PD_POLAR_REFINE") if polar_refine is None else polar_refine)
         self.uncertainty = (os.environ.get("PD_UNCERTAINTY") == "1") if uncertainty is None else bool(uncertainty)
         if isinstance(uncertainty_range, str):
             uncertainty_range = [float(x) for x in uncertainty_range.split(",")]
@@ -256,6 +287,13 @@ class Evaluation:
             out["uncertainty"] = uncertainty_eval.scale_of(out["uncertainty_u"], self.uncertainty_range)
         if with_normals_pred and "normals_decoder" in self.models:
             out["normals_pred"] = self.models["normals_decoder"](nf)
+        if with_normals_pred and self.polar_refine is not None:
+            pol = normals if self.augment_normals else pdpolar.polar_inputs(
+                inputs, (self.height, self.width), ("xolp", "normals"), self.pol_angles, dofp=self.pol_dofp, cdofp=self.pol_cdofp,
+                calibration=self.pol_calibration)
+            ref = pdrefine.polar_refine(out["depth"], inputs[("K", 0)], pol, inputs["xolp", 0, 0], aolp_sign=self.aolp_sign,
+                                        ray_frame=self.polar_ray_frame, **self.polar_refine)
+            out["depth_refined"], out["refine_residual"], out["refine_touched"] = ref.depth, ref.residual, ref.touched
         return out
 
     @torch.no_grad()
@@ -323,18 +361,22 @@ class Evaluation:
         "bad": int}} with mean, median, rmse (degrees), the shares within 11.25 / 22.5 / 30 degrees and the pixel count:
         "per_image" is the mean over images of the per-image figures (this project's convention for depth; images without a
         pixel of the class do not count), "pooled" takes all pixels of all images as one set (the normals literature's).  The
-        records stay on the device until the loop is over."""
-        if source not in ("auto", "depth", "decoder"):
-            raise ValueError(f'source must be "auto", "depth" or "decoder", got {source!r}')
+        records stay on the device until the loop is over.  "refined" (``Evaluation(polar_refine=...)``) scores the normals of
+        the depth refined with the polarisation normals."""
+        if source not in ("auto", "depth", "decoder", "refined"):
+            raise ValueError(f'source must be "auto", "depth", "decoder" or "refined", got {source!r}')
         if source == "auto":
             source = "decoder" if "normals_decoder" in self.models else "depth"
         if source == "decoder" and "normals_decoder" not in self.models:
             raise ValueError('source="decoder" needs Evaluation(normals_decoder=True) (or PD_NORMALS_DECODER=1)')
+        if source == "refined" and self.polar_refine is None:
+            raise ValueError('source="refined" needs Evaluation(polar_refine=True) (or PD_POLAR_REFINE=1)')
+        key = {"decoder": "normals_pred", "depth": "depth", "refined": "depth_refined"}[source]
         total, sums, counts = None, None, None
         for inputs in self.test_loader:
             inputs = {k: v.to(self.device) for k, v in inputs.items()}
-            out = self._forward(inputs, source == "decoder")
-            st = normals_eval.normals_stats(out["normals_pred" if source == "decoder" else "depth"], inputs["depth_gt"],
+            out = self._forward(inputs, source != "depth")
+            st = normals_eval.normals_stats(out[key], inputs["depth_gt"],
                                             inputs[("K", 0)], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
                                             max_depth=self.max_depth)
             m = st.metrics()
@@ -443,15 +485,21 @@ class Evaluation:
         pixel count: "per_image" is the mean over images of the per-image figures (the reference's and ``test``'s convention;
         images without a pixel of the class do not count), "pooled" takes all pixels of all images as one set.  The records
         stay on the device until the loop is over.  ``source``: "mono" scores ``predict`` over the test loader, "multi"
-        (``multi_frame=True``) ``predict_multi`` over the loader that also serves the lookup frames -- the same scoring."""
-        if source not in ("mono", "multi"):
-            raise ValueError(f'source must be "mono" or "multi", got {source!r}')
+        (``multi_frame=True``) ``predict_multi`` over the loader that also serves the lookup frames, "refined"
+        (``polar_refine=...``) ``predict_all``'s "depth_refined" -- the same scoring."""
+        if source not in ("mono", "multi", "refined"):
+            raise ValueError(f'source must be "mono", "multi" or "refined", got {source!r}')
         if source == "multi" and not self.multi_frame:
             raise ValueError('source="multi" needs Evaluation(multi_frame=True)')
+        if source == "refined" and self.polar_refine is None:
+            raise ValueError('source="refined" needs Evaluation(polar_refine=True) (or PD_POLAR_REFINE=1)')
         total, sums, counts = None, None, None
         for inputs in (self.multi_loader if source == "multi" else self.test_loader):
             inputs = {k: v.to(self.device) for k, v in inputs.items()}
-            depth = self.predict_multi(inputs)["depth"] if source == "multi" else self.predict(inputs)
+            if source == "refined":
+                depth = self.predict_all(inputs)["depth_refined"]
+            else:
+                depth = self.predict_multi(inputs)["depth"] if source == "multi" else self.predict(inputs)
             st = depth_eval.depth_stats(depth, inputs["depth_gt"], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
                                         max_depth=self.max_depth, median_scaling=median_scaling)
             m = st.metrics()

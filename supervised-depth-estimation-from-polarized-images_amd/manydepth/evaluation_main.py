@@ -6,7 +6,8 @@ PD_EVAL_CONSISTENCY=1 the multi-view consistency report of the predicted depth (
 PD_EVAL_POLAR_NORMALS=1 the polarimetric normals report (Evaluation.test_polar_normals; PD_POL_AOLP_SIGN=-1 for a sensor of
 the other AoLP handedness, PD_POLAR_RAY_FRAME=1 to score in the frame of each pixel's viewing ray), PD_EVAL_UNCERTAINTY=1 the
 depth-uncertainty report (Evaluation.test_uncertainty; it makes Evaluation build the decoder with its uncertainty heads, as
-PD_UNCERTAINTY=1 does, and the weights folder must hold them)."""
+PD_UNCERTAINTY=1 does, and the weights folder must hold them), PD_POLAR_REFINE=1 (or "lam,iters") the one-pass depth report
+of the depth refined with the polarisation normals (Evaluation.test_depth(source="refined"); Evaluation reads the variable)."""
 import os
 
 from manydepth.evaluation import Evaluation
@@ -30,6 +31,8 @@ def main():
         ev.test_polar_normals()
     if os.environ.get("PD_EVAL_UNCERTAINTY") == "1":
         ev.test_uncertainty()
+    if os.environ.get("PD_POLAR_REFINE") not in (None, "", "0"):
+        ev.test_depth(median_scaling=os.environ.get("PD_EVAL_MEDIAN_SCALING") or None, source="refined")
 
 
 if __name__ == "__main__":

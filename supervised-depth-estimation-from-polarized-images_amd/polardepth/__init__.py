@@ -6,3 +6,11 @@ Thin host layer over ``libpolardepth.so`` (hand-written HIP for gfx950, C ABI de
 library is missing or the tensors are not on the GPU.
 """
 from ._lib import lib, LibraryMissing, check  # noqa: F401
+
+
+def __getattr__(name):
+    # polar_refine / PolarRefined (polardepth/refine.py), imported on first use: the package itself stays free of torch
+    if name in ("polar_refine", "PolarRefined"):
+        from . import refine
+        return getattr(refine, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -181,6 +181,12 @@ SIGNATURES = {
     "pd_unc_loss_bwd": (_i, [_vp, _vp, _l, _vp, _i, _i, _vp, _f, _f, _dbl, _dbl, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pd_unc_stats_workspace": (_sz, [_i, _i, _i, _i]),
     "pd_unc_stats": (_i, [_vp, _vp, _vp, _vp, _ip, _i, _vp, _dbl, _dbl, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
+    "pd_polar_refine_workspace": (_sz, [_i, _i, _i]),
+    "pd_polar_refine_setup": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pd_polar_refine_table": (_i, [_vp, _sz, _dbl, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "pd_polar_refine_step": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "pd_polar_refine_steps": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "pd_polar_refine_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 

@@ -996,6 +996,12 @@ def polar_loss(depth, K, pol_normals, xolp, valid=None, rho_min=0.05, rho_max=1.
     return values[0], values[1]
 
 
+def polar_refine(*args, **kwargs):
+    """``polardepth.refine.polar_refine``: the depth refined with the polarisation normals it disambiguated."""
+    from .refine import polar_refine as impl
+    return impl(*args, **kwargs)
+
+
 # ------------------------------------------------------------------ depth-uncertainty loss (csrc/unc_loss.hip)
 UNCERTAINTY_RANGE = (0.0005, 0.5)       # (b_lo, b_hi) in metres: a convention (0.5 mm .. 0.5 m, u = 0.5 -> 15.8 mm), not a measurement
 

@@ -15,6 +15,9 @@ physical candidates of K1 and their pi flips, the one closest to the depth norma
 frame of each pixel's viewing ray; the normal written is still a camera-frame one.  ``--max_uncertainty_mm X`` writes only the
 predicted points whose stated uncertainty -- the Laplace scale b of the decoder's uncertainty head, ``Evaluation(uncertainty=True)``
 -- is at most X millimetres; it needs weights trained with ``opt.uncertainty_loss`` and combines with ``--consistent``.
+``--refine`` exports the predicted depth refined with the polarisation normals it disambiguates
+(``polardepth.refine.polar_refine``; ``--refine_lam X --refine_iters N`` replace the conventional 0.02 and 100): the fine relief
+of ``--normals polar`` then lies in the points too, and every later option acts on the refined depth.
 ``gt.ply`` is unchanged."""
 import argparse
 import os
@@ -25,15 +28,20 @@ sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarize
 
 
 def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None, normals=None, aolp_sign=None,
-           ray_frame=None, max_uncertainty_mm=None):
+           ray_frame=None, max_uncertainty_mm=None, refine=False, refine_lam=None, refine_iters=None):
     import torch
     from torch.utils.data.dataloader import default_collate
     from manydepth.evaluation import Evaluation
     from polardepth import pointcloud as pc
     if normals not in (None, "polar", "depth"):
         raise ValueError(f'--normals takes "polar" or "depth", got {normals!r}')
+    if not refine and (refine_lam is not None or refine_iters is not None):
+        raise ValueError("--refine_lam and --refine_iters are options of --refine")
+    more = {} if max_uncertainty_mm is None else {"uncertainty": True}
+    if refine:
+        more["polar_refine"] = {k: v for k, v in (("lam", refine_lam), ("iters", refine_iters)) if v is not None}
     ev = Evaluation(load_weights_folder=weights, data_path=data_path, height=height, width=width, batch_size=1,
-                    aolp_sign=aolp_sign, polar_ray_frame=ray_frame, **({} if max_uncertainty_mm is None else {"uncertainty": True}))
+                    aolp_sign=aolp_sign, polar_ray_frame=ray_frame, **more)
     ev.load_mono_model()
     ds = ev.test_loader.dataset
     if not 0 <= index < len(ds):
@@ -41,9 +49,9 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True, con
     inputs = {k: v.to(ev.device) for k, v in default_collate([ds[index]]).items()}
     colour = inputs[("color", 0, 0)][0].float()                        # [3,H,W] in 0 .. 1, before predict expands the batch
     scale = None
-    if max_uncertainty_mm is not None:            # one pass gives the depth and the head's Laplace scale b
+    if max_uncertainty_mm is not None or refine:  # one pass gives the depth, the head's Laplace scale b, the refined depth
         both = ev.predict_all(inputs)
-        depth, scale = both["depth"], both["uncertainty"]
+        depth, scale = both["depth_refined" if refine else "depth"], both.get("uncertainty")
     else:
         depth = ev.predict(inputs)
     gt, K = inputs["depth_gt"], inputs[("K", 0)]
@@ -129,7 +137,11 @@ if __name__ == "__main__":
                     help="--normals polar: choose the candidate in the frame of each pixel's viewing ray")
     ap.add_argument("--max_uncertainty_mm", type=float, default=None, metavar="X",
                     help="keep the predicted points whose stated uncertainty (Laplace scale b) is at most X mm")
+    ap.add_argument("--refine", action="store_true", help="export the depth refined with the polarisation normals")
+    ap.add_argument("--refine_lam", type=float, default=None, metavar="X", help="--refine: the weight of the prior (0.02)")
+    ap.add_argument("--refine_iters", type=int, default=None, metavar="N", help="--refine: Chebyshev steps (100)")
     args = ap.parse_args()
     for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip,
-                          args.consistent, args.normals, args.aolp_sign, args.ray_frame, args.max_uncertainty_mm).items():
+                          args.consistent, args.normals, args.aolp_sign, args.ray_frame, args.max_uncertainty_mm, args.refine,
+                          args.refine_lam, args.refine_iters).items():
         print(f"{path}: {n} points")

@@ -23,10 +23,21 @@ from polardepth import polar_normals_eval
 from polardepth import refine as pdrefine
 from polardepth import uncertainty_eval
 from polardepth import matching as pdmatching
-from polardepth._lib import lib, check, ptr, stream_ptr
+from polardepth._records import ClassReport
 
 _MATERIAL_GREY = {"box": 20, "bottle": 40, "can": 60, "cup": 80, "remote": 100, "teapot": 120, "cutlery": 140,
                   "glass": 160, "table": 180, "wall": 200}
+
+
+def _option(value, var):
+    """A constructor argument, else the environment's string (None where neither is given)."""
+    return value if value is not None else os.environ.get(var)
+
+
+def _switch(value, env_on):
+    """A constructor argument as a bool, else what the environment says: ``env_on`` is the call's ``$PD_... == "1"``, spelled
+    out there (tests/test_polar_ray_cabi.py reads it in the constructor's source)."""
+    return env_on if value is None else bool(value)
 
 
 _REFINE_OPTIONS = ("lam", "iters", "edge_max", "incidence_max_deg", "rho_min", "rho_max", "rounds")
@@ -108,16 +119,16 @@ class Evaluation:
         ``test_normals`` take ``source="refined"``.  None reads $PD_POLAR_REFINE: "1" = the defaults (conventions, not
         measurements), "lam,iters" = those two.  It honours ``aolp_sign`` and ``polar_ray_frame``.  Without it not a bit of any
         call or report changes."""
-        self.polar_refine = _polar_refine_option(os.environ.get("PD_POLAR_REFINE") if polar_refine is None else polar_refine)
-        self.uncertainty = (os.environ.get("PD_UNCERTAINTY") == "1") if uncertainty is None else bool(uncertainty)
+        self.polar_refine = _polar_refine_option(_option(polar_refine, "PD_POLAR_REFINE"))
+        self.uncertainty = _switch(uncertainty, os.environ.get("PD_UNCERTAINTY") == "1")
         if isinstance(uncertainty_range, str):
             uncertainty_range = [float(x) for x in uncertainty_range.split(",")]
         if uncertainty_range is not None and not self.uncertainty:
             raise ValueError("uncertainty_range is an option of the uncertainty heads: it needs Evaluation(uncertainty=True) "
                              "(or PD_UNCERTAINTY=1)")
         self.uncertainty_range = None if uncertainty_range is None else ops.uncertainty_range(uncertainty_range)
-        self.polar_ray_frame = (os.environ.get("PD_POLAR_RAY_FRAME") == "1") if polar_ray_frame is None else bool(polar_ray_frame)
-        aolp_sign = aolp_sign if aolp_sign is not None else os.environ.get("PD_POL_AOLP_SIGN")
+        self.polar_ray_frame = _switch(polar_ray_frame, os.environ.get("PD_POLAR_RAY_FRAME") == "1")
+        aolp_sign = _option(aolp_sign, "PD_POL_AOLP_SIGN")
         self.aolp_sign = 1 if aolp_sign is None else int(aolp_sign)
         if self.aolp_sign not in (1, -1):
             raise ValueError(f"aolp_sign must be +1 or -1, got {aolp_sign!r}")
@@ -129,8 +140,8 @@ class Evaluation:
             pdmatching.chain_pairs(self.matching_ids)
             if multi_poses == "network":
                 pose_network = True
-        data_path = data_path if data_path is not None else os.environ.get("PD_EVAL_DATA_PATH")
-        load_weights_folder = load_weights_folder if load_weights_folder is not None else os.environ.get("PD_EVAL_WEIGHTS")
+        data_path = _option(data_path, "PD_EVAL_DATA_PATH")
+        load_weights_folder = _option(load_weights_folder, "PD_EVAL_WEIGHTS")
         if data_path is None:
             raise FileNotFoundError("Evaluation needs data_path (or $PD_EVAL_DATA_PATH): a HAMMER test tree, or 'synthetic'")
         if not torch.cuda.is_available():
@@ -139,51 +150,35 @@ class Evaluation:
         self.min_depth, self.max_depth, self.scales = 0.1, 2.0, [0, 1, 2, 3]
         self.augment_xolp, self.augment_normals = augment_xolp, augment_normals
         self.load_weights_folder = load_weights_folder
-        self.pol_angles = pdpolar.angles_from_degrees(pol_angles if pol_angles is not None else os.environ.get("PD_POL_ANGLES"))
-        self.pol_dofp = pddofp.options(pol_layout if pol_layout is not None else os.environ.get("PD_POL_LAYOUT"),
-                                       pol_demosaic if pol_demosaic is not None else os.environ.get("PD_POL_DEMOSAIC"))
-        self.pol_cdofp = pdcdofp.options(pol_layout if pol_layout is not None else os.environ.get("PD_POL_LAYOUT"),
-                                         pol_bayer if pol_bayer is not None else os.environ.get("PD_POL_BAYER"),
-                                         pol_gains if pol_gains is not None else os.environ.get("PD_POL_GAINS"),
-                                         pol_color_scale if pol_color_scale is not None
-                                         else os.environ.get("PD_POL_COLOR_SCALE"))
-        self.xolp_norm = pdpolar.parse_xolp_norm(xolp_norm if xolp_norm is not None else os.environ.get("PD_XOLP_NORM"))
-        self.pol_calibration = pdcal.parse(pol_calibration if pol_calibration is not None
-                                           else os.environ.get("PD_POL_CALIBRATION"), torch.device("cuda"))
+        self.pol_angles = pdpolar.angles_from_degrees(_option(pol_angles, "PD_POL_ANGLES"))
+        pol_layout = _option(pol_layout, "PD_POL_LAYOUT")
+        self.pol_dofp = pddofp.options(pol_layout, _option(pol_demosaic, "PD_POL_DEMOSAIC"))
+        self.pol_cdofp = pdcdofp.options(pol_layout, _option(pol_bayer, "PD_POL_BAYER"), _option(pol_gains, "PD_POL_GAINS"),
+                                         _option(pol_color_scale, "PD_POL_COLOR_SCALE"))
+        self.xolp_norm = pdpolar.parse_xolp_norm(_option(xolp_norm, "PD_XOLP_NORM"))
+        self.pol_calibration = pdcal.parse(_option(pol_calibration, "PD_POL_CALIBRATION"), torch.device("cuda"))
         if self.pol_calibration is not None and tuple(self.pol_calibration.layout) != tuple(self.pol_dofp[0]):
             raise ValueError(f"pol_calibration was fitted for the layout {tuple(self.pol_calibration.layout)}, pol_layout is "
                              f"{tuple(self.pol_dofp[0])}")
-        state_path = os.path.join(load_weights_folder, "trainer_state.pth") if load_weights_folder is not None else None
-        if self.xolp_norm is None and state_path is not None and os.path.isfile(state_path):
-            self.xolp_norm = pdpolar.parse_xolp_norm(torch.load(state_path, map_location="cpu").get("xolp_norm"))
-        if self.uncertainty and self.uncertainty_range is None:
-            stored = None
-            if state_path is not None and os.path.isfile(state_path):
-                stored = torch.load(state_path, map_location="cpu").get("uncertainty_range")
-            self.uncertainty_range = ops.uncertainty_range(stored)
+        # what the weights were trained with, where the arguments leave it open: one read of the Trainer's state file
+        want_range = self.uncertainty and self.uncertainty_range is None
+        state = {}
+        if (self.xolp_norm is None or want_range) and load_weights_folder is not None:
+            state_path = os.path.join(load_weights_folder, "trainer_state.pth")
+            if os.path.isfile(state_path):
+                state = torch.load(state_path, map_location="cpu")
+        if self.xolp_norm is None:
+            self.xolp_norm = pdpolar.parse_xolp_norm(state.get("xolp_norm"))
+        if want_range:
+            self.uncertainty_range = ops.uncertainty_range(state.get("uncertainty_range"))
         self.device = torch.device("cuda")
-        self.models = {"rgb_encoder": networks.ShallowResnetEncoder(18, False)}
-        if augment_normals:
-            self.models["normals_encoder"] = networks.ShallowNormalsEncoder(9, 0.0)
-        if augment_xolp:
-            self.models["xolp_encoder"] = networks.ShallowEncoder('XOLP', 2, 0.0, xolp_norm=self.xolp_norm)
-        self.models["joint_encoder"] = networks.JointEncoder(
-            0.0, augment_normals, augment_xolp,
-            attention=(os.environ.get("PD_JOINT_ATTENTION") == "1") if joint_attention is None else joint_attention)
-        if self.uncertainty:
-            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.scales,
-                                                              uncertainty=True)
-        else:
-            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.scales)
-        if (os.environ.get("PD_NORMALS_DECODER") == "1") if normals_decoder is None else normals_decoder:
-            if not augment_normals:
-                raise ValueError("the separate normals decoder sits behind the normals encoder: it needs augment_normals")
-            self.models["normals_decoder"] = networks.NormalsDecoder(64)
-        self.pose_network = (os.environ.get("PD_POSE_NETWORK") == "1") if pose_network is None else bool(pose_network)
-        if self.pose_network:                     # as Trainer.__init__ builds them (trainer.py:222-236, "separate_resnet")
-            self.models["pose_encoder"] = networks.ResnetEncoder(18, False, num_input_images=2)
-            self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc, num_input_features=1,
-                                                       num_frames_to_predict_for=2)
+        self.pose_network = _switch(pose_network, os.environ.get("PD_POSE_NETWORK") == "1")
+        self.models = networks.build_models(      # no pretrained weights, no dropout; the Trainer's order and draws
+            False, 0.0, self.xolp_norm, self.scales, augment_normals, augment_xolp,
+            attention=_switch(joint_attention, os.environ.get("PD_JOINT_ATTENTION") == "1"),
+            uncertainty=self.uncertainty,
+            normals_decoder=_switch(normals_decoder, os.environ.get("PD_NORMALS_DECODER") == "1"),
+            pose_network=self.pose_network)
         if self.multi_frame:                      # last: the models above draw what they drew without them
             self.models["encoder"] = networks.ResnetEncoderMatching(18, False, height, width, min_depth_bin=self.min_depth,
                                                                     max_depth_bin=self.max_depth,
@@ -203,25 +198,58 @@ class Evaluation:
             if str(data_path) != datasets.SYNTHETIC:
                 raise FileNotFoundError("splits/HAMMER_unseen/test_files.txt not found (evaluation.py:96)")
             files = []
-        ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0], 4, is_train=False)
+        self._loader_args = (data_path, files, num_workers)
+        self.test_loader = self._loader([0])
         if self.pol_calibration is not None:                  # a calibration of another frame size is refused here, not in predict
-            pdcal.check_dataset(self.pol_calibration, ds, "the test loader")
-        self.test_loader = DataLoader(ds, batch_size, False, num_workers=num_workers, drop_last=True)
+            pdcal.check_dataset(self.pol_calibration, self.test_loader.dataset, "the test loader")
         self.pose_frame_ids = [-1, 1]
         if self.pose_network:
             # a pair is scored only where the neighbour's picture and both pose files exist (need_poses=True)
-            pose_ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0] + self.pose_frame_ids, 4, is_train=False,
-                                              supervised_depth_only=False, need_poses=True)
-            self.pose_loader = DataLoader(pose_ds, batch_size, False, num_workers=num_workers, drop_last=True)
-        self._loader_args = (data_path, files, num_workers)
+            self.pose_loader = self._loader([0] + self.pose_frame_ids, supervised_depth_only=False, need_poses=True)
         self._chain_loaders = {}
         self._consistency_loaders = {}
         if self.multi_frame:
             # an absent lookup frame arrives as a zero picture with frame_valid 0 (and the identity as its pose: predict_multi
             # hands the sweep an all-zero pose instead); with "files" a frame counts only with both pose files
-            multi_ds = datasets.HAMMER_Dataset(data_path, files, height, width, [0] + self.matching_ids[1:], 4, is_train=False,
-                                               supervised_depth_only=False, need_poses=(multi_poses == "files"))
-            self.multi_loader = DataLoader(multi_ds, batch_size, False, num_workers=num_workers, drop_last=True)
+            self.multi_loader = self._loader([0] + self.matching_ids[1:], supervised_depth_only=False,
+                                             need_poses=(multi_poses == "files"))
+
+    def _loader(self, frame_ids, **dataset_kw):
+        """The test split's items with the frames ``frame_ids``, in order, in whole batches."""
+        data_path, files, num_workers = self._loader_args
+        ds = datasets.HAMMER_Dataset(data_path, files, self.height, self.width, frame_ids, 4, is_train=False, **dataset_kw)
+        return DataLoader(ds, self.batch_size, False, num_workers=num_workers, drop_last=True)
+
+    def _batches(self, loader):
+        """The loader's batches on the device, the nested ("neighbour", i) items of ``test_consistency`` included."""
+        def to_device(d):
+            return {k: to_device(v) if isinstance(v, dict) else v.to(self.device) for k, v in d.items()}
+        for inputs in loader:
+            yield to_device(inputs)
+
+    def _expand(self, inputs):
+        """Raw colour frames of the batch (HAMMER_Dataset(raw_color=True), colour sensor frames) -> its colour pyramids."""
+        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+
+    def _polar(self, inputs, want=("xolp", "normals")):
+        """K1 on the batch (``polar_inputs``): fills ("xolp", 0, 0) and returns the nine-channel normals, if wanted."""
+        return pdpolar.polar_inputs(inputs, (self.height, self.width), want, self.pol_angles, dofp=self.pol_dofp,
+                                    cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+
+    def _resolve_source(self, source, allowed):
+        """``source`` of a ``test_*`` method: one of ``allowed``, "auto" settled, and the option it needs switched on."""
+        if source not in allowed:
+            quoted = [f'"{a}"' for a in allowed]
+            raise ValueError(f'source must be {", ".join(quoted[:-1])} or {quoted[-1]}, got {source!r}')
+        if source == "auto":
+            source = "decoder" if "normals_decoder" in self.models else "depth"
+        if source == "decoder" and "normals_decoder" not in self.models:
+            raise ValueError('source="decoder" needs Evaluation(normals_decoder=True) (or PD_NORMALS_DECODER=1)')
+        if source == "multi" and not self.multi_frame:
+            raise ValueError('source="multi" needs Evaluation(multi_frame=True)')
+        if source == "refined" and self.polar_refine is None:
+            raise ValueError('source="refined" needs Evaluation(polar_refine=True) (or PD_POLAR_REFINE=1)')
+        return source
 
     def load_mono_model(self):
         if self.load_weights_folder is None:
@@ -264,33 +292,28 @@ class Evaluation:
         (``uncertainty_eval.scale_of`` with ``uncertainty_range``), and "uncertainty_u", the head's own output in [0, 1]."""
         return self._forward(inputs, True)
 
+    def _depth_of(self, disp):
+        """A decoder's scale-0 disparity as the depth ``predict`` returns: full resolution, clamped to the depth range."""
+        return ops.disp_to_depth(disp, (self.height, self.width), self.min_depth, self.max_depth, clamp=True)
+
     def _forward(self, inputs, with_normals_pred):
         # HAMMER_Dataset(raw_color=True) batches; colour sensor frames are demosaicked here, for polar_inputs too
-        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        self._expand(inputs)
         # the Trainer's hand-over: interleaved sensor frames (demosaic), un-split mosaics, raw planes of any of K1's dtypes (device LANCZOS), 612 -> 640 padding
-        normals = pdpolar.polar_inputs(inputs, (self.height, self.width),
-                                       ("xolp", "normals") if self.augment_normals else ("xolp",), self.pol_angles,
-                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        normals = self._polar(inputs, ("xolp", "normals") if self.augment_normals else ("xolp",))
         feats = self.models["rgb_encoder"](inputs["color_aug", 0, 0].float())
         xf = self.models["xolp_encoder"](inputs["xolp", 0, 0].float()) if self.augment_xolp else None
         nf = self.models["normals_encoder"](inputs["xolp", 0, 0].float(), normals=normals) if self.augment_normals else None
         feats = list(feats) + self.models["joint_encoder"](feats[-1], xf, nf)
         dec = self.models["mono_depth"](feats)
-        disp = dec[("disp", 0)].contiguous()
-        N = disp.shape[0]
-        depth = torch.empty((N, 1, self.height, self.width), device=disp.device)
-        check(lib.pd_disp_to_depth(ptr(disp), ptr(depth), None, N, disp.shape[2], disp.shape[3], self.height, self.width,
-                                   self.min_depth, self.max_depth, stream_ptr()), "pd_disp_to_depth")
-        out = {"depth": depth.clamp(self.min_depth, self.max_depth)}
+        out = {"depth": self._depth_of(dec[("disp", 0)])}
         if with_normals_pred and self.uncertainty:            # scale 0 is already H x W
             out["uncertainty_u"] = dec[("uncertainty", 0)].contiguous()
             out["uncertainty"] = uncertainty_eval.scale_of(out["uncertainty_u"], self.uncertainty_range)
         if with_normals_pred and "normals_decoder" in self.models:
             out["normals_pred"] = self.models["normals_decoder"](nf)
         if with_normals_pred and self.polar_refine is not None:
-            pol = normals if self.augment_normals else pdpolar.polar_inputs(
-                inputs, (self.height, self.width), ("xolp", "normals"), self.pol_angles, dofp=self.pol_dofp, cdofp=self.pol_cdofp,
-                calibration=self.pol_calibration)
+            pol = normals if self.augment_normals else self._polar(inputs)
             ref = pdrefine.polar_refine(out["depth"], inputs[("K", 0)], pol, inputs["xolp", 0, 0], aolp_sign=self.aolp_sign,
                                         ray_frame=self.polar_ray_frame, **self.polar_refine)
             out["depth_refined"], out["refine_residual"], out["refine_touched"] = ref.depth, ref.residual, ref.touched
@@ -308,7 +331,7 @@ class Evaluation:
         clamp as ``predict`` ends."""
         if not self.multi_frame:
             raise ValueError("predict_multi needs Evaluation(multi_frame=True)")
-        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        self._expand(inputs)
         ids = self.matching_ids
         lookups = torch.stack([inputs[("color", i, 0)].float() for i in ids[1:]], 1)
         if self.multi_poses == "network":
@@ -321,35 +344,19 @@ class Evaluation:
                                  for i in ids[1:]], 1)
         feats, lowest_cost, confidence = self.models["encoder"](inputs[("color_aug", 0, 0)].float(), lookups, poses,
                                                                 inputs[("K", 2)].float(), inputs[("inv_K", 2)].float())
-        disp = self.models["depth"](feats)[("disp", 0)].contiguous()
-        N = disp.shape[0]
-        depth = torch.empty((N, 1, self.height, self.width), device=disp.device)
-        check(lib.pd_disp_to_depth(ptr(disp), ptr(depth), None, N, disp.shape[2], disp.shape[3], self.height, self.width,
-                                   self.min_depth, self.max_depth, stream_ptr()), "pd_disp_to_depth")
-        return {"depth": depth.clamp(self.min_depth, self.max_depth), "lowest_cost": lowest_cost, "confidence": confidence}
+        return {"depth": self._depth_of(self.models["depth"](feats)[("disp", 0)]), "lowest_cost": lowest_cost,
+                "confidence": confidence}
 
     def test(self):
         """evaluation.py:120-288: mean over images of the 7 masked depth metrics, for the whole frame and per material
         class (instance-mask grey values :242-264).  The per-image reductions run on the device (pd_depth_metrics);
         11 x 8 numbers per batch leave the GPU instead of every depth map."""
-        objects = ["all"] + list(_MATERIAL_GREY)
-        sums = {o: torch.zeros(7, dtype=torch.float64, device=self.device) for o in objects}
-        counts = {o: torch.zeros((), dtype=torch.float64, device=self.device) for o in objects}
-        for inputs in self.test_loader:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
-            depth = self.predict(inputs)
-            for o in objects:
-                m = ops.depth_metrics(inputs["depth_gt"], depth, self.min_depth, self.max_depth,
-                                      mask=None if o == "all" else inputs[("mask", 0, 0)],
-                                      mask_value=_MATERIAL_GREY.get(o, 0))
-                valid = m[:, 7] > 0
-                sums[o] += (m[:, :7].double() * valid[:, None]).sum(0)
-                counts[o] += valid.sum()
-        results = {}
-        for o in objects:
-            if counts[o].item() > 0:
-                results[o] = (sums[o] / counts[o]).cpu().numpy()
-                print(o, ("&{: 8.5f}  " * 7).format(*results[o].tolist()))
+        table = depth_eval.MaterialTable(_MATERIAL_GREY, self.min_depth, self.max_depth, self.device)
+        for inputs in self._batches(self.test_loader):
+            table.add(inputs["depth_gt"], self.predict(inputs), inputs[("mask", 0, 0)])
+        results = table.means()
+        for o, mean_errors in results.items():
+            print(o, ("&{: 8.5f}  " * 7).format(*mean_errors.tolist()))
         return results
 
     @torch.no_grad()
@@ -363,43 +370,16 @@ class Evaluation:
         pixel of the class do not count), "pooled" takes all pixels of all images as one set (the normals literature's).  The
         records stay on the device until the loop is over.  "refined" (``Evaluation(polar_refine=...)``) scores the normals of
         the depth refined with the polarisation normals."""
-        if source not in ("auto", "depth", "decoder", "refined"):
-            raise ValueError(f'source must be "auto", "depth", "decoder" or "refined", got {source!r}')
-        if source == "auto":
-            source = "decoder" if "normals_decoder" in self.models else "depth"
-        if source == "decoder" and "normals_decoder" not in self.models:
-            raise ValueError('source="decoder" needs Evaluation(normals_decoder=True) (or PD_NORMALS_DECODER=1)')
-        if source == "refined" and self.polar_refine is None:
-            raise ValueError('source="refined" needs Evaluation(polar_refine=True) (or PD_POLAR_REFINE=1)')
+        source = self._resolve_source(source, ("auto", "depth", "decoder", "refined"))
         key = {"decoder": "normals_pred", "depth": "depth", "refined": "depth_refined"}[source]
-        total, sums, counts = None, None, None
-        for inputs in self.test_loader:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+        report = ClassReport(normals_eval.METRIC_NAMES)
+        for inputs in self._batches(self.test_loader):
             out = self._forward(inputs, source != "depth")
             st = normals_eval.normals_stats(out[key], inputs["depth_gt"],
                                             inputs[("K", 0)], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
                                             max_depth=self.max_depth)
-            m = st.metrics()
-            valid = st.n > 0
-            s = torch.where(valid[..., None], m, torch.zeros_like(m)).sum(0)
-            if total is None:
-                total, sums, counts = st, s, valid.sum(0)
-            else:
-                total += st
-                sums += s
-                counts += valid.sum(0)
-        if total is None:
-            return {}
-        per_image = sums / counts[:, None].double()
-        per_image, pooled, bad = per_image.cpu().numpy(), total.pooled().cpu().numpy(), total.pooled_bad().cpu().numpy()
-        results = {}
-        print(f"normals ({source}) " + ("{:>9} " * 7).format(*normals_eval.METRIC_NAMES))
-        for k, name in enumerate(total.names):
-            results[name] = {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k])}
-            if pooled[k][6] > 0:
-                print(f"{name:>8} per-image " + ("&{: 9.4f} " * 7).format(*per_image[k].tolist()))
-                print(f"{name:>8} pooled    " + ("&{: 9.4f} " * 7).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
-        return results
+            report.add(st, st.metrics(), st.n > 0)
+        return report.finish(f"normals ({source})")
 
     @torch.no_grad()
     def test_polar_normals(self, source="auto", rho_min=0.05, rho_max=1.0, tilt_min_deg=5.0):
@@ -419,16 +399,9 @@ class Evaluation:
         four counters by name (ints)}: mean, median, rmse (degrees), the shares within 11.25 / 22.5 / 30 degrees, the pixel
         count and the DoLP-weighted mean; "per_image" and "pooled" as in ``test_normals``.  The records stay on the device
         until the loop is over."""
-        if source not in ("auto", "depth", "decoder", "gt"):
-            raise ValueError(f'source must be "auto", "depth", "decoder" or "gt", got {source!r}')
-        if source == "auto":
-            source = "decoder" if "normals_decoder" in self.models else "depth"
-        if source == "decoder" and "normals_decoder" not in self.models:
-            raise ValueError('source="decoder" needs Evaluation(normals_decoder=True) (or PD_NORMALS_DECODER=1)')
-        sets = ("normal", "azimuth")
-        total, sums, counts = None, {}, {}
-        for inputs in self.test_loader:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+        source = self._resolve_source(source, ("auto", "depth", "decoder", "gt"))
+        reports = {s: ClassReport(polar_normals_eval.METRIC_NAMES) for s in ("normal", "azimuth")}
+        for inputs in self._batches(self.test_loader):
             valid = None
             if source == "gt":
                 pred = inputs["depth_gt"].float()
@@ -437,42 +410,17 @@ class Evaluation:
             else:
                 out = self._forward(inputs, source == "decoder")
                 pred = out["normals_pred" if source == "decoder" else "depth"]
-            pol = pdpolar.polar_inputs(inputs, (self.height, self.width), ("xolp", "normals"), self.pol_angles,
-                                       dofp=self.pol_dofp, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
-            st = polar_normals_eval.polar_normals_stats(pred, pol, inputs["xolp", 0, 0], K=inputs[("K", 0)],
+            st = polar_normals_eval.polar_normals_stats(pred, self._polar(inputs), inputs["xolp", 0, 0], K=inputs[("K", 0)],
                                                         mask=inputs[("mask", 0, 0)], valid=valid, rho_min=rho_min,
                                                         rho_max=rho_max, tilt_min_deg=tilt_min_deg, aolp_sign=self.aolp_sign,
                                                         ray_frame=self.polar_ray_frame)
-            for name in sets:
-                rs = getattr(st, name)
-                m = rs.metrics()
-                ok = rs.n > 0
-                s = torch.where(ok[..., None], m, torch.zeros_like(m)).sum(0)
-                sums[name] = s if total is None else sums[name] + s
-                counts[name] = ok.sum(0) if total is None else counts[name] + ok.sum(0)
-            if total is None:
-                total = st
-            else:
-                total += st
-        if total is None:
-            return {}
-        results = {name: {} for name in total.names}
-        nm = len(polar_normals_eval.METRIC_NAMES)
-        for sname in sets:
-            rs = getattr(total, sname)
-            per_image = (sums[sname] / counts[sname][:, None].double()).cpu().numpy()
-            pooled, counters = rs.pooled().cpu().numpy(), rs.pooled_counters().cpu().numpy()
-            frame = ", ray frame" if self.polar_ray_frame else ""
-            print(f"polar {sname} ({source}{frame}) " + ("{:>9} " * nm).format(*polar_normals_eval.METRIC_NAMES))
-            for k, name in enumerate(total.names):
-                r = {"per_image": per_image[k], "pooled": pooled[k]}
-                r.update({c: int(counters[k][j]) for j, c in enumerate(rs.counter_names)})
-                results[name][sname] = r
-                if pooled[k][6] > 0:
-                    print(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
-                    print(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) +
-                          "".join(f" {c} {int(counters[k][j])}" for j, c in enumerate(rs.counter_names)))
-        return results
+            for s, report in reports.items():
+                rs = getattr(st, s)
+                report.add(rs, rs.metrics(), rs.n > 0)
+        frame = ", ray frame" if self.polar_ray_frame else ""
+        counters = lambda rs: dict(zip(rs.counter_names, rs.pooled_counters().unbind(-1)))
+        sets = {s: report.finish(f"polar {s} ({source}{frame})", extras=counters) for s, report in reports.items()}
+        return {name: {s: r[name] for s, r in sets.items()} for name in sets["normal"]}
 
     @torch.no_grad()
     def test_depth(self, median_scaling=None, source="mono"):
@@ -487,43 +435,17 @@ class Evaluation:
         stay on the device until the loop is over.  ``source``: "mono" scores ``predict`` over the test loader, "multi"
         (``multi_frame=True``) ``predict_multi`` over the loader that also serves the lookup frames, "refined"
         (``polar_refine=...``) ``predict_all``'s "depth_refined" -- the same scoring."""
-        if source not in ("mono", "multi", "refined"):
-            raise ValueError(f'source must be "mono", "multi" or "refined", got {source!r}')
-        if source == "multi" and not self.multi_frame:
-            raise ValueError('source="multi" needs Evaluation(multi_frame=True)')
-        if source == "refined" and self.polar_refine is None:
-            raise ValueError('source="refined" needs Evaluation(polar_refine=True) (or PD_POLAR_REFINE=1)')
-        total, sums, counts = None, None, None
-        for inputs in (self.multi_loader if source == "multi" else self.test_loader):
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+        source = self._resolve_source(source, ("mono", "multi", "refined"))
+        report = ClassReport(depth_eval.METRIC_NAMES)
+        for inputs in self._batches(self.multi_loader if source == "multi" else self.test_loader):
             if source == "refined":
                 depth = self.predict_all(inputs)["depth_refined"]
             else:
                 depth = self.predict_multi(inputs)["depth"] if source == "multi" else self.predict(inputs)
             st = depth_eval.depth_stats(depth, inputs["depth_gt"], mask=inputs[("mask", 0, 0)], min_depth=self.min_depth,
                                         max_depth=self.max_depth, median_scaling=median_scaling)
-            m = st.metrics()
-            valid = st.n > 0
-            s = torch.where(valid[..., None], m, torch.zeros_like(m)).sum(0)
-            if total is None:
-                total, sums, counts = st, s, valid.sum(0)
-            else:
-                total += st
-                sums += s
-                counts += valid.sum(0)
-        if total is None:
-            return {}
-        per_image = sums / counts[:, None].double()
-        per_image, pooled, bad = per_image.cpu().numpy(), total.pooled().cpu().numpy(), total.pooled_bad().cpu().numpy()
-        results = {}
-        nm = len(depth_eval.METRIC_NAMES)
-        print(f"depth ({median_scaling or 'unscaled'}) " + ("{:>9} " * nm).format(*depth_eval.METRIC_NAMES))
-        for k, name in enumerate(total.names):
-            results[name] = {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k])}
-            if pooled[k][nm - 1] > 0:
-                print(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
-                print(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
-        return results
+            report.add(st, st.metrics(), st.n > 0)
+        return report.finish(f"depth ({median_scaling or 'unscaled'})")
 
     @torch.no_grad()
     def test_uncertainty(self):
@@ -539,26 +461,23 @@ class Evaluation:
         if not self.uncertainty:
             raise ValueError("test_uncertainty needs Evaluation(uncertainty=True) (or PD_UNCERTAINTY=1)")
         calls = []
-        for inputs in self.test_loader:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+        for inputs in self._batches(self.test_loader):
             out = self._forward(inputs, True)
             calls.append(uncertainty_eval.uncertainty_stats(out["depth"], inputs["depth_gt"], out["uncertainty_u"],
                                                             mask=inputs[("mask", 0, 0)], b_range=self.uncertainty_range,
                                                             min_depth=self.min_depth, max_depth=self.max_depth))
         if not calls:
             return {}
+        # these metrics are NumPy's (the sparsification curves are drawn on the host): every image's in one array, reduced once
         per = np.concatenate([st.metrics() for st in calls], 0)              # [images, K, 10]
-        total = calls[0]
-        for st in calls[1:]:
-            total += st
-        valid = per[..., 9] > 0
+        valid = per[..., uncertainty_eval.METRIC_NAMES.index("n")] > 0
         with np.errstate(invalid="ignore", divide="ignore"):
             per_image = np.where(valid[..., None], per, 0.0).sum(0) / valid.sum(0)[:, None]
-        pooled, bad = total.pooled(), total.pooled_bad().cpu().numpy()
+        report = ClassReport(uncertainty_eval.METRIC_NAMES)
+        for st in calls:
+            report.add(st)
         lo, hi = self.uncertainty_range
-        print(uncertainty_eval.format_report(total.names, per_image, pooled, bad,
-                                             title=f"uncertainty (b from {lo * 1e3:g} to {hi * 1e3:g} mm)"))
-        return {name: {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k])} for k, name in enumerate(total.names)}
+        return report.finish(f"uncertainty (b from {lo * 1e3:g} to {hi * 1e3:g} mm)", per_image=per_image)
 
     @torch.no_grad()
     def predict_poses(self, inputs):
@@ -566,7 +485,7 @@ class Evaluation:
         neighbour on the un-jittered frame pair in temporal order, as Trainer.predict_poses runs it."""
         if not self.pose_network:
             raise ValueError("predict_poses needs Evaluation(pose_network=True) (or PD_POSE_NETWORK=1)")
-        pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        self._expand(inputs)
         cur = inputs[("color", 0, 0)].float()
         out = {}
         for f_i in self.pose_frame_ids:
@@ -588,12 +507,16 @@ class Evaluation:
             raise ValueError("test_pose needs Evaluation(pose_network=True) (or PD_POSE_NETWORK=1)")
         ids = self.pose_frame_ids
         records, valids = [], []
-        for inputs in self.pose_loader:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+        for inputs in self._batches(self.pose_loader):
             T = self.predict_poses(inputs)
             valid = torch.stack([inputs[("frame_valid", i)] for i in ids], 1).float()
             records.append(pose_eval.pair_records([T[i] for i in ids], [inputs[("poses", i)] for i in ids], valid))
             valids.append(valid)
+        return self._pose_report(records, valids, ids)
+
+    @staticmethod
+    def _pose_report(records, valids, ids):
+        """The per-pair records of all batches -> the printed pose table and its dict ({} without a batch)."""
         if not records:
             return {}
         results = pose_eval.metrics_from_records(torch.cat(records, 1), torch.cat(valids, 0), ids)
@@ -612,25 +535,17 @@ class Evaluation:
         ids = [0] + list(range(-1, -1 - int(num_links), -1))
         pdmatching.chain_pairs(ids)
         if num_links not in self._chain_loaders:
-            data_path, files, num_workers = self._loader_args
-            ds = datasets.HAMMER_Dataset(data_path, files, self.height, self.width, ids, 4, is_train=False,
-                                         supervised_depth_only=False, need_poses=True)
-            self._chain_loaders[num_links] = DataLoader(ds, self.batch_size, False, num_workers=num_workers, drop_last=True)
+            self._chain_loaders[num_links] = self._loader(ids, supervised_depth_only=False, need_poses=True)
         records, valids = [], []
-        for inputs in self._chain_loaders[num_links]:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
-            pdcolor.expand_batch(inputs, (self.height, self.width), 4, cdofp=self.pol_cdofp, calibration=self.pol_calibration)
+        for inputs in self._batches(self._chain_loaders[num_links]):
+            self._expand(inputs)
             present = {i: inputs[("frame_valid", i)].float() for i in ids[1:]}
             rel, _ = pdmatching.matching_poses(self.models["pose_encoder"], self.models["pose"],
                                                {i: inputs[("color", i, 0)] for i in ids}, ids, present)
             valid = torch.cumprod(torch.stack([present[i] for i in ids[1:]], 1), 1)
             records.append(pose_eval.pair_records([rel[i] for i in ids[1:]], [inputs[("poses", i)] for i in ids[1:]], valid))
             valids.append(valid)
-        if not records:
-            return {}
-        results = pose_eval.metrics_from_records(torch.cat(records, 1), torch.cat(valids, 0), ids[1:])
-        print(pose_eval.format_report(results))
-        return results
+        return self._pose_report(records, valids, ids[1:])
 
     @torch.no_grad()
     def test_consistency(self, ids=(-1, 1), visible="auto", per_view=False):
@@ -651,14 +566,11 @@ class Evaluation:
         if not ids or 0 in ids or len(ids) > consistency_eval.MAX_FRAMES:
             raise ValueError(f"ids must name 1 .. {consistency_eval.MAX_FRAMES} neighbouring frames, got {ids!r}")
         if ids not in self._consistency_loaders:
-            data_path, files, num_workers = self._loader_args
-            ds = datasets.HAMMER_Dataset(data_path, files, self.height, self.width, [0] + list(ids), 4, is_train=False,
-                                         supervised_depth_only=False, need_poses=True, neighbour_items=True)
-            self._consistency_loaders[ids] = DataLoader(ds, self.batch_size, False, num_workers=num_workers, drop_last=True)
-        to_dev = lambda d: {k: to_dev(v) if isinstance(v, dict) else v.to(self.device) for k, v in d.items()}
-        total, views = None, {i: None for i in ids}
-        for inputs in self._consistency_loaders[ids]:
-            inputs = to_dev(inputs)
+            self._consistency_loaders[ids] = self._loader([0] + list(ids), supervised_depth_only=False, need_poses=True,
+                                                          neighbour_items=True)
+        new = lambda: ClassReport(consistency_eval.METRIC_NAMES, width=11)
+        total, views = new(), {i: new() for i in ids}
+        for inputs in self._batches(self._consistency_loaders[ids]):
             depth0 = self.predict(inputs)
             depths = torch.cat([self.predict(inputs[("neighbour", i)]) for i in ids], 1)
             T = torch.stack([inputs[("poses", i)] for i in ids], 1)
@@ -670,38 +582,18 @@ class Evaluation:
                 gts = torch.cat([inputs[("neighbour", i)]["depth_gt"] for i in ids], 1)
                 vis = consistency_eval.visibility(inputs["depth_gt"], gts, T, K, inv_K, frame_valid=valid,
                                                   min_depth=self.min_depth, max_depth=self.max_depth)
-            st = consistency_eval.consistency(depth0, depths, T, K, inv_K, frame_valid=valid, visible=vis, want=(), **kw)
-            if total is None:
-                total = st
-            else:
-                total += st
+            total.add(consistency_eval.consistency(depth0, depths, T, K, inv_K, frame_valid=valid, visible=vis, want=(), **kw))
             if per_view:
                 for f, i in enumerate(ids):
-                    sv = consistency_eval.consistency(depth0, depths[:, f:f + 1], T[:, f:f + 1], K, inv_K,
-                                                      frame_valid=valid[:, f:f + 1],
-                                                      visible=None if vis is None else vis[:, f:f + 1], want=(), **kw)
-                    if views[i] is None:
-                        views[i] = sv
-                    else:
-                        views[i] += sv
-        if total is None:
-            return {}
-
-        def table(pool, title):
-            n, counters, sums, hist = (t.cpu().numpy() for t in pool._totals())
-            pooled = pool.pooled().cpu().numpy()
-            nm = len(consistency_eval.METRIC_NAMES)
-            print(f"consistency ({title}) " + ("{:>11} " * nm).format(*consistency_eval.METRIC_NAMES))
-            out = {}
-            for k, name in enumerate(pool.names):
-                out[name] = {"pooled": pooled[k], "n": int(n[k]), "counters": counters[k], "sums": sums[k], "hist": hist[k]}
-                if n[k] > 0:
-                    print(f"{name:>8} pooled    " + ("&{: 11.4f} " * nm).format(*pooled[k].tolist()))
-            return out
-
+                    views[i].add(consistency_eval.consistency(depth0, depths[:, f:f + 1], T[:, f:f + 1], K, inv_K,
+                                                              frame_valid=valid[:, f:f + 1],
+                                                              visible=None if vis is None else vis[:, f:f + 1], want=(), **kw))
+        # pooled figures only, and beside them the pool's own fields
+        fields = lambda pool: dict(zip(("n", "counters", "sums", "hist"), pool._totals()))
+        table = lambda report, title: report.finish(f"consistency ({title})", extras=fields, show_extras=False)
         how = "mutually visible pairs" if visible == "auto" else "all pairs"
         results = table(total, f"views {list(ids)}, {how}")
-        if per_view:
+        if per_view and results:
             results["views"] = {i: table(views[i], f"view {i}, {how}") for i in ids}
         return results
 
@@ -716,32 +608,10 @@ class Evaluation:
         "per_image" is the mean over images of the per-image figures (images where either cloud has no point of the class do
         not count), "pooled" takes all points of all images as one set.  ``prune=False`` takes the brute-force route of
         pd_cloud_nn: the same bits, slower.  The records stay on the device until the loop is over."""
-        total, sums, counts = None, None, None
-        for inputs in self.test_loader:
-            inputs = {k: v.to(self.device) for k, v in inputs.items()}
+        report = ClassReport(pointcloud.METRIC_NAMES)
+        for inputs in self._batches(self.test_loader):
             depth = self.predict(inputs)
             st = pointcloud.cloud_stats(depth, inputs["depth_gt"], inputs[("K", 0)], mask=inputs[("mask", 0, 0)],
                                         min_depth=self.min_depth, max_depth=self.max_depth, prune=prune)
-            m = st.metrics()
-            valid = (st.acc.n > 0) & (st.comp.n > 0)
-            s = torch.where(valid[..., None], m, torch.zeros_like(m)).sum(0)
-            if total is None:
-                total, sums, counts = st, s, valid.sum(0)
-            else:
-                total += st
-                sums += s
-                counts += valid.sum(0)
-        if total is None:
-            return {}
-        per_image = (sums / counts[:, None].double()).cpu().numpy()
-        pooled, bad, unmatched = (total.pooled().cpu().numpy(), total.pooled_bad().cpu().numpy(),
-                                  total.pooled_unmatched().cpu().numpy())
-        results = {}
-        print("pointcloud " + ("{:>9} " * 9).format(*pointcloud.METRIC_NAMES))
-        for k, name in enumerate(total.names):
-            results[name] = {"per_image": per_image[k], "pooled": pooled[k], "bad": int(bad[k]), "unmatched": int(unmatched[k])}
-            if pooled[k][8] > 0:
-                print(f"{name:>8} per-image " + ("&{: 9.4f} " * 9).format(*per_image[k].tolist()))
-                print(f"{name:>8} pooled    " + ("&{: 9.4f} " * 9).format(*pooled[k].tolist()) +
-                      f" bad {int(bad[k])} unmatched {int(unmatched[k])}")
-        return results
+            report.add(st, st.metrics(), (st.acc.n > 0) & (st.comp.n > 0))
+        return report.finish("pointcloud", extras=lambda t: {"bad": t.pooled_bad(), "unmatched": t.pooled_unmatched()})

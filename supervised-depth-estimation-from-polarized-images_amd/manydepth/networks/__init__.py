@@ -13,6 +13,30 @@ from .normals_decoder import NormalsDecoder      # `arch1++_separate_normals_dec
 from .pose_decoder import PoseDecoder
 
 
+def build_models(pretrained, dropout_rate, xolp_norm, scales, augment_normals, augment_xolp, attention, uncertainty,
+                 normals_decoder, pose_network):
+    """The ordered model table of the Trainer (trainer.py:192-236) and of Evaluation, which differ in the arguments only.  The
+    order of construction is part of the contract: every module draws its initialisation from torch's generator, so a
+    module added anywhere but at the end changes what the ones behind it draw."""
+    models = {"rgb_encoder": ShallowResnetEncoder(18, pretrained)}
+    if augment_normals:
+        models["normals_encoder"] = ShallowNormalsEncoder(in_channels=9, dropout_rate=dropout_rate)
+    if augment_xolp:
+        models["xolp_encoder"] = ShallowEncoder(mode='XOLP', in_channels=2, dropout_rate=dropout_rate, xolp_norm=xolp_norm)
+    models["joint_encoder"] = JointEncoder(dropout_rate=dropout_rate, include_normals=augment_normals,
+                                           include_xolp=augment_xolp, attention=attention)
+    # with ``uncertainty`` the reference's heads, under its checkpoint names (depth_decoder.py:46-73)
+    models["mono_depth"] = DepthDecoder(models["rgb_encoder"].num_ch_enc, scales, uncertainty=bool(uncertainty))
+    if normals_decoder:                           # `arch1++_separate_normals_dec`
+        if not augment_normals:
+            raise ValueError("the separate normals decoder sits behind the normals encoder: it needs augment_normals")
+        models["normals_decoder"] = NormalsDecoder(64)
+    if pose_network:                              # trainer.py:222-236 for pose_model_type "separate_resnet"
+        models["pose_encoder"] = ResnetEncoder(18, pretrained, num_input_images=2)
+        models["pose"] = PoseDecoder(models["pose_encoder"].num_ch_enc, num_input_features=1, num_frames_to_predict_for=2)
+    return models
+
+
 def _out_of_scope(name):
     class _Placeholder:
         def __init__(self, *a, **k):

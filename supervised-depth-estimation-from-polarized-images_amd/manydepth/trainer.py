@@ -76,6 +76,7 @@ from polardepth import cdofp as pdcdofp
 from polardepth import calibration as pdcal
 from polardepth import color as pdcolor
 from polardepth import ops
+from polardepth import depth_eval
 from polardepth import matching as pdmatching
 from polardepth.engine import ParamStore, FusedAdam, GradReducer
 from polardepth._lib import lib, check, ptr, stream_ptr
@@ -341,38 +342,18 @@ class Trainer:
         assert self.opt.height % 32 == 0, "'height' must be a multiple of 32"
         assert self.opt.width % 32 == 0, "'width' must be a multiple of 32"
 
-        self.models = {}
         self.parameters_to_train = []
         self.num_scales = len(self.opt.scales)
         self.train_teacher_and_pose = not self.opt.freeze_teacher_and_pose
 
-        # MODEL SETUP (trainer.py:192-216)
-        self.models["rgb_encoder"] = networks.ShallowResnetEncoder(18, self.opt.weights_init == "pretrained")
-        if self.opt.augment_normals:
-            self.models["normals_encoder"] = networks.ShallowNormalsEncoder(in_channels=9,
-                                                                            dropout_rate=self.opt.dropout_rate)
-        if self.opt.augment_xolp:
-            self.models["xolp_encoder"] = networks.ShallowEncoder(mode='XOLP', in_channels=2,
-                                                                  dropout_rate=self.opt.dropout_rate, xolp_norm=self.xolp_norm)
-        self.models["joint_encoder"] = networks.JointEncoder(dropout_rate=self.opt.dropout_rate,
-                                                             include_normals=self.opt.augment_normals,
-                                                             include_xolp=self.opt.augment_xolp,
-                                                             attention=_attention_variant(self.opt))
-        if self.uncertainty_loss is not None:     # the reference's heads, under its checkpoint names (depth_decoder.py:46-73)
-            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.opt.scales,
-                                                              uncertainty=True)
+        # MODEL SETUP (trainer.py:192-236)
+        self.models = networks.build_models(
+            self.opt.weights_init == "pretrained", self.opt.dropout_rate, self.xolp_norm, self.opt.scales,
+            self.opt.augment_normals, self.opt.augment_xolp, attention=_attention_variant(self.opt),
+            uncertainty=self.uncertainty_loss is not None, normals_decoder=_normals_decoder_variant(self.opt),
+            pose_network=self.pose_network)
+        if self.uncertainty_loss is not None:
             self.models["mono_depth"].uncertainty_detach = self.uncertainty_detach
-        else:
-            self.models["mono_depth"] = networks.DepthDecoder(self.models["rgb_encoder"].num_ch_enc, self.opt.scales)
-        if _normals_decoder_variant(self.opt):
-            if not self.opt.augment_normals:
-                raise ValueError("the separate normals decoder sits behind the normals encoder: it needs --augment_normals")
-            self.models["normals_decoder"] = networks.NormalsDecoder(64)
-        if self.pose_network:                     # trainer.py:222-236 for pose_model_type "separate_resnet"
-            self.models["pose_encoder"] = networks.ResnetEncoder(18, self.opt.weights_init == "pretrained",
-                                                                 num_input_images=2)
-            self.models["pose"] = networks.PoseDecoder(self.models["pose_encoder"].num_ch_enc, num_input_features=1,
-                                                       num_frames_to_predict_for=2)
         for m in self.models.values():
             m.to(self.device)
         if self.distributed:                    # identical replicas: broadcast rank 0's initialisation
@@ -792,31 +773,17 @@ class Trainer:
         if self.rank == 0:
             print("Running full test set at Epoch: ", self.epoch)
         self.set_eval()
-        objects = ["all"] + list(_MATERIAL_GREY)
-        sums = {o: torch.zeros(7, dtype=torch.float64, device=self.device) for o in objects}
-        counts = {o: torch.zeros((), dtype=torch.float64, device=self.device) for o in objects}
+        table = depth_eval.MaterialTable(_MATERIAL_GREY, self.opt.min_depth, self.opt.max_depth, self.device)
         with torch.no_grad():
             for inputs in self.test_loader:
                 for key, ipt in inputs.items():
                     inputs[key] = ipt.to(self.device)
                 outputs = self._forward_models(inputs)
-                depth = torch.empty_like(inputs["depth_gt"])
-                N, _, H, W = depth.shape
-                d0 = outputs[("disp", 0)].contiguous()
-                check(lib.pd_disp_to_depth(ptr(d0), ptr(depth), None, N, d0.shape[2], d0.shape[3], H, W,
-                                           self.opt.min_depth, self.opt.max_depth, stream_ptr()), "pd_disp_to_depth")
-                for o in objects:
-                    m = ops.depth_metrics(inputs["depth_gt"], depth, self.opt.min_depth, self.opt.max_depth,
-                                          mask=None if o == "all" else inputs[("mask", 0, 0)],
-                                          mask_value=_MATERIAL_GREY.get(o, 0))
-                    valid = m[:, 7] > 0
-                    sums[o] += (m[:, :7].double() * valid[:, None]).sum(0)
-                    counts[o] += valid.sum()
+                depth = ops.disp_to_depth(outputs[("disp", 0)], inputs["depth_gt"].shape[2:], self.opt.min_depth,
+                                          self.opt.max_depth)
+                table.add(inputs["depth_gt"], depth, inputs[("mask", 0, 0)])
         if self.rank == 0:
-            for o in objects:
-                if counts[o].item() == 0:
-                    continue
-                mean_errors = (sums[o] / counts[o]).cpu().numpy()
+            for o, mean_errors in table.means().items():
                 print("\n  " + o + "\n  " + ("{:>8} | " * 7).format("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
                 print(("&{: 8.5f}  " * 7).format(*mean_errors.tolist()) + "\\\\")
                 losses = {metric: np.array(mean_errors[i]) for i, metric in enumerate(self.depth_metric_names)}

@@ -10,6 +10,7 @@ ops.  The definition is the header's; tests/depth_stats_ref.py states it in NumP
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import lib, check, ptr, stream_ptr
 from ._records import Pool, device_table, frames, hist_median, need_cuda
 from .normals_eval import DEFAULT_CLASSES, class_table
@@ -183,3 +184,27 @@ def depth_stats(pred, gt, mask=None, classes=DEFAULT_CLASSES, min_depth=0.1, max
                                  ptr(ws), ws.numel(), N, H, W, float(min_depth), float(max_depth), stream_ptr()),
               "pd_depth_stats")
     return DepthStats(records, names, scale, err)
+
+
+class MaterialTable:
+    """The reference's test table (evaluation.py:120-288, trainer.py:782-980) as one accumulator: per batch the seven figures of
+    ``ops.depth_metrics`` for the whole frame and for every material of ``grey`` {name: the instance mask's grey value}, one
+    launch each, added over the images that have a pixel of the class (fp64, on the device) and counted."""
+
+    def __init__(self, grey, min_depth, max_depth, device):
+        self.grey, self.min_depth, self.max_depth = grey, min_depth, max_depth
+        self.objects = ["all"] + list(grey)
+        self.sums = {o: torch.zeros(7, dtype=torch.float64, device=device) for o in self.objects}
+        self.counts = {o: torch.zeros((), dtype=torch.float64, device=device) for o in self.objects}
+
+    def add(self, gt, depth, mask):
+        for o in self.objects:
+            m = ops.depth_metrics(gt, depth, self.min_depth, self.max_depth, mask=None if o == "all" else mask,
+                                  mask_value=self.grey.get(o, 0))
+            valid = m[:, 7] > 0
+            self.sums[o] += (m[:, :7].double() * valid[:, None]).sum(0)
+            self.counts[o] += valid.sum()
+
+    def means(self):
+        """{class: float64 NumPy [7], the mean over its images} for the classes that some image has: the host reads here."""
+        return {o: (self.sums[o] / self.counts[o]).cpu().numpy() for o in self.objects if self.counts[o].item() > 0}

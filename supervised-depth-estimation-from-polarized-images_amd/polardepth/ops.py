@@ -1108,6 +1108,18 @@ def uncertainty_loss(depth, gt, unc, b_range=None, min_depth=0.1, max_depth=2.0,
     return value[0]
 
 
+def disp_to_depth(disp, size, min_depth, max_depth, clamp=False):
+    """The depth read-out of evaluation: a decoder's disparity [N,1,hs,ws] -> the depth in metres [N,1,H,W] at ``size`` =
+    (H, W) (pd_disp_to_depth), with ``clamp`` limited to [min_depth, max_depth] afterwards.  The loss launches the same
+    kernel for all its scales itself (functional.py)."""
+    disp = disp.contiguous()
+    N, (H, W) = disp.shape[0], size
+    depth = torch.empty((N, 1, H, W), device=disp.device)
+    check(lib.pd_disp_to_depth(ptr(disp), ptr(depth), None, N, disp.shape[2], disp.shape[3], H, W, min_depth, max_depth,
+                               stream_ptr()), "pd_disp_to_depth")
+    return depth.clamp(min_depth, max_depth) if clamp else depth
+
+
 def depth_metrics(gt, pred, min_depth, max_depth, mask=None, mask_value=0):
     """Per-image depth metrics on the device: [N,8] = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, count."""
     _require_cuda(gt, pred, mask)

@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from ._lib import lib, check, ptr, stream_ptr
-from ._records import Pool, frames, need_cuda
+from ._records import Pool, format_table, frames, need_cuda
 from .depth_eval import edges
 from .normals_eval import DEFAULT_CLASSES, class_table
 
@@ -187,10 +187,4 @@ def uncertainty_stats(pred, gt, unc, mask=None, classes=DEFAULT_CLASSES, b_range
 
 def format_report(names, per_image, pooled, bad, title="uncertainty"):
     """The table ``Evaluation.test_uncertainty`` prints: per class the mean over images and the pooled figures."""
-    nm = len(METRIC_NAMES)
-    lines = [f"{title} " + ("{:>9} " * nm).format(*METRIC_NAMES)]
-    for k, name in enumerate(names):
-        if pooled[k][nm - 1] > 0:
-            lines.append(f"{name:>8} per-image " + ("&{: 9.4f} " * nm).format(*per_image[k].tolist()))
-            lines.append(f"{name:>8} pooled    " + ("&{: 9.4f} " * nm).format(*pooled[k].tolist()) + f" bad {int(bad[k])}")
-    return "\n".join(lines)
+    return "\n".join(format_table(title, METRIC_NAMES, names, per_image, pooled, {"bad": bad}))

@@ -1802,6 +1802,44 @@ int pd_polar_refine_steps(const void* coef, const void* table, int iters, int k0
 int pd_polar_refine_finish(const void* depth, const void* coef, const void* zeta, void* depth_out, void* touched,
                            void* residual, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
 
+/* ---- A PER-PIXEL WEIGHT OF THE PRIOR (csrc/polar_refine.hip; NumPy statement: tests/polar_refine_w_ref.py).  The scalar lam
+ * trusts the prior equally everywhere.  Here  E = sum lam_i (zeta - zeta0)^2 + sum w (zeta_b - zeta_a - g)^2  with
+ *     lam_i = lam * w_i,    w_i = weight_min where !(weight >= weight_min)   (a NaN, a zero, a negative),
+ *                                 weight_max where weight > weight_max         (+inf),       else (double)weight
+ * from weight fp32 [N,H,W] (any values), the comparisons in fp64.  Liveness and the edges do not depend on the weight:
+ *     diag = (((lam_i + wE) + wW) + wS) + wN,    rhs = (((lam_i*zeta0 - wE*gE) + wW*gW) - wS*gS) + wN*gN
+ * and everything else is as written above.  THE SPECTRUM: row i of D^-1 A has Gershgorin radius s_i / diag_i and the grid is
+ * still bipartite, so the spectrum lies in [a, 2 - a] with
+ *     a = min over the touched pixels (s_i > 0) of  a_i = lam_i / (lam_i + s_i)
+ * an exact minimum, hence without an order.  With weight == 1 everywhere a equals lam / (lam + S) bit for bit (fp addition and
+ * division are monotone), and so does everything that follows.  a >= lam*weight_min / (lam*weight_min + 4*rho_max): a smaller
+ * weight_min needs more steps for the same residual.
+ * pd_polar_refine_setup_w: pd_polar_refine_setup with the weight; the same zeta0 / coef / pq planes; the workspace (the same
+ *     size) receives per workgroup the minimum of a_i, +inf where the workgroup touches nothing.
+ * pd_polar_refine_table_w: A double [N] = a of the item, 0 where nothing is touched, and table [N][iters][2] by the recurrence
+ *     above started from that a (delta = 1.0 - a, ...); all zero where A is 0, and the item stays at its prior.
+ * pd_polar_refine_step, _steps and _finish take the coefficient planes of either setup.
+ * pd_polar_refine_weights writes a raw map  weight = (float)(u * h),  a lane per pixel, only + - x / :
+ *     u = t*t,  t = (unc_ref * (double)z) / (double)b     from b fp32 [N,H,W], the Laplace scale in metres that the decoder
+ *                 states for its depth z (`depth`); NaN where z or b is not finite or not positive; 1.0 where b is NULL.
+ *                 unc_ref is the relative scale b / z at which the prior has the weight 1.  A Laplace density has the
+ *                 variance 2 b^2: the factor is absorbed in unc_ref.
+ *     h = c / r where r = fabs(zeta_prev - zeta0) > c, else 1.0       a Huber data term solved by iteratively reweighted least
+ *                 squares: zeta_prev double [N,H,W] is the previous round's solution; 1.0 where zeta_prev is NULL (zeta_prev and
+ *                 zeta0 are both given or both NULL).
+ * One launch each; plain vector stores, no atomics, no allocation, no synchronisation; capturable.  N == 0 returns PD_OK after the
+ * checks.  Refusals (PD_EINVAL before any launch): those of setup / table; a null weight; !(0 < weight_min <= weight_max < inf);
+ * !(unc_ref > 0) or not finite when b is given; !(c > 0) or not finite when zeta_prev is given; zeta_prev without zeta0 or the
+ * other way round; misaligned pointers.  unc_ref, weight_min and c are conventions of the caller, not measurements. */
+int pd_polar_refine_setup_w(const void* depth, const void* K_intrinsics, const void* pol_normal, const void* xolp, long ldp,
+                            const void* valid, double lam, double edge_max, double cos_inc, const void* weight,
+                            double weight_min, double weight_max, void* zeta0, void* coef, void* pq, void* workspace,
+                            size_t ws_bytes, int N, int H, int W, void* stream);
+int pd_polar_refine_table_w(const void* workspace, size_t ws_bytes, int iters, void* A, void* table, int N, int H, int W,
+                            void* stream);
+int pd_polar_refine_weights(const void* depth, const void* b, double unc_ref, const void* zeta_prev, const void* zeta0,
+                            double c, void* weight, int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,12 +9,18 @@
 // refine_setup_kernel: a pixel needs liveness, rho, p, q and zeta0 of itself and of its E, W, S, N neighbours.  They are
 //   recomputed (pix_at, five evaluations per pixel, the neighbours' loads hit L2) instead of staged: setup runs once next to
 //   `iters` steps, and the same function on the same inputs gives the same bits on both sides of an edge.
+//   Its second instantiation (<Weight>, pd_polar_refine_setup_w) takes a per-pixel weight of the prior: lam_i = lam * clamp(w)
+//   enters diag and rhs only, and the partial that leaves is the workgroup's MINIMUM of a_i = lam_i / (lam_i + s_i), the lower
+//   end of the spectrum (refine_table_w_kernel reduces it per item).  The steps and finish read coefficient planes and do not
+//   know of the weight.  refine_weights_kernel makes such a map from the decoder's stated uncertainty and, for a robust data
+//   term, from the previous round's solution: a lane per pixel, streaming.
 // refine_step_kernel: one step per launch.  Per pixel and step it reads wE, wS, rhs, idiag, zeta, d (48 B) and writes zeta, d
 //   (16 B); wW, wN and the four neighbours' zeta are re-reads of lines the tile or its neighbour tile fetched.
 #include "pd_common.h"
 #include "depth_normals.hpp"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -36,8 +42,9 @@ __device__ __forceinline__ bool locate(const Geo& g, long& n, int& x, int& y) {
     return x < g.W && y < g.H;
 }
 
-// the workgroup's maximum of v >= 0 into out[blockIdx.x]
-__device__ __forceinline__ void block_max(double v, double* __restrict__ out) {
+// the workgroup's maximum of v >= 0 (MIN: its minimum, +inf = nothing) into out[blockIdx.x]
+template <bool MIN>
+__device__ __forceinline__ void block_reduce(double v, double* __restrict__ out) {
     __shared__ double sm[RT];
     sm[threadIdx.x] = v;
     __syncthreads();
@@ -45,12 +52,14 @@ __device__ __forceinline__ void block_max(double v, double* __restrict__ out) {
     for (int s = RT / 2; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
             const double o = sm[threadIdx.x + s];
-            if (o > sm[threadIdx.x]) sm[threadIdx.x] = o;
+            if (MIN ? o < sm[threadIdx.x] : o > sm[threadIdx.x]) sm[threadIdx.x] = o;
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
 }
+
+__device__ __forceinline__ void block_max(double v, double* __restrict__ out) { block_reduce<false>(v, out); }
 
 struct Pix { bool live; double rho, p, q, zeta; };
 
@@ -94,11 +103,26 @@ __device__ __forceinline__ void edge(const Pix& a, const Pix& b, double ga, doub
     }
 }
 
+// the per-pixel weight of the prior (pd_polar_refine_setup_w); NoWeight is the scalar lam
+struct Weight { const float* map; double lo, hi; };
+struct NoWeight {};
+
+// lam_i of pixel i: lam * clamp(weight_i); a NaN takes the lower end
+__device__ __forceinline__ double lam_at(double lam, const NoWeight&, size_t) { return lam; }
+__device__ __forceinline__ double lam_at(double lam, const Weight& wt, size_t i) {
+    const double w = (double)wt.map[i];
+    return lam * (!(w >= wt.lo) ? wt.lo : w > wt.hi ? wt.hi : w);
+}
+
+// W = NoWeight: the partial is the workgroup's maximum of s.  W = Weight: lam_i = lam * clamp(weight) enters diag and rhs, and
+// the partial is the workgroup's minimum of a_i = lam_i / (lam_i + s) over its touched pixels, +inf where it touches nothing.
+template <class W>
 __global__ __launch_bounds__(RT) void refine_setup_kernel(SetupArgs a, Geo g, double* __restrict__ zeta0, double* __restrict__ coef,
-                                                          double* __restrict__ pq, double* __restrict__ partial) {
+                                                          double* __restrict__ pq, double* __restrict__ partial, W wt) {
+    constexpr bool WT = std::is_same<W, Weight>::value;
     long n; int x, y;
     const bool in = locate(g, n, x, y);
-    double s = 0.0;
+    double s = 0.0, ai = INFINITY;
     if (in) {
         const pd_dn::Cam c = pd_dn::load_cam(a.K, n);
         const Pix m = pix_at(a, g, c, n, x, y), e = pix_at(a, g, c, n, x + 1, y), w = pix_at(a, g, c, n, x - 1, y),
@@ -109,8 +133,9 @@ __global__ __launch_bounds__(RT) void refine_setup_kernel(SetupArgs a, Geo g, do
         edge(m, so, m.q, so.q, a.edge_max, wS, gS);
         edge(no, m, no.q, m.q, a.edge_max, wN, gN);
         s = ((wE + wW) + wS) + wN;
-        const double diag = (((a.lam + wE) + wW) + wS) + wN;
-        const double rhs = (((a.lam * m.zeta - wE * gE) + wW * gW) - wS * gS) + wN * gN;
+        const double lam = lam_at(a.lam, wt, (size_t)n * g.P + (size_t)y * g.W + x);
+        const double diag = (((lam + wE) + wW) + wS) + wN;
+        const double rhs = (((lam * m.zeta - wE * gE) + wW * gW) - wS * gS) + wN * gN;
         const size_t o = (size_t)y * g.W + x;
         zeta0[(size_t)n * g.P + o] = m.zeta;
         double* cf = coef + (size_t)n * 4 * g.P + o;
@@ -119,19 +144,20 @@ __global__ __launch_bounds__(RT) void refine_setup_kernel(SetupArgs a, Geo g, do
             pq[(size_t)n * 2 * g.P + o] = m.p;
             pq[(size_t)n * 2 * g.P + g.P + o] = m.q;
         }
+        if (WT && s > 0.0) ai = lam / (lam + s);
     }
-    block_max(s, partial);
+    block_reduce<WT>(WT ? ai : s, partial);
 }
 
-// one workgroup per item: the maximum of its `per` partials; lane 0 goes on with fin(n, max)
-template <class F>
-__device__ __forceinline__ void item_max(const double* __restrict__ partial, int per, F fin) {
+// one workgroup per item: the maximum (MIN: the minimum, +inf = nothing) of its `per` partials; lane 0 goes on with fin(n, it)
+template <bool MIN, class F>
+__device__ __forceinline__ void item_reduce(const double* __restrict__ partial, int per, F fin) {
     __shared__ double sm[RT];
     const long n = blockIdx.x;
-    double m = 0.0;
+    double m = MIN ? (double)INFINITY : 0.0;
     for (int i = threadIdx.x; i < per; i += RT) {
         const double v = partial[n * per + i];
-        if (v > m) m = v;
+        if (MIN ? v < m : v > m) m = v;
     }
     sm[threadIdx.x] = m;
     __syncthreads();
@@ -139,31 +165,48 @@ __device__ __forceinline__ void item_max(const double* __restrict__ partial, int
     for (int s = RT / 2; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
             const double o = sm[threadIdx.x + s];
-            if (o > sm[threadIdx.x]) sm[threadIdx.x] = o;
+            if (MIN ? o < sm[threadIdx.x] : o > sm[threadIdx.x]) sm[threadIdx.x] = o;
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) fin(n, sm[0]);
 }
 
+template <class F>
+__device__ __forceinline__ void item_max(const double* __restrict__ partial, int per, F fin) { item_reduce<false>(partial, per, fin); }
+
+// the Chebyshev scalars of one item from the lower end a of its spectrum; zeros where there is none
+__device__ __forceinline__ void write_table(double* __restrict__ t, int iters, bool any, double a) {
+    if (!any) {
+        for (int k = 0; k < 2 * iters; ++k) t[k] = 0.0;
+        return;
+    }
+    const double delta = 1.0 - a, sigma = 1.0 / delta;
+    double rho = 1.0 / sigma;
+    t[0] = 0.0; t[1] = 1.0;
+    for (int k = 1; k < iters; ++k) {
+        const double rk = 1.0 / (2.0 * sigma - rho);
+        t[2 * k] = rk * rho;
+        t[2 * k + 1] = (2.0 * rk) / delta;
+        rho = rk;
+    }
+}
+
 __global__ __launch_bounds__(RT) void refine_table_kernel(const double* __restrict__ partial, int per, double lam, int iters,
                                                           double* __restrict__ S, double* __restrict__ table) {
     item_max(partial, per, [&](long n, double s) {
         S[n] = s;
-        double* t = table + (size_t)n * iters * 2;
-        if (!(s > 0.0) || !__builtin_isfinite(s)) {
-            for (int k = 0; k < 2 * iters; ++k) t[k] = 0.0;
-            return;
-        }
-        const double a = lam / (lam + s), delta = 1.0 - a, sigma = 1.0 / delta;
-        double rho = 1.0 / sigma;
-        t[0] = 0.0; t[1] = 1.0;
-        for (int k = 1; k < iters; ++k) {
-            const double rk = 1.0 / (2.0 * sigma - rho);
-            t[2 * k] = rk * rho;
-            t[2 * k + 1] = (2.0 * rk) / delta;
-            rho = rk;
-        }
+        write_table(table + (size_t)n * iters * 2, iters, s > 0.0 && __builtin_isfinite(s), lam / (lam + s));
+    });
+}
+
+// the weighted route: the partials are minima of a_i, +inf where a workgroup touches nothing
+__global__ __launch_bounds__(RT) void refine_table_w_kernel(const double* __restrict__ partial, int per, int iters,
+                                                            double* __restrict__ A, double* __restrict__ table) {
+    item_reduce<true>(partial, per, [&](long n, double a) {
+        const bool any = a > 0.0 && __builtin_isfinite(a);
+        A[n] = any ? a : 0.0;
+        write_table(table + (size_t)n * iters * 2, iters, any, a);
     });
 }
 
@@ -218,6 +261,26 @@ __global__ __launch_bounds__(RT) void refine_finish_kernel(const float* __restri
         if (!(ar >= 0.0)) ar = 0.0;               // a NaN is ignored
     }
     block_max(ar, partial);
+}
+
+// the raw weight of the prior, (float)(u * h), a lane per pixel over the whole batch (streaming: 4 to 28 bytes per pixel):
+// u = ((unc_ref z) / b)^2 from the stated Laplace scale b, h = min(1, c / |zeta_prev - zeta0|) from the previous solution
+__global__ __launch_bounds__(RT) void refine_weights_kernel(const float* __restrict__ depth, const float* __restrict__ b, double unc_ref,
+                                                            const double* __restrict__ zeta_prev, const double* __restrict__ zeta0,
+                                                            double c, float* __restrict__ weight, size_t total) {
+    const size_t i = (size_t)blockIdx.x * RT + threadIdx.x;
+    if (i >= total) return;
+    double u = 1.0, h = 1.0;
+    if (b) {
+        const float z = depth[i], bi = b[i];
+        const double t = (unc_ref * (double)z) / (double)bi;
+        u = __builtin_isfinite(z) && z > 0.f && __builtin_isfinite(bi) && bi > 0.f ? t * t : (double)NAN;
+    }
+    if (zeta_prev) {
+        const double r = fabs(zeta_prev[i] - zeta0[i]);
+        if (r > c) h = c / r;
+    }
+    weight[i] = (float)(u * h);
 }
 
 // T consecutive steps k0 .. k0 + T - 1 in one launch (overlapped tiling): a workgroup owns FW x FH pixels of one item and holds
@@ -372,9 +435,9 @@ extern "C" int pd_polar_refine_setup(const void* depth, const void* K_intrinsics
     const Geo g = geo_of(H, W);
     SetupArgs a{static_cast<const float*>(depth), static_cast<const float*>(K_intrinsics), static_cast<const float4*>(pol_normal),
                 static_cast<const float*>(xolp), static_cast<const unsigned char*>(valid), (size_t)ldp, lam, edge_max, cos_inc};
-    hipLaunchKernelGGL(refine_setup_kernel, dim3((unsigned)(N * tiles_of(H, W))), dim3(RT), 0, (hipStream_t)stream, a, g,
+    hipLaunchKernelGGL(refine_setup_kernel<NoWeight>, dim3((unsigned)(N * tiles_of(H, W))), dim3(RT), 0, (hipStream_t)stream, a, g,
                        static_cast<double*>(zeta0), static_cast<double*>(coef), static_cast<double*>(pq),
-                       static_cast<double*>(workspace));
+                       static_cast<double*>(workspace), NoWeight{});
     return pd::check_launch(who);
 }
 
@@ -391,6 +454,69 @@ extern "C" int pd_polar_refine_table(const void* workspace, size_t ws_bytes, dou
     hipLaunchKernelGGL(refine_table_kernel, dim3((unsigned)N), dim3(RT), 0, (hipStream_t)stream,
                        static_cast<const double*>(workspace), (int)tiles_of(H, W), lam, iters, static_cast<double*>(S),
                        static_cast<double*>(table));
+    return pd::check_launch(who);
+}
+
+extern "C" int pd_polar_refine_setup_w(const void* depth, const void* K_intrinsics, const void* pol_normal, const void* xolp,
+                                       long ldp, const void* valid, double lam, double edge_max, double cos_inc, const void* weight,
+                                       double weight_min, double weight_max, void* zeta0, void* coef, void* pq, void* workspace,
+                                       size_t ws_bytes, int N, int H, int W, void* stream) {
+    const char* who = "pd_polar_refine_setup_w";
+    if (int e = shape_args(who, N, H, W)) return e;
+    PD_REQUIRE(depth && K_intrinsics && pol_normal && xolp && weight && zeta0 && coef,
+               "%s: depth, K, pol_normal, xolp, weight, zeta0 and coef must not be null", who);
+    PD_REQUIRE(ldp >= W, "%s: the row pitch ldp = %ld must be at least W = %d", who, ldp, W);
+    PD_REQUIRE(std::isfinite(lam) && lam > 0.0, "%s: lam = %g must be finite and > 0", who, lam);
+    PD_REQUIRE(std::isfinite(edge_max) && edge_max >= 0.0, "%s: edge_max = %g must be finite and >= 0", who, edge_max);
+    PD_REQUIRE(cos_inc > 0.0 && cos_inc <= 1.0, "%s: cos_inc = %g must be in (0, 1]: the cosine of an incidence limit below 90 degrees",
+               who, cos_inc);
+    PD_REQUIRE(0.0 < weight_min && weight_min <= weight_max && std::isfinite(weight_max),
+               "%s: the clamp must be 0 < weight_min <= weight_max < inf, got [%g, %g]", who, weight_min, weight_max);
+    PD_REQUIRE(pd::aligned16(pol_normal) && pd::aligned8(zeta0) && pd::aligned8(coef) && pd::aligned8(pq) && pd::aligned4(depth) &&
+               pd::aligned4(K_intrinsics) && pd::aligned4(xolp) && pd::aligned4(weight),
+               "%s: pol_normal must be 16-byte aligned, zeta0, coef and pq 8-byte aligned, depth, K, xolp and weight 4-byte aligned", who);
+    if (int e = ws_args(who, workspace, ws_bytes, N, H, W)) return e;
+    if (N == 0) return PD_OK;
+    const Geo g = geo_of(H, W);
+    SetupArgs a{static_cast<const float*>(depth), static_cast<const float*>(K_intrinsics), static_cast<const float4*>(pol_normal),
+                static_cast<const float*>(xolp), static_cast<const unsigned char*>(valid), (size_t)ldp, lam, edge_max, cos_inc};
+    const Weight wt{static_cast<const float*>(weight), weight_min, weight_max};
+    hipLaunchKernelGGL(refine_setup_kernel<Weight>, dim3((unsigned)(N * tiles_of(H, W))), dim3(RT), 0, (hipStream_t)stream, a, g,
+                       static_cast<double*>(zeta0), static_cast<double*>(coef), static_cast<double*>(pq),
+                       static_cast<double*>(workspace), wt);
+    return pd::check_launch(who);
+}
+
+extern "C" int pd_polar_refine_table_w(const void* workspace, size_t ws_bytes, int iters, void* A, void* table, int N, int H, int W,
+                                       void* stream) {
+    const char* who = "pd_polar_refine_table_w";
+    if (int e = shape_args(who, N, H, W)) return e;
+    PD_REQUIRE(A && table, "%s: A and table must not be null", who);
+    PD_REQUIRE(iters >= 1, "%s: iters = %d must be at least 1", who, iters);
+    PD_REQUIRE(pd::aligned8(A) && pd::aligned8(table), "%s: A and table must be 8-byte aligned", who);
+    if (int e = ws_args(who, workspace, ws_bytes, N, H, W)) return e;
+    if (N == 0) return PD_OK;
+    hipLaunchKernelGGL(refine_table_w_kernel, dim3((unsigned)N), dim3(RT), 0, (hipStream_t)stream,
+                       static_cast<const double*>(workspace), (int)tiles_of(H, W), iters, static_cast<double*>(A),
+                       static_cast<double*>(table));
+    return pd::check_launch(who);
+}
+
+extern "C" int pd_polar_refine_weights(const void* depth, const void* b, double unc_ref, const void* zeta_prev, const void* zeta0,
+                                       double c, void* weight, int N, int H, int W, void* stream) {
+    const char* who = "pd_polar_refine_weights";
+    if (int e = shape_args(who, N, H, W)) return e;
+    PD_REQUIRE(depth && weight, "%s: depth and weight must not be null", who);
+    PD_REQUIRE(!b || (std::isfinite(unc_ref) && unc_ref > 0.0), "%s: unc_ref = %g must be finite and > 0 when b is given", who, unc_ref);
+    PD_REQUIRE(!zeta_prev == !zeta0, "%s: zeta_prev and zeta0 must both be given or both be null", who);
+    PD_REQUIRE(!zeta_prev || (std::isfinite(c) && c > 0.0), "%s: c = %g must be finite and > 0 when zeta_prev is given", who, c);
+    PD_REQUIRE(pd::aligned4(depth) && pd::aligned4(b) && pd::aligned4(weight) && pd::aligned8(zeta_prev) && pd::aligned8(zeta0),
+               "%s: depth, b and weight must be 4-byte aligned, zeta_prev and zeta0 8-byte aligned", who);
+    if (N == 0) return PD_OK;
+    const size_t total = (size_t)N * H * W;
+    hipLaunchKernelGGL(refine_weights_kernel, dim3((unsigned)((total + RT - 1) / RT)), dim3(RT), 0, (hipStream_t)stream,
+                       static_cast<const float*>(depth), static_cast<const float*>(b), unc_ref, static_cast<const double*>(zeta_prev),
+                       static_cast<const double*>(zeta0), c, static_cast<float*>(weight), total);
     return pd::check_launch(who);
 }
 

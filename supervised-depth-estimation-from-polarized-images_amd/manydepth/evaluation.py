@@ -40,15 +40,18 @@ def _switch(value, env_on):
     return env_on if value is None else bool(value)
 
 
-_REFINE_OPTIONS = ("lam", "iters", "edge_max", "incidence_max_deg", "rho_min", "rho_max", "rounds")
+_REFINE_OPTIONS = ("lam", "iters", "edge_max", "incidence_max_deg", "rho_min", "rho_max", "rounds", "uncertainty", "unc_ref",
+                   "robust", "weight_min", "weight_max")
 
 
-def _polar_refine_option(value):
-    """Evaluation(polar_refine=) / $PD_POLAR_REFINE -> None (off) or the dict of options ``polar_refine`` is called with."""
+def _polar_refine_option(value, unc=None, robust=None):
+    """Evaluation(polar_refine=) / $PD_POLAR_REFINE -> None (off) or the dict of options ``polar_refine`` is called with.
+    ``unc`` / ``robust``: $PD_POLAR_REFINE_UNCERTAINTY ("1", or a number giving unc_ref) and $PD_POLAR_REFINE_ROBUST (c; rounds
+    becomes 2 unless it is given); they fill what the options leave open and mean nothing while the refinement is off."""
     if value is None or value is False or value in ("", "0"):
         return None
     if value is True or value == "1":
-        return {}
+        value = {}
     if isinstance(value, str):
         parts = value.split(",")
         if len(parts) != 2:
@@ -57,8 +60,19 @@ def _polar_refine_option(value):
     if not isinstance(value, dict) or set(value) - set(_REFINE_OPTIONS):
         raise ValueError(f"polar_refine must be True or a dict with keys of {_REFINE_OPTIONS}, got {value!r}")
     opts = dict(value)
+    if unc not in (None, "", "0") and "uncertainty" not in opts:
+        opts["uncertainty"] = True
+        if unc != "1":
+            opts.setdefault("unc_ref", float(unc))
+    if robust not in (None, "", "0") and "robust" not in opts:
+        opts["robust"] = float(robust)
+        opts.setdefault("rounds", 2)
     d = {"lam": 0.02, "iters": 100, "edge_max": 0.05, "incidence_max_deg": 80.0, "rounds": 1}
     pdrefine._check_solver_args(**{k: opts.get(k, v) for k, v in d.items()})
+    pdrefine._check_weight_args(opts.get("unc_ref", 0.002), opts.get("robust"), opts.get("weight_min", 1 / 16),
+                                opts.get("weight_max", 1.0), opts.get("rounds", 1))
+    if "uncertainty" in opts and not isinstance(opts["uncertainty"], bool):
+        raise ValueError(f"polar_refine's uncertainty is a switch (True / False), got {opts['uncertainty']!r}")
     return opts
 
 
@@ -118,9 +132,16 @@ class Evaluation:
         polarisation normals it disambiguates ("depth_refined", "refine_residual", "refine_touched"), and ``test_depth`` /
         ``test_normals`` take ``source="refined"``.  None reads $PD_POLAR_REFINE: "1" = the defaults (conventions, not
         measurements), "lam,iters" = those two.  It honours ``aolp_sign`` and ``polar_ray_frame``.  Without it not a bit of any
-        call or report changes."""
-        self.polar_refine = _polar_refine_option(_option(polar_refine, "PD_POLAR_REFINE"))
+        call or report changes.  Further keys: ``uncertainty`` (True: the prior is weighted per pixel with the Laplace scale the
+        decoder states, ``predict_all``'s "uncertainty"; it needs ``uncertainty=True``), ``unc_ref``, ``robust``, ``weight_min``,
+        ``weight_max`` as ``polar_refine`` takes them.  $PD_POLAR_REFINE_UNCERTAINTY = "1" or a number giving ``unc_ref``, and
+        $PD_POLAR_REFINE_ROBUST = c (``rounds`` becomes 2 unless it is given), fill what the options leave open."""
+        self.polar_refine = _polar_refine_option(_option(polar_refine, "PD_POLAR_REFINE"),
+                                                 os.environ.get("PD_POLAR_REFINE_UNCERTAINTY"), os.environ.get("PD_POLAR_REFINE_ROBUST"))
         self.uncertainty = _switch(uncertainty, os.environ.get("PD_UNCERTAINTY") == "1")
+        if self.polar_refine is not None and self.polar_refine.get("uncertainty") and not self.uncertainty:
+            raise ValueError('polar_refine={"uncertainty": True} weights the prior with the decoder\'s stated uncertainty: it needs '
+                             "Evaluation(uncertainty=True) (or PD_UNCERTAINTY=1)")
         if isinstance(uncertainty_range, str):
             uncertainty_range = [float(x) for x in uncertainty_range.split(",")]
         if uncertainty_range is not None and not self.uncertainty:
@@ -314,8 +335,10 @@ class Evaluation:
             out["normals_pred"] = self.models["normals_decoder"](nf)
         if with_normals_pred and self.polar_refine is not None:
             pol = normals if self.augment_normals else self._polar(inputs)
+            opts = dict(self.polar_refine)
+            opts["uncertainty"] = out["uncertainty"] if opts.pop("uncertainty", False) else None
             ref = pdrefine.polar_refine(out["depth"], inputs[("K", 0)], pol, inputs["xolp", 0, 0], aolp_sign=self.aolp_sign,
-                                        ray_frame=self.polar_ray_frame, **self.polar_refine)
+                                        ray_frame=self.polar_ray_frame, **opts)
             out["depth_refined"], out["refine_residual"], out["refine_touched"] = ref.depth, ref.residual, ref.touched
         return out
 

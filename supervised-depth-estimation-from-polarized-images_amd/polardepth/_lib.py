@@ -187,6 +187,10 @@ SIGNATURES = {
     "pd_polar_refine_step": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pd_polar_refine_steps": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pd_polar_refine_finish": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pd_polar_refine_setup_w": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _dbl, _dbl, _dbl, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp, _sz, _i, _i,
+                                     _i, _vp]),
+    "pd_polar_refine_table_w": (_i, [_vp, _sz, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "pd_polar_refine_weights": (_i, [_vp, _vp, _dbl, _vp, _vp, _dbl, _vp, _i, _i, _i, _vp]),
 }
 
 

@@ -8,7 +8,13 @@ bytes ONE one-step iteration touches, counted here from the shapes -- per pixel 
 zeta and d written (16) -- timed the same way, and the same step written with torch ops in fp64 on the same coefficients.
 The fused route's result is compared with the one-step route's bit for bit at every size it is timed at.  One JSON line per
 measurement, printed and written to ``--out`` (default: profiles/polar_refine.log).  It needs the GPU: there is no CPU
-fallback."""
+fallback.
+
+``--weighted`` measures the per-pixel weight of the prior instead (default ``--out``: profiles/polar_refine_weighted.log), at
+B = 12 at 320x480 and B = 16 at 512x640: pd_polar_refine_setup_w next to pd_polar_refine_setup, pd_polar_refine_weights (both
+sources: 28 bytes per pixel) next to a device copy of its bytes, and the whole route -- ``polardepth.refine.solve`` without a
+weight, with a weight made from the uncertainty (one more launch), and the two rounds of the robust route -- alternating in one
+run."""
 import argparse
 import json
 import math
@@ -170,12 +176,103 @@ def bench(N, H, W, iters, reps, emit):
     emit(dict(base, what="steps_torch_fp64", steps=n_t, ms=ms[0], us_per_step=1e3 * ms[0] / n_t, max_abs_diff_to_kernel=diff))
 
 
+WEIGHT_BYTES = 4 + 4 + 8 + 8 + 4          # per pixel: depth, b, zeta_prev, zeta0 read, the weight written
+
+
+def _alternate(routes, reps):
+    """{name: (median, min, max) ms} of the calls, alternating rep by rep inside one window."""
+    import torch
+    for call in routes.values():
+        call()
+    evs = {name: [] for name in routes}
+    for _ in range(reps):
+        for name, call in routes.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            evs[name].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {}
+    for name, pairs in evs.items():
+        ts = sorted(a.elapsed_time(b) for a, b in pairs)
+        out[name] = (ts[len(ts) // 2], ts[0], ts[-1])
+    return out
+
+
+def bench_weighted(N, H, W, iters, reps, emit):
+    import torch
+    from polardepth import refine
+    from polardepth._lib import lib, check, ptr, stream_ptr
+    depth, K, normal, xolp = make_inputs(N, H, W)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    b = (0.002 + 0.02 * torch.rand(depth.shape, device="cuda", generator=g)).contiguous()       # 2 .. 22 mm
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device="cuda")
+    zeta0, coef = f64(N, H, W), f64(N, 4, H, W)
+    ws = torch.empty(int(lib.pd_polar_refine_workspace(N, H, W)), dtype=torch.uint8, device="cuda")
+    cos_inc = math.cos(math.radians(INCIDENCE_MAX_DEG))
+    st = stream_ptr()
+    px = N * H * W
+    base = {"shape": [N, H, W], "iters": iters}
+    wmap = refine.weights(depth, b)
+
+    def setup():
+        check(lib.pd_polar_refine_setup(ptr(depth), ptr(K), ptr(normal), ptr(xolp), W, None, LAM, EDGE_MAX, cos_inc, ptr(zeta0),
+                                        ptr(coef), None, ptr(ws), ws.numel(), N, H, W, st), "setup")
+
+    def setup_w():
+        check(lib.pd_polar_refine_setup_w(ptr(depth), ptr(K), ptr(normal), ptr(xolp), W, None, LAM, EDGE_MAX, cos_inc, ptr(wmap),
+                                          1 / 16, 1.0, ptr(zeta0), ptr(coef), None, ptr(ws), ws.numel(), N, H, W, st), "setup_w")
+
+    ms = _alternate({"setup": setup, "setup_w": setup_w}, max(reps, 20))
+    emit(dict(base, what="setup_w_next_to_setup", setup_ms=ms["setup"][0], setup_w_ms=ms["setup_w"][0],
+              setup_w_over_setup=ms["setup_w"][0] / ms["setup"][0], setup_minmax=ms["setup"][1:], setup_w_minmax=ms["setup_w"][1:]))
+
+    zprev, wout = zeta0 + 0.004 * torch.randn(zeta0.shape, device="cuda", dtype=torch.float64, generator=g), torch.empty_like(depth)
+    half = px * WEIGHT_BYTES // 2
+    src, dst = torch.empty(half, dtype=torch.uint8, device="cuda").fill_(1), torch.empty(half, dtype=torch.uint8, device="cuda")
+
+    def weights():
+        check(lib.pd_polar_refine_weights(ptr(depth), ptr(b), 0.002, ptr(zprev), ptr(zeta0), 0.005, ptr(wout), N, H, W, st), "weights")
+
+    ms = _alternate({"weights": weights, "copy": lambda: dst.copy_(src)}, max(reps, 20))
+    emit(dict(base, what="weights_next_to_a_copy_of_its_bytes", bytes=2 * half, weights_us=1e3 * ms["weights"][0],
+              copy_us=1e3 * ms["copy"][0], weights_over_copy=ms["weights"][0] / ms["copy"][0],
+              weights_gbps=2 * half / (ms["weights"][0] * 1e-3) / 1e9, copy_gbps=2 * half / (ms["copy"][0] * 1e-3) / 1e9))
+    del src, dst
+
+    args = (depth, K, normal, xolp, W, None, LAM, iters, EDGE_MAX, INCIDENCE_MAX_DEG)
+
+    def scalar():
+        return refine.solve(*args)
+
+    def weighted():
+        return refine.solve(*args, weight=refine.weights(depth, b))
+
+    def robust():
+        z0 = f64(N, H, W)
+        zeta = refine.solve(*args, zeta0_out=z0)[3]
+        return refine.solve(*args, weight=refine.weights(depth, None, 0.002, zeta, z0, 0.005))
+
+    ones = refine.solve(*args, weight=torch.ones_like(depth))
+    equal = all(bool(torch.equal(x, y)) for x, y in zip(ones, scalar()))
+    res = {"scalar": float(scalar()[1].max()), "weighted": float(weighted()[1].max()), "robust": float(robust()[1].max())}
+    ms = _alternate({"scalar": scalar, "weighted": weighted, "robust_two_rounds": robust}, reps)
+    emit(dict(base, what="route", weight_one_equals_scalar_bits=equal, scalar_ms=ms["scalar"][0], weighted_ms=ms["weighted"][0],
+              robust_two_rounds_ms=ms["robust_two_rounds"][0], weighted_over_scalar=ms["weighted"][0] / ms["scalar"][0],
+              robust_over_two_scalar=ms["robust_two_rounds"][0] / (2 * ms["scalar"][0]), scalar_minmax=ms["scalar"][1:],
+              weighted_minmax=ms["weighted"][1:], residual_max=res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "polar_refine.log"))
+    ap.add_argument("--weighted", action="store_true", help="measure the per-pixel weight of the prior instead")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "polar_refine_weighted.log" if args.weighted else "polar_refine.log")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_polar_refine.py needs the GPU: there is no CPU fallback")
@@ -186,8 +283,8 @@ def main():
             print(line, flush=True)
             f.write(line + "\n")
             f.flush()
-        for N, H, W in SIZES:
-            bench(N, H, W, args.iters, args.reps, emit)
+        for N, H, W in SIZES[1:] if args.weighted else SIZES:
+            (bench_weighted if args.weighted else bench)(N, H, W, args.iters, args.reps, emit)
 
 
 if __name__ == "__main__":

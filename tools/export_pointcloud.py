@@ -18,6 +18,9 @@ predicted points whose stated uncertainty -- the Laplace scale b of the decoder'
 ``--refine`` exports the predicted depth refined with the polarisation normals it disambiguates
 (``polardepth.refine.polar_refine``; ``--refine_lam X --refine_iters N`` replace the conventional 0.02 and 100): the fine relief
 of ``--normals polar`` then lies in the points too, and every later option acts on the refined depth.
+``--refine_uncertainty [TAU]`` weights the prior per pixel with the uncertainty the decoder states (``polar_refine``'s
+``uncertainty=``, TAU = ``unc_ref``, 0.002 without a value; it needs weights trained with ``opt.uncertainty_loss``), and
+``--refine_robust C`` adds a second, reweighted round with the Huber threshold C in log depth (``robust=``, ``rounds=2``).
 ``gt.ply`` is unchanged."""
 import argparse
 import os
@@ -28,7 +31,8 @@ sys.path.insert(0, os.path.join(ROOT, "supervised-depth-estimation-from-polarize
 
 
 def export(data_path, weights, index, out, height=320, width=480, flip=True, consistent=None, normals=None, aolp_sign=None,
-           ray_frame=None, max_uncertainty_mm=None, refine=False, refine_lam=None, refine_iters=None):
+           ray_frame=None, max_uncertainty_mm=None, refine=False, refine_lam=None, refine_iters=None, refine_uncertainty=None,
+           refine_robust=None):
     import torch
     from torch.utils.data.dataloader import default_collate
     from manydepth.evaluation import Evaluation
@@ -37,9 +41,17 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True, con
         raise ValueError(f'--normals takes "polar" or "depth", got {normals!r}')
     if not refine and (refine_lam is not None or refine_iters is not None):
         raise ValueError("--refine_lam and --refine_iters are options of --refine")
-    more = {} if max_uncertainty_mm is None else {"uncertainty": True}
+    if not refine and (refine_uncertainty is not None or refine_robust is not None):
+        raise ValueError("--refine_uncertainty and --refine_robust are options of --refine")
+    more = {} if max_uncertainty_mm is None and refine_uncertainty is None else {"uncertainty": True}
     if refine:
         more["polar_refine"] = {k: v for k, v in (("lam", refine_lam), ("iters", refine_iters)) if v is not None}
+        if refine_uncertainty is not None:          # True: the conventional unc_ref
+            more["polar_refine"]["uncertainty"] = True
+            if refine_uncertainty is not True:
+                more["polar_refine"]["unc_ref"] = float(refine_uncertainty)
+        if refine_robust is not None:
+            more["polar_refine"].update(robust=float(refine_robust), rounds=2)
     ev = Evaluation(load_weights_folder=weights, data_path=data_path, height=height, width=width, batch_size=1,
                     aolp_sign=aolp_sign, polar_ray_frame=ray_frame, **more)
     ev.load_mono_model()
@@ -59,7 +71,7 @@ def export(data_path, weights, index, out, height=320, width=480, flip=True, con
         depth, gt_gate = consistent_depth(ev, index, depth, gt, int(consistent))
     else:
         gt_gate = gt
-    if scale is not None:                         # the head's own statement of where the prediction should not be trusted
+    if max_uncertainty_mm is not None:            # the head's own statement of where the prediction should not be trusted
         gt_gate = torch.where(scale * 1e3 <= float(max_uncertainty_mm), gt_gate, torch.zeros_like(gt_gate))
     clouds = {"pred": pc.backproject(depth, K, gate=gt_gate, min_depth=ev.min_depth, max_depth=ev.max_depth),
               "gt": pc.backproject(gt, K, min_depth=ev.min_depth, max_depth=ev.max_depth)}
@@ -140,8 +152,12 @@ if __name__ == "__main__":
     ap.add_argument("--refine", action="store_true", help="export the depth refined with the polarisation normals")
     ap.add_argument("--refine_lam", type=float, default=None, metavar="X", help="--refine: the weight of the prior (0.02)")
     ap.add_argument("--refine_iters", type=int, default=None, metavar="N", help="--refine: Chebyshev steps (100)")
+    ap.add_argument("--refine_uncertainty", nargs="?", type=float, const=True, default=None, metavar="TAU",
+                    help="--refine: weight the prior per pixel with the decoder's stated uncertainty (unc_ref = TAU, 0.002)")
+    ap.add_argument("--refine_robust", type=float, default=None, metavar="C",
+                    help="--refine: a second, reweighted round with the Huber threshold C in log depth")
     args = ap.parse_args()
     for path, n in export(args.data_path, args.weights, args.index, args.out, args.height, args.width, not args.no_flip,
                           args.consistent, args.normals, args.aolp_sign, args.ray_frame, args.max_uncertainty_mm, args.refine,
-                          args.refine_lam, args.refine_iters).items():
+                          args.refine_lam, args.refine_iters, args.refine_uncertainty, args.refine_robust).items():
         print(f"{path}: {n} points")
